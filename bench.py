@@ -69,6 +69,28 @@ def measured_clock_hz(key):
     return g * 1e9 if g else None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, records, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the records of the last timed step, one DIR/<field>.npy per field of the 48-byte record
+    (float fields as float32, integer fields as float64, both exact).  Above `limit_bytes` in all, a fixed seeded
+    sample of the sectors is written instead, in sector order, and DIR/sector.npy names them."""
+    fields = records.dtype.names
+    out_dtype = {k: np.float32 if records.dtype[k].base == np.float32 else np.float64 for k in fields}
+    per_record = sum(np.dtype(out_dtype[k]).itemsize * max(1, int(np.prod(records.dtype[k].shape))) for k in fields)
+    pick = None
+    if len(records) * per_record > limit_bytes:
+        n = max(1, (limit_bytes - 4096) // (per_record + 8))   # (sector.npy: one float64 per record; 4 kB for the headers)
+        pick = np.sort(np.random.default_rng(0).choice(len(records), size=n, replace=False))
+        records = records[pick]
+    os.makedirs(out_dir, exist_ok=True)
+    for k in fields:
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(records[k], out_dtype[k]))
+    if pick is not None:
+        np.save(os.path.join(out_dir, "sector.npy"), pick.astype(np.float64))
+
+
 def cpu_baseline(wl, und, dfm, budget_sectors):
     """The CPU oracle (a port of the reference's CPU engine, oracle/lk_oracle.c) timed on
     this box's host cores on a bounded sample of the same workload."""
@@ -639,8 +661,8 @@ def native_group_bench(args, ca, wl):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps of the headline measurement")
+    ap.add_argument("--warmup", type=int, default=20, help="untimed steps before them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sectors", type=int, default=10000)
     ap.add_argument("--no-other-configs", action="store_true")
@@ -664,7 +686,14 @@ def main():
                     help="C2 (default, the headline: weak scaling, every rank its own 10k-sector grid); "
                          "C4 / C4B / C5: ONE pair of that config with its sector grid sharded over the ranks "
                          "(strong scaling; frame broadcast + record all-gather per round)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last one (all ranks' records, gathered, "
+                         "when N > 1) as DIR/<field>.npy (float32 / float64, 64 MB at most)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.native and args.dump_outputs:
+        ap.error("--dump-outputs is not available with --native (its timed steps leave their records on the devices)")
 
     import torch
     import correlation_amd as ca
@@ -802,6 +831,14 @@ def main():
     dt = time.perf_counter() - t0
     m_last, j_last = divmod(pending["k"] - 1, R)
     res = d_ress[m_last % 2][j_last][:S].cpu().numpy().view(ca.RESULT_DTYPE).reshape(-1)   # the last timed step's records
+    if args.dump_outputs and rank == 0:
+        if use_dist:   # what the ranks received: the all-gathered blocks of that step, rank after rank
+            counts = [shard_range(wl.hs * wl.vs, r, world)[1] if strong else S for r in range(world)]
+            blocks = d_alls[m_last % 2][:, j_last].contiguous().cpu().numpy()
+            recs = np.concatenate([blocks[r, :counts[r]].reshape(-1).view(ca.RESULT_DTYPE) for r in range(world)])
+        else:
+            recs = res
+        dump_outputs(args.dump_outputs, recs)
 
     # The dominant kernel of the SAME engine on the SAME stream: per-launch duration measured live
     # with HIP events around K back-to-back solve launches (no pyramid launches in between), then

@@ -2,7 +2,8 @@
 """Generate tests/golden/*.npz from the REFERENCE'S OWN objects (oracle/_ref).
 
 Run in the build container only (needs /root/reference; `make -C oracle ref` first):
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py          # every file below
+    python tests/golden/make_golden.py pins     # ref_pins.npz only
 Only the pieces of the reference that compile without third-party stand-ins are
 available: ModelClass_* (model_class.cpp), polygonBlob_class (polygon_class.cpp) and the
 helpers of parameters.cpp.  The vectors are inputs + the reference's outputs (data, not
@@ -10,11 +11,15 @@ source).  Everything else on the hot path has no reference-generated golden vect
 ("parity unpinned", DESIGN.md).
 """
 import os
+import re
+import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+REF = os.environ.get("REF", "/root/reference")
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from oracle import lk_oracle as lo  # noqa: E402
 
@@ -25,11 +30,54 @@ def star(cx, cy, r0, r1, n, phase=0.0):
     return np.stack([cx + r * np.cos(t), cy + r * np.sin(t)], 1).astype(np.float32)
 
 
-def main():
+def ref_lib():
     R = lo.ref_lib()
     if R is None:
         raise SystemExit("oracle/_ref/libref_pieces.so missing: run `make -C oracle ref` where "
                          "/root/reference exists")
+    return R
+
+
+def pins():
+    """ref_pins.npz: what tests/test_oracle_pins.py and tests/test_ffi_host.py compare against the reference -
+    its literal 16x16 bicubic table (interpolation_class.cpp:539-558, the numbers), polygonBlob_class's outputs on
+    20 seeded random contours, and the values and layout of the declarations the adapter uses (tests/host/
+    ref_types_probe.cpp compiled against the reference's enums.hpp / domains.hpp)."""
+    R = ref_lib()
+    F = lo._fp
+    out = {}
+    src = open(os.path.join(REF, "interpolation_class.cpp")).read()
+    m = re.search(r"float\s+temp1\[256\]\s*=\s*\{(.*?)\};", src, re.S)
+    table = np.array([float(t) for t in m.group(1).replace("\n", " ").split(",") if t.strip()], np.float32)
+    assert table.size == 256
+    out["bicubic_table"] = table
+    rng = np.random.default_rng(99)
+    for i in range(20):
+        nv = int(rng.integers(3, 24))
+        t = np.sort(rng.uniform(0, 2 * np.pi, nv))
+        r = rng.uniform(20, 90, nv)
+        c = np.ascontiguousarray(np.stack([120 + r * np.cos(t), 110 + r * np.sin(t)], 1), np.float32)
+        n = R.ref_blob_points(F(c), nv, None, 0)
+        out[f"random{i}_contour"] = c
+        out[f"random{i}_count"] = np.array([n], np.int64)
+        if n > 0:
+            pts = np.zeros((n, 2), np.float32)
+            R.ref_blob_points(F(c), nv, F(pts), n)
+            assert np.array_equal(pts, np.round(pts))
+            out[f"random{i}_pts"] = pts.astype(np.int16)  # integer valued; compact
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "probe")
+        subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + REF,
+                        os.path.join(os.path.dirname(HERE), "host", "ref_types_probe.cpp"), "-o", exe], check=True)
+        lines = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
+    out["types_names"] = np.array([ln.rsplit(" ", 1)[0] for ln in lines])
+    out["types_values"] = np.array([int(ln.rsplit(" ", 1)[1]) for ln in lines], np.int64)
+    np.savez_compressed(os.path.join(HERE, "ref_pins.npz"), **out)
+    print("wrote ref_pins.npz")
+
+
+def main():
+    R = ref_lib()
     F = lo._fp
     rng = np.random.default_rng(123)
 
@@ -83,7 +131,8 @@ def main():
     rot = np.array([R.ref_best_rotation(F(np.ascontiguousarray(p))) for p in ps], np.float32)
     np.savez_compressed(os.path.join(HERE, "ref_rotation.npz"), p=ps, angle=rot)
     print("wrote ref_model.npz ref_blob.npz ref_rotation.npz")
+    pins()
 
 
 if __name__ == "__main__":
-    main()
+    pins() if sys.argv[1:] == ["pins"] else main()

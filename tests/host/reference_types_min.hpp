@@ -1,9 +1,9 @@
 // reference_types_min.hpp - TEST INFRASTRUCTURE: the handful of reference declarations that
 // include/lk_cuda_class_adapter.hpp uses (enums.hpp:10-35,73-78; domains.hpp:10,59,110-118),
-// restated so that the adapter can be compiled and RUN on a box without /root/reference (the
-// GPU box).  The CPU test suite compiles the adapter against the reference's real headers
-// (tests/test_ffi_host.py) - that is what pins the real layout; this file only has to agree
-// with the adapter's static_assert on the 48-byte record.
+// restated so that the adapter can be compiled and RUN without the reference tree.  The values
+// and layout are pinned to the reference's real headers: tests/host/ref_types_probe.cpp prints
+// them, tests/golden/ref_pins.npz holds what it printed against the reference, and
+// tests/test_ffi_host.py compares.
 #pragma once
 #include <utility>
 #include <vector>

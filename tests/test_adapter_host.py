@@ -14,12 +14,11 @@ import correlation_amd as ca
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "tests", "host")
-REF = "/root/reference"
 
 
 def ref_include():
-    """the reference's own headers where they exist, else the test-only restatement of the few types"""
-    return REF if os.path.isdir(REF) else os.path.join(HOST, "ref_min")
+    """the test-only restatement of the few reference types (pinned to the reference's own: tests/test_ffi_host.py)"""
+    return os.path.join(HOST, "ref_min")
 
 
 def write_frames(tmp_path, frames):

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -80,8 +81,33 @@ def check_line(d, n1):
 def test_command_line_of_the_driver():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs"):
         assert flag in r.stdout
+
+
+def test_dump_outputs_writes_every_record_field(tmp_path):
+    """--dump-outputs: one DIR/<field>.npy per field of the 48-byte record, float32 or float64, values exact; above the
+    size limit a seeded sample of the sectors (the same one every run), named by DIR/sector.npy."""
+    import bench
+    from correlation_amd import RESULT_DTYPE
+    rng = np.random.default_rng(5)
+    rec = np.zeros(1000, RESULT_DTYPE)
+    rec["p"] = rng.normal(size=(1000, 6))
+    rec["chi"] = rng.random(1000)
+    rec["n_points"], rec["iterations"], rec["error_code"] = 361, rng.integers(1, 50, 1000), rng.integers(0, 4, 1000)
+    rec["und_cx"], rec["und_cy"] = rng.random(1000) * 2048, rng.random(1000) * 2048
+    bench.dump_outputs(str(tmp_path / "all"), rec)
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(f"{k}.npy" for k in RESULT_DTYPE.names)
+    for k in RESULT_DTYPE.names:
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, rec[k]), k
+    limit = 20000
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), rec, limit_bytes=limit)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= limit
+    pick = np.load(tmp_path / "s1" / "sector.npy")
+    assert 0 < len(pick) < 1000 and np.array_equal(pick, np.load(tmp_path / "s2" / "sector.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "p.npy"), rec["p"][pick.astype(np.int64)])
 
 
 @pytest.mark.parametrize("pattern,n1", [("profiles/r0[3-9]_bench.json", True), ("profiles/r0[3-9]_bench_dist_rehearsal.json", False)])

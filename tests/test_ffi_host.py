@@ -86,11 +86,24 @@ def test_speckle_generator_is_deterministic():
     assert np.array_equal(a1, a2) and np.array_equal(b1, b2) and not np.array_equal(a1, b1)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference headers not present on this box")
 def test_cuda_class_adapter_compiles_against_reference_headers(tmp_path):
-    """include/lk_cuda_class_adapter.hpp is meant to be compiled inside the reference tree
-    (it uses the reference's own enums.hpp / domains.hpp): check that it does."""
+    """include/lk_cuda_class_adapter.hpp is meant to be compiled inside the reference tree (it uses the reference's
+    own enums.hpp / domains.hpp): check that it compiles against tests/host/ref_min, whose values and layout must be
+    the reference headers' own (tests/host/ref_types_probe.cpp, compiled against the reference by make_golden.py ->
+    tests/golden/ref_pins.npz)."""
     import subprocess
+    ref_min = os.path.join(ROOT, "tests", "host", "ref_min")
+    probe = tmp_path / "probe"
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", ref_min,
+                        os.path.join(ROOT, "tests", "host", "ref_types_probe.cpp"), "-o", str(probe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(probe)], capture_output=True, text=True)
+    assert r.returncode == 0
+    got = [ln.rsplit(" ", 1) for ln in r.stdout.splitlines()]
+    g = np.load(os.path.join(ROOT, "tests", "golden", "ref_pins.npz"))
+    assert [k for k, _ in got] == list(g["types_names"])
+    assert [int(v) for _, v in got] == list(g["types_values"])
     src = tmp_path / "adapter_check.cpp"
     src.write_text('#include "lk_cuda_class_adapter.hpp"\n'
                    "int main() { HipCudaClass c; frame_results fr{}; float g[6] = {0};\n"
@@ -98,7 +111,7 @@ def test_cuda_class_adapter_compiles_against_reference_headers(tmp_path):
                    "  CorrelationResult *r = c.correlate(0, g, fr); v_points p = c.getUndXY0ToCPU(0);\n"
                    "  return (int)p.size() + (int)r->errorCode + (int)c.resetPolygon(0, 1, 2, 3, 4); }\n")
     r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-I", "/root/reference", "-c", str(src), "-o", str(tmp_path / "a.o")],
+                        "-I", ref_min, "-c", str(src), "-o", str(tmp_path / "a.o")],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 

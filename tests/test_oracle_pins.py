@@ -1,18 +1,16 @@
-"""Pins of the CPU oracle against what the reference itself provides in this image:
+"""Pins of the CPU oracle against what the reference itself provides:
  - golden vectors produced by the reference's own ModelClass_* / polygonBlob_class objects
    (tests/golden/make_golden.py, built by oracle/Makefile `ref`);
- - the reference's literal 16x16 bicubic table, read as text when /root/reference exists.
+ - the reference's literal 16x16 bicubic table (tests/golden/ref_pins.npz, the numbers of its text).
 Everything else of the hot path is "parity unpinned" (DESIGN.md): the reference has no
 tests or fixtures and its CPU engine needs OpenCV + Eigen, absent from this image.
 """
 import os
-import re
 
 import numpy as np
-import pytest
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-REF = "/root/reference"
+REF_LIB = os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref", "libref_pieces.so")
 
 
 def test_model_matches_reference_goldens(oracle):
@@ -43,15 +41,11 @@ def test_blob_matches_reference_goldens(oracle):
             assert np.array_equal(pts, g[f"{name}_pts"].astype(np.float32)), name
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present on this box")
 def test_bicubic_matrix_equals_reference_table(oracle):
     """The derived (exact-inverse) matrix equals the literal table of
-    interpolation_class.cpp:539-558, parsed from the reference's text."""
-    src = open(os.path.join(REF, "interpolation_class.cpp")).read()
-    m = re.search(r"float\s+temp1\[256\]\s*=\s*\{(.*?)\};", src, re.S)
-    assert m
-    ref = np.array([float(t) for t in m.group(1).replace("\n", " ").split(",") if t.strip()], np.float32)
-    assert ref.size == 256
+    interpolation_class.cpp:539-558 (its numbers, stored by make_golden.py in ref_pins.npz)."""
+    ref = np.load(os.path.join(GOLD, "ref_pins.npz"))["bicubic_table"]
+    assert ref.dtype == np.float32 and ref.size == 256
     hdr = open(os.path.join(os.path.dirname(GOLD), "..", "oracle", "lk_bicubic_matrix.h")).read()
     start = hdr.index("LKO_BICUBIC_M[256] = {")
     body = hdr[hdr.index("{", start) + 1:hdr.rindex("}")]
@@ -60,27 +54,28 @@ def test_bicubic_matrix_equals_reference_table(oracle):
     assert np.array_equal(mine, ref)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref",
-                                                    "libref_pieces.so")),
-                    reason="partial reference build not present")
 def test_oracle_vs_live_reference_pieces(oracle):
-    """Fresh random cases straight against oracle/_ref (beyond the committed goldens)."""
-    R = oracle.ref_lib()
-    rng = np.random.default_rng(99)
+    """20 seeded random contours against polygonBlob_class (beyond the hand-made goldens): its outputs stored by
+    make_golden.py in ref_pins.npz and, where oracle/_ref was built, the reference's objects live on the same cases."""
+    g = np.load(os.path.join(GOLD, "ref_pins.npz"))
+    R = oracle.ref_lib() if os.path.exists(REF_LIB) else None
     F = oracle._fp
-    for _ in range(20):
-        nv = int(rng.integers(3, 24))
-        t = np.sort(rng.uniform(0, 2 * np.pi, nv))
-        r = rng.uniform(20, 90, nv)
-        c = np.ascontiguousarray(np.stack([120 + r * np.cos(t), 110 + r * np.sin(t)], 1), np.float32)
-        n = R.ref_blob_points(F(c), nv, None, 0)
+    for i in range(20):
+        c = g[f"random{i}_contour"]
+        n = int(g[f"random{i}_count"][0])
         mine = oracle.blob_points(c)
         if n < 0:
-            assert mine is None
+            assert mine is None, i
         else:
-            out = np.zeros((max(n, 1), 2), np.float32)
-            R.ref_blob_points(F(c), nv, F(out), n)
-            assert mine is not None and len(mine) == n and np.array_equal(mine, out[:n])
+            assert mine is not None and len(mine) == n, i
+            if n:
+                assert np.array_equal(mine, g[f"random{i}_pts"].astype(np.float32)), i
+        if R is not None:
+            assert R.ref_blob_points(F(c), len(c), None, 0) == n, i
+            if n > 0:
+                out = np.zeros((n, 2), np.float32)
+                R.ref_blob_points(F(c), len(c), F(out), n)
+                assert np.array_equal(mine, out), i
 
 
 def test_oracle_regression_vectors(oracle):
