@@ -288,12 +288,13 @@ struct lk_engine {
   std::vector<unsigned> ring_window;    // per slot: the last window that read it (+ 1; 0: none)
   hipEvent_t seq_done[4] = {nullptr, nullptr, nullptr, nullptr}; // recorded behind window w on the engine's stream: [w % 4]
   unsigned seq_windows = 0;             // windows launched so far
+  uint64_t window_safe_reruns = 0;      // windows solved again with the SAFE flavour (lk_stats)
   DevBuf<lk_result> d_seq_result;       // [frames][S]
   DevBuf<uint32_t> d_seq_stats;         // [frames][S][4]
   DevBuf<float> d_seq_guess;            // [frames][S][6] (LK_SEQ_CHECK / tests)
-  DevBuf<unsigned long long> d_seq_chain;
+  DevBuf<unsigned long long> d_seq_chain, d_seq_chain_safe; // (the SAFE pass behind the fast flavour has a chain of its own)
   DevBuf<LkSeqFrame> d_seq_img;
-  DevBuf<uint32_t> d_seq_flags;         // [4]: wait bound hit, bad pivot in the fast flavour
+  DevBuf<uint32_t> d_seq_flags;         // [4]: wait bound hit, bad pivot in the fast flavour; wait bound hit in the SAFE pass
   DevBuf<float> d_prev_p_alt;           // previous_resulting_parameters as the window's last frame leaves them
   struct SeqWindow {
     int und_slot = -1, first_slot = 0, n_frames = 0, reference_previous = 0, velocity = 0, want_host = 0, want_guesses = 0;
@@ -435,6 +436,7 @@ void lk_destroy(lk_engine *e) {
   e->d_seq_stats.release();
   e->d_seq_guess.release();
   e->d_seq_chain.release();
+  e->d_seq_chain_safe.release();
   e->d_seq_img.release();
   e->d_seq_flags.release();
   e->d_prev_p_alt.release();
@@ -2921,7 +2923,7 @@ static bool seq_pipelinable(const lk_engine *e) {
 
 // one window on the device: the pipelined launches, or - domains with classes that have no such instance (teams,
 // workgroup-wide groups) - the frames one after the other through the ordinary launches, same buffers either way
-static int launch_window(lk_engine *e, bool force_safe_flavour) {
+static int launch_window(lk_engine *e) {
   lk_engine::SeqWindow &w = e->seq;
   const int S = e->S, n = w.n_frames, R = (int)e->ring.size();
   const DevImage &u0 = w.und_slot >= 0 ? e->ring[(size_t)w.und_slot] : e->img[LK_IMG_UND];
@@ -2977,6 +2979,11 @@ static int launch_window(lk_engine *e, bool force_safe_flavour) {
     int n_classes = 0, n_launched = 0;
     for (int c = 0; c < kNumClasses; ++c)
       n_classes += e->class_begin[c + 1] > e->class_begin[c];
+    struct SafePass {
+      LkSolveArgs a;
+      int group;
+    };
+    std::vector<SafePass> safe_pass; // the classes that run the fast flavour
     if (n_classes > 1) { // classes are independent sector sets: side by side, as in launch_all
       if (!e->ev_fork)
         HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
@@ -3012,7 +3019,7 @@ static int launch_window(lk_engine *e, bool force_safe_flavour) {
       a.seq_flags = e->d_seq_flags.p;
       if (const char *f = std::getenv("LK_SEQ_FAULT")) // test hook, read per launch: a frame that never publishes
         a.seq_fault = std::atoi(f);
-      int flavour = (force_safe_flavour || safe_flavour(e) || e->class_starved[c]) ? 1 : 0;
+      int flavour = (safe_flavour(e) || e->class_starved[c]) ? 1 : 0;
       if (e->reference_order > 0) {
         flavour = 2;
         a.reference_order = e->reference_order;
@@ -3036,7 +3043,7 @@ static int launch_window(lk_engine *e, bool force_safe_flavour) {
         // rows, aligned / not: 0.50 / 0.59 ms per pair)
         if (n0 <= (long long)small_n0 * nc && nc > latency_nc) {
           a.align = 0;
-          if (!safe_flavour(e) && !force_safe_flavour) {
+          if (!safe_flavour(e)) {
             flavour = 2;
             a.reference_order = 1;
             a.mark_stale = -1; // (a first evaluation that fails reports 0 iterations, like every default-mode instance)
@@ -3044,12 +3051,31 @@ static int launch_window(lk_engine *e, bool force_safe_flavour) {
         }
       }
       a.safe = flavour != 0;
-      HIPCHK(lk_launch_solve_seq(a, e->cfg.fitting_model, e->cfg.interpolation, seq_group_of_class(e, c, nc), flavour, st));
+      const int group = seq_group_of_class(e, c, nc);
+      HIPCHK(lk_launch_solve_seq(a, e->cfg.fitting_model, e->cfg.interpolation, group, flavour, st));
       if (st != e->stream) {
         HIPCHK(hipEventRecord(e->ev_join[c], st));
         HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join[c], 0));
       }
       ++n_launched;
+      if (flavour == 0)
+        safe_pass.push_back({a, group});
+    }
+    // A bad pivot in the fast flavour (d_seq_flags[1]; textureless sectors): the window of those classes again with the
+    // SAFE instances - same guesses, same history, the records and sequence state overwritten.  Decided on the device, behind
+    // every class of the window: the gated launches leave at once while the flag is 0, and the window's done-event (which
+    // releases its ring slots to lk_sequence_set_frame) and records follow them.  A chain and a void flag of its own: nothing
+    // is reset between the passes.  (Classes that borrow the reference-order instance keep their records: they met no pivot.)
+    if (!safe_pass.empty()) {
+      HIPCHK(e->d_seq_chain_safe.ensure((size_t)S * kLkSeqChainWords));
+      HIPCHK(hipMemsetAsync(e->d_seq_chain_safe.p, 0, (size_t)S * kLkSeqChainWords * sizeof(unsigned long long), e->stream));
+      for (SafePass &sp : safe_pass) {
+        sp.a.seq_chain = e->d_seq_chain_safe.p;
+        sp.a.seq_flags = e->d_seq_flags.p + 2;
+        sp.a.seq_gate = e->d_seq_flags.p + 1;
+        sp.a.safe = 1;
+        HIPCHK(lk_launch_solve_seq(sp.a, e->cfg.fitting_model, e->cfg.interpolation, sp.group, 1, e->stream));
+      }
     }
     // reference-order mode: the stale iteration counts, in the order the reference solves - frame by frame, sector by
     // sector, which IS the layout of the window's records
@@ -3193,7 +3219,7 @@ int lk_correlate_sequence_async(lk_engine *e, int und_slot, int first_slot, int 
       return rc;
   }
   Range range_("lk:solve window");
-  int rc = launch_window(e, false);
+  int rc = launch_window(e);
   if (rc)
     return rc;
   HIPCHK(hipEventRecord(e->seq_done[e->seq_windows % 4], e->stream));
@@ -3217,19 +3243,10 @@ int lk_wait_sequence(lk_engine *e, lk_result *out) {
   w.outstanding = false;
   const int S = e->S, n = w.n_frames;
   if (w.pipelined) {
-    if (e->h_seq_flags[0] != 0u)
+    if (e->h_seq_flags[1] != 0u) // (the SAFE pass of launch_window solved the fast flavour's classes again)
+      ++e->window_safe_reruns;
+    if (e->h_seq_flags[0] != 0u || e->h_seq_flags[2] != 0u)
       return e->fail(LK_ERROR_DEVICE, "lk_wait_sequence: a sector's wait for its previous frame ran into its bound - the window is void");
-    if (e->h_seq_flags[1] != 0u) {
-      // a bad pivot in the fast flavour: the whole window again with the SAFE instances (same guesses, same history -
-      // the sequence state is only committed below)
-      int rc = launch_window(e, true);
-      if (rc)
-        return rc;
-      HIPCHK(hipEventRecord(e->seq_done[(e->seq_windows + 3) % 4], e->stream)); // (this window's event, again)
-      HIPCHK(hipEventSynchronize(e->ev_seq));
-      if (e->h_seq_flags[0] != 0u)
-        return e->fail(LK_ERROR_DEVICE, "lk_wait_sequence: a sector's wait for its previous frame ran into its bound - the window is void");
-    }
     // commit the sequence state: previous_resulting_parameters (the last frame but one), the engine's own record buffer
     if (n >= 2)
       HIPCHK(hipMemcpyAsync(e->d_prev_p.p, e->d_prev_p_alt.p, 6 * (size_t)S * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
@@ -3419,6 +3436,7 @@ int lk_get_stats(lk_engine *e, lk_stats *out) {
     if (hipEventSynchronize(e->ev_p1) == hipSuccess && hipEventElapsedTime(&ms, e->ev_p0, e->ev_p1) == hipSuccess)
       e->stats.pyramid_ms = ms;
   }
+  e->stats.window_safe_reruns = e->window_safe_reruns;
   *out = e->stats;
   return LK_ERROR_NONE;
 }

@@ -1064,6 +1064,7 @@ int lk_group_get_stats(lk_group *g, lk_stats *out) {
     s.point_iterations += q.point_iterations;
     s.algorithmic_bytes += q.algorithmic_bytes;
     s.ill_conditioned_solves += q.ill_conditioned_solves;
+    s.window_safe_reruns += q.window_safe_reruns;
     s.solve_ms = std::max(s.solve_ms, q.solve_ms);
     s.pyramid_ms = std::max(s.pyramid_ms, q.pyramid_ms);
   }

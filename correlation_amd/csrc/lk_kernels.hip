@@ -1950,6 +1950,12 @@ template <int MODEL, int INTERP, int GROUP, int THREADS, bool SAFE, bool REF = f
 __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAFE && !REF ? 4 : LK_MIN_WAVES) : THREADS == 512 ? LK_MIN_WAVES_512 : 1)) lk_solve_kernel(LkSolveArgs a) {
   static_assert(!REF || (SAFE && ((THREADS == kWave && (GROUP == 16 || GROUP == kWave)) || (THREADS == 512 && GROUP == 512))), "reference-order instances");
   static_assert(!SEQ || (THREADS == kWave && GROUP >= 16 && GROUP <= kWave), "frame-pipelined instances: one wavefront per workgroup");
+  if constexpr (SEQ) {
+    // the SAFE pass of a window (lk_engine.cpp: launch_window): enqueued behind the fast flavour on the same stream, so the
+    // flag is final here - no bad pivot, nothing to solve again
+    if (a.seq_gate && __hip_atomic_load(a.seq_gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+      return;
+  }
   constexpr int P = n_params(MODEL);
   using SumsT = Sums<P>;
   constexpr bool COLD_IN_LDS = GROUP > 1 && GROUP <= kWave;
@@ -2703,8 +2709,9 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
           ++k.n_ill;
         if constexpr (SEQ && !SAFE) {
           // fast flavour inside a window: there is no second pass to hand the sector to (its next frame waits for this
-          // one).  The step of the bad parameter is zero and the host is told: it solves the window again with the SAFE
-          // instances (never seen on textured images: lk_stats.ill_conditioned_solves is 0 on configs 2 and 5).
+          // one).  The step of the bad parameter is zero and the flag is raised: the SAFE pass enqueued behind this launch
+          // solves the class's window again (never seen on textured images: lk_stats.ill_conditioned_solves is 0 on configs
+          // 2 and 5; textureless sectors do it - tests/test_sequence_oracle_gpu.py).
           if (!wc && (int)threadIdx.x % GROUP == 0)
             __hip_atomic_store(a.seq_flags + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -4244,8 +4251,9 @@ static hipError_t launch_solve_seq_gs(const LkSolveArgs &a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// flavour: 0 fast (root-free Cholesky; a bad pivot raises seq_flags[1]), 1 SAFE (the QR inside the kernel; 16-lane rows:
-// starved levels with the finisher's arithmetic), 2 reference order (a.reference_order = T)
+// flavour: 0 fast (root-free Cholesky; a bad pivot raises seq_flags[1], the seq_gate of the SAFE pass behind it), 1 SAFE
+// (the QR inside the kernel; 16-lane rows: starved levels with the finisher's arithmetic), 2 reference order
+// (a.reference_order = T)
 template <int MODEL, int INTERP>
 static hipError_t launch_solve_seq_mi(const LkSolveArgs &a, int group, int flavour, hipStream_t st) {
   if (flavour == 2) {

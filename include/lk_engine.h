@@ -94,6 +94,8 @@ typedef struct {
   uint64_t ill_conditioned_solves; /* damped solves (outside starved levels) that met a bad pivot */
   float solve_ms;             /* HIP-event time of the solve kernel(s) of the last call */
   float pyramid_ms;           /* HIP-event time of the last pyramid build */
+  uint64_t window_safe_reruns;/* since lk_create: frame-pipelined windows whose fast flavour met a bad pivot and were
+                               * solved again with the SAFE flavour */
 } lk_stats;
 
 typedef struct lk_engine lk_engine;
@@ -297,7 +299,9 @@ int lk_wait_results(lk_engine *e, lk_result *out);
  * Records: the arithmetic of a (frame, sector) is the one-pair kernels' - in batch-invariant and in reference-order
  * mode the window's records are byte-identical to solving the pairs one after the other with
  * lk_adjust_initial_guess + lk_correlate_all*.  The default mode uses the fixed lane groups and the fast flavour
- * inside a window (a window in which a damped system meets a bad pivot is solved again with the SAFE flavour).
+ * inside a window; if a damped system meets a bad pivot there, the same launch solves the window of the fast classes again
+ * with the SAFE flavour (a pass gated on the device), before the window's ring slots are released and its records copied
+ * (lk_stats.window_safe_reruns counts such windows).
  * Domains with sectors of more than 8192 samples (workgroup-wide groups, teams), and classes of more than 128 samples per
  * sector that have a starved pyramid level (config 5's geometry: their one-pair launch chain is the faster form), have
  * no pipelined instance: their windows run the frames one after the other on the device - same interface, same records. */

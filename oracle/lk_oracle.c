@@ -994,11 +994,20 @@ int lko_correlate_sectors(lko_engine *e, int S, const int64_t *off, const int *c
     for (int s = 0; s < S; ++s) {
       float p[6];
       memcpy(p, guesses + 6 * (size_t)s, sizeof(p));
-      local.reached_iterations = 0;
+      local.reached_iterations = -1; /* (no LM trip ran: resolved below) */
       lko_newton_raphson(&local, p, cnt[s], xy + 2 * off[s], use_center,
                          use_center ? centers[2 * s] : 0.f, use_center ? centers[2 * s + 1] : 0.f,
                          &results[s], NULL, 0, NULL);
     }
+  }
+  /* a sector whose first evaluation failed ran no LM trip and reports reached_iterations as the sector solved before it
+     left it (correlation_class.cpp:413-419, :870): in the sequential order, as the one-thread path above does - across
+     calls too */
+  for (int s = 0; s < S; ++s) {
+    if (results[s].iterations < 0)
+      results[s].iterations = e->reached_iterations;
+    else
+      e->reached_iterations = results[s].iterations;
   }
   return 0;
 #else

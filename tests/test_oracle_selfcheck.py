@@ -187,3 +187,33 @@ def test_initial_guess_policy(oracle):
     assert np.allclose(prev2[:2], [2, 3])
     g3, _ = oracle.adjust_initial_guess(3, 1, 0, [0] * 6, 0, 0, 0, 0, [2, 3, 0, 0, 0, 0], prev)
     assert np.allclose(g3[:2], [2, 3])
+
+
+def test_host_threads_keep_the_sequential_stale_iteration_count(oracle):
+    """A sector whose first evaluation fails runs no LM trip and reports reached_iterations as the sector solved before it
+    left it (correlation_class.cpp:413-419, :870) - a sequential quantity, carried across calls.  The host-parallel path
+    (nthreads > 1) must give the one-thread path's records byte for byte, those counts included: 7 x 7-sample sectors with
+    two starved levels over three pairs of a moving sequence, where several sectors fail at their first evaluation."""
+    from correlation_amd import speckle
+    frames = speckle.speckle_sequence(448, 448, 4, velocity=(0.8, -0.4), dilation=2e-4, seed=5)
+    n = int((423.0 - 24.0) // 8.95)
+    xd, yd, cen = oracle.rect_sector_geometry(24.0, 24.0, 423.0, 423.0, n, n)
+    lists = [oracle.rect_points(cx - xd, cy - yd, cx + xd, cy + yd) for cx, cy in cen]
+    out = []
+    for nthreads in (1, 4):
+        o = oracle.Oracle()
+        o.set_image(0, frames[0])
+        recs, g = [], np.zeros((len(lists), 6), np.float32)
+        for k in range(3):
+            o.set_image(1, frames[k + 1])
+            r = o.correlate_sectors(lists, centers=cen.astype(np.float32), guesses=g, nthreads=nthreads)
+            g = np.nan_to_num(r["p"], nan=0.0)
+            recs.append(r)
+        o.close()
+        out.append(np.stack(recs))
+    first_failed = (out[0]["error_code"] != 0) & (out[0]["chi"] == np.finfo(np.float32).max)
+    assert first_failed.sum() >= 3 and (out[0]["iterations"][first_failed] > 0).any()
+    a, b = out[0].copy(), out[1].copy()
+    for r in (a, b):
+        r["p"][np.isnan(r["p"])] = 0.0
+    assert a.tobytes() == b.tobytes()

@@ -92,10 +92,12 @@ def test_window_records_are_the_one_pair_loops_bytes(frames448, mode, kind):
 
 
 @pytest.mark.parametrize("pyramid", [(1, 1, 2), (0, 2, 2), (0, 1, 0), (0, 1, 3)], ids=lambda t: "levels_%d_%d_%d" % t)
-@pytest.mark.parametrize("interpolation", [ca.IM_BICUBIC, ca.IM_BILINEAR, ca.IM_NEAREST], ids=["bicubic", "bilinear", "nearest"])
+@pytest.mark.parametrize("interpolation", [ca.IM_BICUBIC, ca.IM_BILINEAR, ca.IM_NEAREST, ca.IM_BICUBIC_SEPARABLE],
+                         ids=["bicubic", "bilinear", "nearest", "bicubic_separable"])
 def test_window_bytes_on_other_pyramids_and_interpolators(frames448, pyramid, interpolation):
-    """levels that stop above the image, skip a level, are the image alone, or go one level deeper; the two cheaper samplers:
-    the window's frames still are the loop's bytes (batch-invariant mode; the mixed domain: every group width at once)"""
+    """levels that stop above the image, skip a level, are the image alone, or go one level deeper; the two cheaper samplers
+    and the separable bicubic extension: the window's frames still are the loop's bytes (batch-invariant mode; the mixed
+    domain: every group width at once)"""
     if interpolation != ca.IM_BICUBIC and pyramid != (0, 1, 2) and pyramid != (1, 1, 2):
         pytest.skip("the samplers are crossed with one other pyramid only")
     frames, n, c = frames448, 5, (223.5, 223.5)
@@ -184,6 +186,7 @@ def test_default_mode_window_stays_with_the_loop(frames448):
     b.sequence_reserve(n)
     _, r_win = window(b, frames, 0, n, center=c)
     assert b.sequence_is_pipelined
+    assert b.stats()["window_safe_reruns"] == 0      # (no bad pivot on speckle: the fast flavour's window stands)
     assert np.array_equal(r_win["error_code"], r_loop["error_code"])
     ok = r_loop["error_code"] == 0
     assert np.abs(r_win["p"] - r_loop["p"])[ok][:, :2].max() < 2e-3
