@@ -39,6 +39,29 @@ class LkStats(C.Structure):
                 ("pyramid_ms", C.c_float), ("window_safe_reruns", C.c_uint64)]
 
 
+# automatic initial guess (include/lk_engine.h: lk_search_guesses)
+GS_OK, GS_TEXTURELESS, GS_NO_CANDIDATE, GS_TOO_FEW, GS_TOO_LARGE, GS_WEAK = range(6)
+GS_MAX_RADIUS = 32
+GS_MAX_SAMPLES = 1 << 22
+
+
+class LkGuessSearch(C.Structure):
+    _fields_ = [("level", C.c_int), ("radius", C.c_int), ("min_samples", C.c_int), ("min_score", C.c_float),
+                ("def_slot", C.c_int)]
+
+
+class LkGuessMatch(C.Structure):
+    _fields_ = [("center_x", C.c_int), ("center_y", C.c_int), ("shift_x", C.c_int), ("shift_y", C.c_int),
+                ("n_samples", C.c_int), ("n_valid", C.c_int), ("status", C.c_int),
+                ("score", C.c_double), ("runner_up", C.c_double)]
+
+
+# lk_guess_match as a numpy record (same layout as LkGuessMatch)
+GUESS_MATCH_DTYPE = np.dtype({"names": [f for f, _ in LkGuessMatch._fields_],
+                              "formats": [np.int32] * 7 + [np.float64] * 2,
+                              "offsets": [getattr(LkGuessMatch, f).offset for f, _ in LkGuessMatch._fields_],
+                              "itemsize": C.sizeof(LkGuessMatch)})
+
 # layout of lk_result == CorrelationResult (domains.hpp:110-118), 48 bytes
 RESULT_DTYPE = np.dtype([("p", np.float32, (6,)), ("chi", np.float32),
                          ("n_points", np.int32), ("iterations", np.int32),
@@ -109,6 +132,8 @@ SYMBOLS = {
     "lk_get_sequence_guesses": (C.c_int, [_P, _F]),
     "lk_adjust_initial_guess": (C.c_int, [_P, C.c_int, C.c_int, _F, C.c_float, C.c_float]),
     "lk_get_guesses": (C.c_int, [_P, _F]),
+    "lk_search_guesses": (C.c_int, [_P, C.POINTER(LkGuessSearch), _F]),
+    "lk_get_guess_search_info": (C.c_int, [_P, _P]),
     "lk_evaluate": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_sample": (C.c_int, [_P, C.c_int, C.c_int, _F, C.c_int, _F]),
     "lk_damped_solve": (C.c_int, [_P, C.c_int, _F, _F, C.c_float, C.c_float, C.c_int, _F]),
@@ -128,6 +153,8 @@ SYMBOLS = {
     "lk_tracker_begin_frame": (C.c_int, [_P, C.c_int, _P, _F]),
     "lk_tracker_end_frame": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_char_p, _P, _I, _I]),
     "lk_tracker_get_results": (C.c_int, [_P, _P]),
+    "lk_tracker_set_guess_search": (C.c_int, [_P, C.POINTER(LkGuessSearch)]),
+    "lk_tracker_override_guesses": (C.c_int, [_P, _F]),
     "lk_tracker_report": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "lk_sequence_frame": (C.c_int, [_P, _P, C.c_int, C.c_char_p, C.c_char_p, _I]),
     "lk_sequence_run": (C.c_int, [_P, _P, C.c_int, _P, _P, _I]),

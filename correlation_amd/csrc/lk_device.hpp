@@ -184,3 +184,20 @@ struct LkEvalArgs { // stand-alone evaluation (known-answer tests)
   float *out; // [36 + 6 + 1 + 1]: A row-major 6x6 (upper), b, chi, error
   int ref_threads; // > 0: the reference's summation order for number_of_threads = ref_threads (evaluate_ordered)
 };
+
+// Automatic initial guess (lk_guess_search.hip): one workgroup per sector.
+struct LkGuessSearchArgs {
+  const uint8_t *und, *def; // level-L images, pitch == cols
+  int urows, ucols, drows, dcols;
+  const float2 *xy;         // level-L lists, [S+1] offsets, [S] implicit rectangles (LkLevelView)
+  const uint32_t *off;
+  const int4 *rect;
+  float *guess;             // [S][6] in: centres; out: the winners of OK sectors (g[0], g[1] only)
+  float *prev_p;            // [S][6] out: = guess (the frame-0 rule's previous_resulting_parameters)
+  lk_guess_match *match;    // [S]
+  int n_sectors, level, radius, has_v, min_samples;
+  float min_score;
+  int win_bytes;            // LDS bytes for the staged deformed window (a larger window is read from global memory)
+};
+constexpr int kLkGsThreads = 256;
+constexpr int kLkGsChunk = 1024; // template samples staged in LDS at a time (uint32 partial sums per chunk are exact)

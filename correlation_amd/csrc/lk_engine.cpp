@@ -279,6 +279,8 @@ struct lk_engine {
   DevBuf<uint32_t> d_team_arrivals;
   DevBuf<float> d_scratch; // 64 floats for the stand-alone entry points
   DevBuf<float2> d_warp;
+  DevBuf<lk_guess_match> d_gs_match; // lk_search_guesses: the matches of the last search
+  int gs_count = 0;                  //   for this many sectors (0: no search yet)
   // Frame-pipelined windows (lk_correlate_sequence_async): a ring of resident deformed-frame pyramids, filled on the
   // next-frame stream, and the buffers of one window - records and counters per frame, the per-sector granule chain that
   // hands a sector's parameters from frame to frame, the per-frame image table, two flag words.
@@ -388,6 +390,7 @@ void lk_destroy(lk_engine *e) {
     e->d_rect[l].release();
   }
   e->d_center.release();
+  e->d_gs_match.release();
   e->d_xy0_alt.release();
   e->d_xy_eval0_alt.release();
   e->d_off_eval.release();
@@ -2647,6 +2650,66 @@ int lk_internal_team_launches(const lk_engine *e) {
   return (n_team > 0 && e->team_w > 1) || (e->reference_order > 1 && n_big > 0) ? 1 : 0;
 }
 int lk_internal_sector_count(const lk_engine *e) { return e ? e->S : 0; }
+
+int lk_internal_fail(lk_engine *e, int code, const char *what) { return e->fail(code, what); }
+int lk_internal_hipfail(lk_engine *e, hipError_t err, const char *where) { return e->hipfail(err, where); }
+int *lk_internal_guess_search_count(lk_engine *e) { return &e->gs_count; }
+
+int lk_internal_guess_search_matches(lk_engine *e, lk_guess_match **d_match, hipStream_t *stream) {
+  if (!e->d_gs_match.p)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_get_guess_search_info: no search yet");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  *d_match = e->d_gs_match.p;
+  *stream = e->stream;
+  return LK_ERROR_NONE;
+}
+
+int lk_internal_guess_search_view(lk_engine *e, int level, int def_slot, LkGuessSearchView *v) {
+  if (level < 0)
+    level = e->cfg.py_stop;
+  if (!e->committed)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_search_guesses: sectors are not committed (call lk_commit_sectors)");
+  if (level < 0 || level > e->cfg.py_stop || level >= LK_MAX_LEVELS || e->h_off[level].size() != (size_t)e->S + 1 ||
+      e->h_rect[level].size() != (size_t)e->S)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_search_guesses: the engine builds no sample lists for that level");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  if (e->recommit_pending) { // lk_update_sector moved lists: rebuild them as the next solve would
+    e->recommit_pending = false;
+    if (int rc = commit_impl(e, true))
+      return rc;
+  }
+  const DevImage &u = e->img[LK_IMG_UND];
+  const DevImage *d = &e->img[LK_IMG_DEF];
+  if (def_slot >= 0) {
+    if (def_slot >= (int)e->ring.size())
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_search_guesses: unknown ring slot (lk_sequence_reserve)");
+    d = &e->ring[(size_t)def_slot];
+    if (d->valid)
+      HIPCHK(hipStreamWaitEvent(e->stream, e->ring_ready[(size_t)def_slot], 0));
+  }
+  if (!u.valid || !d->valid || !u.lvl[level] || !d->lvl[level])
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_search_guesses: the undeformed and the deformed image must be set");
+  HIPCHK(e->d_gs_match.ensure((size_t)std::max(e->S, 1)));
+  v->stream = e->stream;
+  v->S = e->S;
+  v->model = e->cfg.fitting_model;
+  v->level = level;
+  v->und = u.lvl[level];
+  v->def = d->lvl[level];
+  v->urows = u.rows >> level;
+  v->ucols = u.cols >> level;
+  v->drows = d->rows >> level;
+  v->dcols = d->cols >> level;
+  v->xy = e->d_xy[level].p;
+  v->off = e->d_off[level].p;
+  v->rect = e->d_rect[level].p;
+  v->h_rect = e->h_rect[level].data();
+  v->h_off = e->h_off[level].data();
+  v->d_guess = e->d_guess.p;
+  v->d_prev_p = e->d_prev_p.p;
+  v->d_match = e->d_gs_match.p;
+  return LK_ERROR_NONE;
+}
 
 extern "C" {
 

@@ -32,3 +32,26 @@ int lk_internal_sector_count(const lk_engine *e);
 // iteration counts resolved in the order the reference solves - frame by frame, sector by sector
 hipError_t lk_launch_stale_iterations_window(lk_result *all, int n_sectors, int n_ranks, int cap, int frames, const int *carry_in,
                                              int *carry_out, hipStream_t st);
+
+// Automatic initial guess (lk_guess_search.cpp): what the search needs of the engine.  The accessor finishes pending
+// rebuilds of the lists, makes the engine's stream wait for a ring slot's pyramid, and sizes the match buffer [S].
+struct LkGuessSearchView {
+  hipStream_t stream;
+  int S, model, level;
+  const uint8_t *und, *def; // level-L images (def: LK_IMG_DEF or the ring slot)
+  int urows, ucols, drows, dcols;
+  const float2 *xy;         // level-L lists in the reference's order, [S+1] offsets, [S] implicit rectangles (device)
+  const uint32_t *off;
+  const int4 *rect;
+  const int4 *h_rect;       // [S] the same rectangles on the host (width 0: explicit list)
+  const uint32_t *h_off;    // [S+1]
+  float *d_guess, *d_prev_p; // [S][6] engine-held guesses and previous_resulting_parameters
+  lk_guess_match *d_match;  // [S]
+};
+int lk_internal_guess_search_view(lk_engine *e, int level, int def_slot, LkGuessSearchView *v);
+// level -1: py_stop (v->level says which)
+int lk_internal_guess_search_matches(lk_engine *e, lk_guess_match **d_match, hipStream_t *stream);
+int lk_internal_fail(lk_engine *e, int code, const char *what);
+int lk_internal_hipfail(lk_engine *e, hipError_t err, const char *where);
+// the sector count the match buffer holds results for (set by lk_search_guesses; 0: none yet)
+int *lk_internal_guess_search_count(lk_engine *e);

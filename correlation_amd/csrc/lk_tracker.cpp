@@ -132,6 +132,11 @@ struct lk_tracker {
   bool report_enabled = true;
   std::string err;
   bool begun = false;
+  int begun_frame = -1; // the frame lk_tracker_begin_frame was called for
+  // automatic initial guess (lk_tracker_set_guess_search, lk_guess_search.cpp): frame 0's search, run through a pointer so
+  // that this file links without the engine (tests/host: the mock)
+  lk_guess_search search_cfg{};
+  int (*search)(lk_engine *, const lk_guess_search *, float *) = nullptr;
   Workers workers, report_workers;
   size_t min_block = 4096; // sectors per block of the threaded loops (LK_TRACKER_MIN_BLOCK: test hook)
   // scratch of lk_sequence_frame (kept: three multi-megabyte buffers per frame otherwise)
@@ -717,6 +722,20 @@ int lk_tracker_begin_frame(lk_tracker *t, int frame, lk_sector_command *commands
   }
   }
   t->begun = true;
+  t->begun_frame = frame;
+  return LK_ERROR_NONE;
+}
+
+int lk_tracker_override_guesses(lk_tracker *t, const float *guesses) {
+  if (!t)
+    return LK_ERROR_BAD_DOMAIN;
+  if (!guesses || !t->begun || t->begun_frame != 0)
+    return t->fail(LK_ERROR_BAD_DOMAIN, "lk_tracker_override_guesses: only between lk_tracker_begin_frame(0) and lk_tracker_end_frame(0)");
+  for (size_t k = 0; k < t->res.size(); ++k) // adjust_initial_guess's frame-0 rule with these guesses (:2602-2650)
+    for (int p = 0; p < t->P; ++p) {
+      t->res[k].initial_guess[p] = guesses[6 * k + (size_t)p];
+      t->res[k].previous_resulting_parameters[p] = guesses[6 * k + (size_t)p];
+    }
   return LK_ERROR_NONE;
 }
 
@@ -794,6 +813,26 @@ int lk_tracker_report(const lk_tracker *t, char *buf, size_t cap, size_t *needed
 // ------------------------------------------------------------------------------------
 // frame loop on an engine
 // ------------------------------------------------------------------------------------
+// the switch behind lk_tracker_set_guess_search (lk_guess_search.cpp)
+int lk_tracker_internal_set_search(lk_tracker *t, const lk_guess_search *cfg,
+                                   int (*search)(lk_engine *, const lk_guess_search *, float *)) {
+  if (!t)
+    return LK_ERROR_BAD_DOMAIN;
+  t->search = cfg ? search : nullptr;
+  if (cfg) {
+    t->search_cfg = *cfg;
+    t->search_cfg.def_slot = -1; // the pair's deformed image
+  }
+  return LK_ERROR_NONE;
+}
+
+// frame 0 with the automatic guess on: the rule guesses in `guesses` are the search's centres; the searched guesses come
+// back in `guesses`, in the engine-held guesses and sequence history, and in the tracker's frame 0 (sectors registered)
+static int search_frame0(lk_engine *e, lk_tracker *t, float *guesses) {
+  int rc = t->search(e, &t->search_cfg, guesses);
+  return rc ? rc : lk_tracker_override_guesses(t, guesses);
+}
+
 // frame 0: the tracker's commands become the engine's sectors
 static int register_sectors(lk_engine *e, lk_tracker *t, const std::vector<lk_sector_command> &cmds) {
   const int S = (int)cmds.size();
@@ -846,6 +885,8 @@ int lk_sequence_frame(lk_engine *e, lk_tracker *t, int frame, const char *und_na
   bool moved = false;
   if (frame == 0) {
     rc = register_sectors(e, t, cmds);
+    if (!rc && t->search)
+      rc = search_frame0(e, t, guesses.data());
   } else if (S > 0 && cmds[0].kind != LK_SECTOR_KEEP) {
     moved = true;
     std::vector<float> off(2 * (size_t)S), cen(2 * (size_t)S);
@@ -929,8 +970,9 @@ int lk_sequence_run(lk_engine *e, lk_tracker *t, int n_frames, lk_frame_provider
     guesses.resize(6 * (size_t)S);
     results.resize((size_t)S);
     std::vector<float> device_guesses(check ? 6 * (size_t)S : 0);
+    bool searched = false; // frame 0's guesses came from the search: the engine holds them already
     auto launch = [&](int k) {
-      int r = lk_adjust_initial_guess(e, k, velocity ? 1 : 0, gg, t->x_center, t->y_center);
+      int r = k == 0 && searched ? 0 : lk_adjust_initial_guess(e, k, velocity ? 1 : 0, gg, t->x_center, t->y_center);
       if (!r && check)
         r = lk_get_guesses(e, device_guesses.data());
       return r ? r : lk_correlate_all_async(e);
@@ -948,6 +990,10 @@ int lk_sequence_run(lk_engine *e, lk_tracker *t, int n_frames, lk_frame_provider
     rc = lk_tracker_begin_frame(t, 0, cmds.data(), guesses.data());
     if (!rc)
       rc = register_sectors(e, t, cmds);
+    if (!rc && t->search) {
+      rc = search_frame0(e, t, guesses.data());
+      searched = !rc;
+    }
     mark("sectors registered and committed");
     // Windows of K pairs (LK_SEQ_WINDOW, default 16; 1 = pair by pair, below): the K deformed frames of a window are
     // resident in the engine's ring and ONE launch per size class solves them all, every sector moving on to its next
@@ -1030,7 +1076,7 @@ int lk_sequence_run(lk_engine *e, lk_tracker *t, int n_frames, lk_frame_provider
           if (nrc) // error_multiThread in the reference (manager_class.cpp:1470-1475)
             rc = nrc;
         }
-        if (!rc)
+        if (!rc && !(first == 0 && searched))
           rc = lk_adjust_initial_guess(e, first, velocity ? 1 : 0, gg, t->x_center, t->y_center);
         if (!rc && check)
           rc = lk_get_guesses(e, win_first[buf].data());

@@ -319,6 +319,25 @@ class HipCorrelationEngine:
         self._chk(self.lib.lk_get_guesses(self._h, _ffi.fptr(g)))
         return g
 
+    # ---- automatic initial guess (the GUI's "Initial Guess: Automatic") -----------------------
+    def search_guesses(self, radius, level=-1, guesses=None, min_samples=0, min_score=0.0, def_slot=-1):
+        """Integer-pixel ZNCC search of every sector at pyramid `level` (-1: py_stop) within +-radius pixels of that level
+        about its guess (include/lk_engine.h: lk_search_guesses).  guesses None: about the engine-held guesses, on the
+        engine's stream, returns None; else [S][6] centres, returns the refined [S][6] (also engine-held)."""
+        cfg = _ffi.LkGuessSearch(int(level), int(radius), int(min_samples), float(min_score), int(def_slot))
+        if guesses is None:
+            self._chk(self.lib.lk_search_guesses(self._h, C.byref(cfg), None))
+            return None
+        g = np.array(guesses, np.float32).reshape(self.n_sectors, 6)
+        self._chk(self.lib.lk_search_guesses(self._h, C.byref(cfg), _ffi.fptr(g)))
+        return g
+
+    def guess_search_info(self):
+        """The matches of the last search_guesses: a GUESS_MATCH_DTYPE array [S]."""
+        out = np.zeros(self.n_sectors, _ffi.GUESS_MATCH_DTYPE)
+        self._chk(self.lib.lk_get_guess_search_info(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     # ---- stand-alone pieces -------------------------------------------------------------
     def evaluate(self, sector, level, p):
         pp = np.zeros(6, np.float32)

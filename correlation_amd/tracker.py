@@ -111,6 +111,16 @@ class SequenceTracker:
                                                 r.ctypes.data_as(C.c_void_p), C.byref(first), C.byref(stop)))
         return first.value, bool(stop.value)
 
+    def set_guess_search(self, radius, level=-1, min_samples=0, min_score=0.0):
+        """Automatic initial guess on frame 0 of lk_sequence_frame / lk_sequence_run (radius 0: off)."""
+        cfg = _ffi.LkGuessSearch(int(level), int(radius), int(min_samples), float(min_score), -1)
+        self._chk(self.lib.lk_tracker_set_guess_search(self._h, C.byref(cfg)))
+
+    def override_guesses(self, guesses):
+        """Frame 0's guesses [S][6], between begin_frame(0) and end_frame(0)."""
+        g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
+        self._chk(self.lib.lk_tracker_override_guesses(self._h, _ffi.fptr(g)))
+
     def results(self):
         out = np.zeros(self.n_sectors, FRAME_RESULT_DTYPE)
         self._chk(self.lib.lk_tracker_get_results(self._h, out.ctypes.data_as(C.c_void_p)))

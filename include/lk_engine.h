@@ -352,6 +352,48 @@ int lk_adjust_initial_guess(lk_engine *e, int frame, int constant_velocity,
 /* copy the engine-held guesses ([S][6]) to the host */
 int lk_get_guesses(lk_engine *e, float *guesses);
 
+/* ---- automatic initial guess: integer-pixel ZNCC search ------------------------------ */
+/* The reference GUI's "Initial Guess: Automatic" (initialGuessEnum ic_Auto, enums.hpp:41; never implemented there).
+ * Per sector, at pyramid level L: template = the sector's level-L samples, positions rounded (int)(v + 0.5f) and clamped
+ * to the undeformed image like the solve's reads, values of the u8 level-L undeformed image; centre c = floor(g / 2^L + 0.5)
+ * of the sector's guess g[0], g[1]; candidates c + (i, j), |i|, |j| <= radius (j = 0 for LK_FM_U) whose every shifted
+ * sample lies inside the level-L deformed image.  Exact int64 sums St, Stt, Sd, Sdd, Std give
+ * score = (n Std - St Sd) / sqrt((n Stt - St^2)(n Sdd - Sd^2)) (a candidate with n Sdd == Sd^2 is not valid).  Winner: the
+ * highest score; ties go to the smaller i^2 + j^2, then the smaller j, then the smaller i.  Runner-up: the best score at
+ * Chebyshev distance >= 2 from the winner (-2: none).  An OK sector gets g[0] = (c_x + i) 2^L and, for models with v,
+ * g[1] = (c_y + j) 2^L; g[2..5] and the guesses of the other sectors stay as they were, bit for bit.  The results go to the
+ * engine-held guesses and to the sequence history frame 0 leaves (previous_resulting_parameters = initial guess), so a
+ * window or pair loop started afterwards continues as if they had been frame 0's guesses.  Integer sums: a sector gets
+ * the same bits in any batch, shard or mode. */
+enum {
+  LK_GS_OK = 0,
+  LK_GS_TEXTURELESS = 1,  /* n Stt == St^2 */
+  LK_GS_NO_CANDIDATE = 2, /* no valid candidate */
+  LK_GS_TOO_FEW = 3,      /* n < min_samples */
+  LK_GS_TOO_LARGE = 4,    /* n > 2^22 */
+  LK_GS_WEAK = 5          /* best score <= min_score */
+};
+#define LK_GS_MAX_RADIUS 32
+#define LK_GS_MAX_SAMPLES (1 << 22)
+typedef struct {
+  int level;       /* -1 = py_stop; must be a level the engine builds */
+  int radius;      /* R, pixels of that level, 0 .. LK_GS_MAX_RADIUS */
+  int min_samples; /* <= 0: 9 */
+  float min_score;
+  int def_slot;    /* -1: LK_IMG_DEF; k >= 0: ring slot k (lk_sequence_set_frame) */
+} lk_guess_search;
+typedef struct {
+  int center_x, center_y, shift_x, shift_y; /* level-L pixels; the winner is centre + shift */
+  int n_samples, n_valid, status;           /* n_valid: candidates with a score; status: LK_GS_* (checked in the
+                                             * order TOO_LARGE, TOO_FEW, TEXTURELESS, NO_CANDIDATE, WEAK) */
+  double score, runner_up;                  /* -2 where there is none */
+} lk_guess_match;
+/* guesses_inout NULL: search about the engine-held guesses (asynchronous, engine stream);
+ * else host [S][6]: centres in, refined guesses out (synchronous) - and engine-held either way */
+int lk_search_guesses(lk_engine *e, const lk_guess_search *cfg, float *guesses_inout);
+/* the matches of the last lk_search_guesses, [S] (waits for it) */
+int lk_get_guess_search_info(lk_engine *e, lk_guess_match *out);
+
 /* ---- stand-alone pieces (known-answer tests, same kernels as the batch path) ------- */
 /* one evaluation of one sector at one level: raw sums A (6x6 row-major, upper valid),
  * b, chi (unscaled), error flag (apply_model_and_interpolate, correlation_class.cpp:131) */

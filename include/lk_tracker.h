@@ -109,6 +109,14 @@ int lk_tracker_begin_frame(lk_tracker *t, int frame, lk_sector_command *commands
 int lk_tracker_end_frame(lk_tracker *t, int frame, const char *und_name, const char *def_name,
                          const lk_result *results, int *first_unsolved, int *stop_sequence);
 int lk_tracker_get_results(const lk_tracker *t, lk_frame_result *out /* [S] */);
+/* Automatic initial guess (lk_search_guesses).  cfg NULL or radius 0: off (the default).  On: lk_sequence_frame and
+ * lk_sequence_run search about frame 0's rule guesses (lk_tracker_begin_frame) in the pair's deformed image (LK_IMG_DEF;
+ * cfg->def_slot is ignored); the searched guesses become frame 0's initial_guess / previous_resulting_parameters and the
+ * solve's starting point. */
+int lk_tracker_set_guess_search(lk_tracker *t, const lk_guess_search *cfg);
+/* host only, between lk_tracker_begin_frame(t, 0) and lk_tracker_end_frame(t, 0): frame 0's guesses [S][6] are replaced -
+ * initial_guess and previous_resulting_parameters of every sector (for callers that run lk_search_guesses themselves) */
+int lk_tracker_override_guesses(lk_tracker *t, const float *guesses);
 /* the report so far (initializeReport + addFrameToReport text); *needed = bytes incl. NUL */
 int lk_tracker_report(const lk_tracker *t, char *buf, size_t cap, size_t *needed);
 
