@@ -8,7 +8,8 @@ and fails loudly if the library is missing.
 from ._ffi import (ERROR_BAD_DOMAIN, ERROR_CORRELATION_MAX_ITERS_REACHED, ERROR_DEVICE,  # noqa: F401
                    ERROR_INTERPOLATION_OUT_OF_IMAGE, ERROR_NONE, FM_U, FM_UV, FM_UVQ,
                    FM_UVUXUYVXVY, IM_BICUBIC, IM_BICUBIC_SEPARABLE, IM_BILINEAR, IM_NEAREST, IMG_DEF, IMG_NXT, IMG_UND,
-                   LIB_PATH, N_PARAMS, RESULT_DTYPE, SYMBOLS, load_library)
+                   LIB_PATH, N_PARAMS, RESULT_DTYPE, SYMBOLS, UPDATE_BACKWARD, UPDATE_FORWARD, compose_inverse,
+                   load_library)
 from ._ffi import (GS_NO_CANDIDATE, GS_OK, GS_TEXTURELESS, GS_TOO_FEW, GS_TOO_LARGE, GS_WEAK,  # noqa: F401
                    GUESS_MATCH_DTYPE)
 from .engine import HipCorrelationEngine, LkError  # noqa: F401

@@ -23,6 +23,7 @@ IMG_UND, IMG_DEF, IMG_NXT = 0, 1, 2
  ERROR_MULTITHREAD) = range(8)
 
 N_PARAMS = {FM_U: 1, FM_UV: 2, FM_UVQ: 3, FM_UVUXUYVXVY: 6}
+UPDATE_FORWARD, UPDATE_BACKWARD = 0, 1   # lk_set_update (updateEnum, enums.hpp:39)
 
 
 class LkConfig(C.Structure):
@@ -82,6 +83,7 @@ SYMBOLS = {
     "lk_set_timing": (C.c_int, [_P, C.c_int]),
     "lk_set_batch_invariant": (C.c_int, [_P, C.c_int]),
     "lk_set_reference_order": (C.c_int, [_P, C.c_int]),
+    "lk_set_update": (C.c_int, [_P, C.c_int]),
     "lk_set_pairs_in_flight": (C.c_int, [_P, C.c_int]),
     "lk_synchronize": (C.c_int, [_P]),
     "lk_set_image": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
@@ -135,6 +137,8 @@ SYMBOLS = {
     "lk_search_guesses": (C.c_int, [_P, C.POINTER(LkGuessSearch), _F]),
     "lk_get_guess_search_info": (C.c_int, [_P, _P]),
     "lk_evaluate": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
+    "lk_evaluate_backward": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
+    "lk_compose_inverse": (C.c_int, [C.c_int, _F, _F, _F]),
     "lk_sample": (C.c_int, [_P, C.c_int, C.c_int, _F, C.c_int, _F]),
     "lk_damped_solve": (C.c_int, [_P, C.c_int, _F, _F, C.c_float, C.c_float, C.c_int, _F]),
     "lk_get_stats": (C.c_int, [_P, C.POINTER(LkStats)]),
@@ -235,3 +239,25 @@ def load_library(path=LIB_PATH):
 
 def fptr(a):
     return a.ctypes.data_as(_F)
+
+
+_compose_lib = None
+
+
+def compose_inverse(model, p, delta):
+    """The backward update's W(p) o W(delta)^-1 (lk_compose_inverse, host, the kernel's function): the new parameter set
+    [6] as float32, or None for a singular delta."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    pp = np.zeros(6, np.float32)
+    dd = np.zeros(6, np.float32)
+    pp[:len(p)] = np.asarray(p, np.float32)[:6]
+    dd[:len(delta)] = np.asarray(delta, np.float32)[:6]
+    out = np.zeros(6, np.float32)
+    rc = _compose_lib.lk_compose_inverse(int(model), fptr(pp), fptr(dd), fptr(out))
+    if rc == 1:
+        return None
+    if rc != 0:
+        raise ValueError(f"lk_compose_inverse: bad model {model}")
+    return out

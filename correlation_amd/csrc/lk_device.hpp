@@ -201,3 +201,35 @@ struct LkGuessSearchArgs {
 };
 constexpr int kLkGsThreads = 256;
 constexpr int kLkGsChunk = 1024; // template samples staged in LDS at a time (uint32 partial sums per chunk are exact)
+
+// Backward (inverse-compositional) update (lk_backward.hip, lk_set_update): one lane group per sector for its whole
+// coarse-to-fine solve.  The group is chosen from the sector's level-0 sample count alone (kLkBwGroup*), so that a
+// sector's record does not depend on what else is solved with it.
+struct LkBackwardArgs {
+  const LkLevelView *lv;  // [LK_MAX_LEVELS] in device memory
+  const float2 *center;   // [S] level-0 centre of each sector
+  const float *guess;     // [S][6]
+  lk_result *result;      // [S]
+  float *last_p;          // [S][6] or null
+  float *last_eval_p;     // [S][6] or null
+  uint32_t *stats;        // [S][4] or null
+  const uint32_t *order;  // [n_sectors] the sectors of this launch
+  float4 *tpl;            // template slots {T, dT/dx, dT/dy, 0}: a sector's level-L samples at tpl[tpl_base[s] + k]
+  const uint32_t *tpl_base; // [S] prefix of the level-0 counts
+  int n_sectors;
+  int py_start, py_step, py_stop;
+  float precision;
+  int max_iters;
+  int starved_max;
+};
+struct LkBackwardEvalArgs { // lk_evaluate_backward: template pass + one evaluation of one sector
+  const LkLevelView *lv;
+  const float2 *center;
+  float4 *tpl;
+  int sector, level;
+  float p[6];
+  float *out; // [36 + 6 + 1 + 1]: H row-major 6x6 (full), b, chi, error
+};
+constexpr int kLkBwSmall = 512;   // level-0 samples up to which a 16-lane row owns a sector
+constexpr int kLkBwMedium = 8192; // ... a wavefront; above: a 512-thread workgroup
+__host__ __device__ inline int lk_bw_group(int n0) { return n0 <= kLkBwSmall ? 16 : n0 <= kLkBwMedium ? 64 : 512; }

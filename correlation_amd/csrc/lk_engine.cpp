@@ -14,6 +14,7 @@
 // Everything for an image pair is resident; lk_correlate_all* is one launch per size class
 // (16 / 32 / 64 lanes, 4 / 8 wavefronts, teams) on one stream, preceded by the one-lane kernel
 // and its finisher when the class has a starved pyramid level.
+#include "lk_compose.hpp"
 #include "lk_device.hpp"
 #include "lk_internal.hpp"
 #include "lk_roi.hpp"
@@ -36,6 +37,8 @@ hipError_t lk_launch_solve(const LkSolveArgs &a, int model, int interp, int grou
 hipError_t lk_launch_solve_seq(const LkSolveArgs &a, int model, int interp, int group, int flavour, hipStream_t st);
 hipError_t lk_launch_eval(const LkEvalArgs &a, int model, int interp, int group, hipStream_t st);
 hipError_t lk_launch_solve_only(int n, const float *d_in, float *d_out, hipStream_t st);
+hipError_t lk_launch_backward(const LkBackwardArgs &a, int model, int interp, int group, hipStream_t st);
+hipError_t lk_launch_backward_eval(const LkBackwardEvalArgs &a, int model, int interp, int group, hipStream_t st);
 hipError_t lk_launch_sample(int interp, const uint8_t *def, int rows, int cols, const float2 *pts, int n,
                             float4 *out, hipStream_t st);
 hipError_t lk_launch_pyramid(const uint8_t *src, int srows, int scols, uint8_t *dst, hipStream_t st);
@@ -212,6 +215,15 @@ struct lk_engine {
   int stale_par = 0;
   bool defer_stale = false;     // lk_group member: the markers are resolved over the gathered records, in global sector order
   int reference_order = 0;      // lk_set_reference_order: 0 = off, T = the reference's number_of_threads to reproduce
+  int update = LK_UPDATE_FORWARD; // lk_set_update
+  // backward mode (lk_backward.hip): the sectors by lane group (16 / 64 / 512 lanes, from the level-0 count alone), each
+  // sector's first template slot (prefix of the level-0 counts) and the slots; rebuilt after every classify_sectors
+  bool bw_dirty = true;
+  std::vector<uint32_t> h_bw_order, h_bw_base;
+  int bw_begin[4] = {0, 0, 0, 0};
+  DevBuf<uint32_t> d_bw_order, d_bw_base;
+  DevBuf<float4> d_bw_tpl;
+  int stats_update = LK_UPDATE_FORWARD; // the mode of the solve the counters describe
   int pairs_in_flight = 1;      // lk_set_pairs_in_flight: launches that share the GPU
   bool timing = true; // HIP events around pyramid builds and solves (lk_stats.solve_ms / pyramid_ms)
   std::mutex nxt_mu;
@@ -501,10 +513,29 @@ int lk_set_reference_order(lk_engine *e, int threads) {
     return LK_ERROR_BAD_DOMAIN;
   if (threads < 0 || threads > 4096)
     return e->fail(LK_ERROR_BAD_DOMAIN, "lk_set_reference_order: threads must be in 0..4096");
+  if (threads > 0 && e->update == LK_UPDATE_BACKWARD)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_set_reference_order: the backward update has no reference arithmetic to follow");
   if ((threads > 0) != (e->reference_order > 0) && e->committed)
     e->recommit_pending = true; // the lane groups depend on the mode (commit_impl)
   e->reference_order = threads;
   return LK_ERROR_NONE;
+}
+
+int lk_set_update(lk_engine *e, int mode) {
+  if (!e)
+    return LK_ERROR_BAD_DOMAIN;
+  if (mode != LK_UPDATE_FORWARD && mode != LK_UPDATE_BACKWARD)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_set_update: mode must be LK_UPDATE_FORWARD or LK_UPDATE_BACKWARD");
+  if (mode == LK_UPDATE_BACKWARD && e->reference_order > 0)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_set_update: the backward update has no reference arithmetic (reference-order mode is on)");
+  e->update = mode;
+  return LK_ERROR_NONE;
+}
+
+int lk_compose_inverse(int model, const float *p, const float *delta, float *p_out) {
+  if (model < LK_FM_U || model > LK_FM_UVUXUYVXVY || !p || !delta || !p_out)
+    return LK_ERROR_BAD_DOMAIN;
+  return lk_compose_inverse_impl(model, p, delta, p_out);
 }
 
 int lk_set_pairs_in_flight(lk_engine *e, int n) {
@@ -1310,6 +1341,7 @@ static int classify_sectors(lk_engine *e) {
   HIPCHK(e->d_order.ensure((size_t)S));
   HIPCHK(hipMemcpy(e->d_order.p, e->h_order.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice));
   e->classes_dirty = false;
+  e->bw_dirty = true;
   return LK_ERROR_NONE;
 }
 
@@ -2401,6 +2433,82 @@ static int stale_iterations(lk_engine *e, lk_result *d_result, int n) {
   return LK_ERROR_NONE;
 }
 
+// Backward mode: the sectors by lane group (from each sector's level-0 count alone) and the template slots.
+static const int kBwGroups[3] = {16, 64, 512};
+static int bw_tables(lk_engine *e) {
+  if (!e->bw_dirty && e->h_bw_base.size() == (size_t)e->S)
+    return LK_ERROR_NONE;
+  const int S = e->S;
+  e->h_bw_order.clear();
+  e->h_bw_base.assign((size_t)S, 0u);
+  size_t total = 0;
+  for (int s = 0; s < S; ++s) {
+    e->h_bw_base[(size_t)s] = (uint32_t)total;
+    total += (size_t)level0_count(e, s);
+  }
+  if (total > 0xffffffffull)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "backward update: more than 2^32 level-0 samples");
+  for (int g = 0; g < 3; ++g) {
+    e->bw_begin[g] = (int)e->h_bw_order.size();
+    for (int s = 0; s < S; ++s)
+      if (lk_bw_group(level0_count(e, s)) == kBwGroups[g])
+        e->h_bw_order.push_back((uint32_t)s);
+  }
+  e->bw_begin[3] = (int)e->h_bw_order.size();
+  HIPCHK(hipStreamSynchronize(e->stream)); // (earlier launches may still read the tables)
+  HIPCHK(e->d_bw_order.ensure((size_t)S));
+  HIPCHK(e->d_bw_base.ensure((size_t)S));
+  HIPCHK(e->d_bw_tpl.ensure(total));
+  HIPCHK(hipMemcpy(e->d_bw_order.p, e->h_bw_order.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->d_bw_base.p, e->h_bw_base.data(), (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice));
+  e->bw_dirty = false;
+  return LK_ERROR_NONE;
+}
+
+static LkBackwardArgs bw_args(lk_engine *e, const float *d_guess, lk_result *d_result) {
+  LkBackwardArgs b{};
+  b.lv = e->d_lv.p;
+  b.center = e->d_center.p;
+  b.guess = d_guess;
+  b.result = d_result;
+  b.last_p = e->d_last_p.p;
+  b.last_eval_p = e->d_last_eval_p.p;
+  b.stats = e->d_stats.p;
+  b.tpl = e->d_bw_tpl.p;
+  b.tpl_base = e->d_bw_base.p;
+  b.py_start = e->cfg.py_start;
+  b.py_step = e->cfg.py_step;
+  b.py_stop = e->cfg.py_stop;
+  b.precision = e->cfg.precision;
+  b.max_iters = e->cfg.max_iters;
+  b.starved_max = starved_max(e);
+  return b;
+}
+
+// every sector of the domain with the backward update: one launch per lane group, on the engine's stream
+static int launch_all_backward(lk_engine *e, const float *d_guess, lk_result *d_result) {
+  if (int rc = bw_tables(e))
+    return rc;
+  Range range_("lk:solve backward");
+  if (e->timing)
+    HIPCHK(hipEventRecord(e->ev_s0, e->stream));
+  LkBackwardArgs b = bw_args(e, d_guess, d_result);
+  for (int g = 0; g < 3; ++g) {
+    b.order = e->d_bw_order.p + e->bw_begin[g];
+    b.n_sectors = e->bw_begin[g + 1] - e->bw_begin[g];
+    if (b.n_sectors > 0)
+      HIPCHK(lk_launch_backward(b, e->cfg.fitting_model, e->cfg.interpolation, kBwGroups[g], e->stream));
+  }
+  if (e->timing) {
+    HIPCHK(hipEventRecord(e->ev_s1, e->stream));
+    e->solve_timed = true;
+  }
+  e->stats_valid = false;
+  e->stats_frames = 1;
+  e->stats_update = LK_UPDATE_BACKWARD;
+  return LK_ERROR_NONE;
+}
+
 static int launch_all(lk_engine *e, const float *d_guess, lk_result *d_result) {
   if (e->classes_dirty) { // sectors were appended since the last analysis of the whole domain
     HIPCHK(hipStreamSynchronize(e->stream)); // (earlier launches may still read the order table)
@@ -2408,6 +2516,9 @@ static int launch_all(lk_engine *e, const float *d_guess, lk_result *d_result) {
     if (rc)
       return rc;
   }
+  if (e->update == LK_UPDATE_BACKWARD)
+    return launch_all_backward(e, d_guess, d_result);
+  e->stats_update = LK_UPDATE_FORWARD;
   Range range_("lk:solve");
   if (e->timing)
     HIPCHK(hipEventRecord(e->ev_s0, e->stream));
@@ -2763,6 +2874,29 @@ int lk_correlate(lk_engine *e, int sector, float *guess_inout, lk_result *out) {
   HIPCHK(hipMemcpyAsync(e->d_guess.p + 6 * (size_t)sector, g, sizeof(g), hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipMemcpyAsync(e->d_single.p, &sidx, sizeof(sidx), hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
+  if (e->update == LK_UPDATE_BACKWARD) { // the sector's own lane group: the bits of the batch solve
+    if (int rc2 = bw_tables(e))
+      return rc2;
+    LkBackwardArgs b = bw_args(e, e->d_guess.p, e->d_result.p);
+    b.order = e->d_single.p;
+    b.n_sectors = 1;
+    if (e->timing)
+      HIPCHK(hipEventRecord(e->ev_s0, e->stream));
+    HIPCHK(lk_launch_backward(b, e->cfg.fitting_model, e->cfg.interpolation, lk_bw_group(level0_count(e, sector)), e->stream));
+    if (e->timing) {
+      HIPCHK(hipEventRecord(e->ev_s1, e->stream));
+      e->solve_timed = true;
+    }
+    e->stats_valid = false;
+    e->stats_frames = 1;
+    e->stats_update = LK_UPDATE_BACKWARD;
+    HIPCHK(hipMemcpyAsync(out, e->d_result.p + sector, sizeof(lk_result), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < e->P; ++i)
+      guess_inout[i] = out->resultingParameters[i];
+    return LK_ERROR_NONE;
+  }
+  e->stats_update = LK_UPDATE_FORWARD;
   LkSolveArgs a = base_args(e, e->d_guess.p, e->d_result.p);
   a.order = e->d_single.p;
   const int group = kGroupOfClass[e->h_class[(size_t)sector]];
@@ -2974,7 +3108,7 @@ static int seq_group_of_class(const lk_engine *e, int c, int n) {
 
 static bool seq_pipelinable(const lk_engine *e) {
   static const bool off = [] { const char *f = std::getenv("LK_SEQ_PIPELINE"); return f && std::atoi(f) == 0; }(); // comparison hook
-  if (off)
+  if (off || e->update == LK_UPDATE_BACKWARD) // (the backward update has no frame-pipelined instances)
     return false;
   for (int c = 0; c < kNumClasses; ++c) {
     const int n = e->class_begin[c + 1] - e->class_begin[c];
@@ -3408,6 +3542,49 @@ int lk_evaluate(lk_engine *e, int sector, int level, const float *p, float *A36,
   return LK_ERROR_NONE;
 }
 
+int lk_evaluate_backward(lk_engine *e, int sector, int level, const float *p, float *H36, float *b6, float *chi,
+                         int *error) {
+  if (!e)
+    return LK_ERROR_BAD_DOMAIN;
+  HIPCHK(hipSetDevice(e->cfg.device));
+  int rc = refresh_level_views(e);
+  if (rc)
+    return rc;
+  if (sector < 0 || sector >= e->S || level < 0 || level > e->cfg.py_stop || !p ||
+      e->h_off[level].size() != (size_t)e->S + 1)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_evaluate_backward: unknown sector/level");
+  if (e->classes_dirty) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (int rc2 = classify_sectors(e))
+      return rc2;
+  }
+  if (int rc2 = bw_tables(e))
+    return rc2;
+  HIPCHK(e->d_scratch.ensure(64));
+  LkBackwardEvalArgs a{};
+  a.lv = e->d_lv.p;
+  a.center = e->d_center.p;
+  a.tpl = e->d_bw_tpl.p + e->h_bw_base[(size_t)sector];
+  a.sector = sector;
+  a.level = level;
+  for (int i = 0; i < 6; ++i)
+    a.p[i] = i < e->P ? p[i] : 0.f;
+  a.out = e->d_scratch.p;
+  HIPCHK(lk_launch_backward_eval(a, e->cfg.fitting_model, e->cfg.interpolation, lk_bw_group(level0_count(e, sector)), e->stream));
+  float h[44];
+  HIPCHK(hipMemcpyAsync(h, e->d_scratch.p, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (H36)
+    std::memcpy(H36, h, 36 * sizeof(float));
+  if (b6)
+    std::memcpy(b6, h + 36, 6 * sizeof(float));
+  if (chi)
+    *chi = h[42];
+  if (error)
+    *error = h[43] != 0.f ? LK_ERROR_INTERPOLATION_OUT_OF_IMAGE : LK_ERROR_NONE;
+  return LK_ERROR_NONE;
+}
+
 int lk_sample(lk_engine *e, int slot, int level, const float *xy, int n, float *out4) {
   if (!e)
     return LK_ERROR_BAD_DOMAIN;
@@ -3482,8 +3659,9 @@ int lk_get_stats(lk_engine *e, lk_stats *out) {
       s.point_iterations += h[4 * i + 2];
       s.ill_conditioned_solves += h[4 * i + 3];
     }
-    // 25 B per sample-evaluation + 196 B per evaluation
-    s.algorithmic_bytes = 25ull * s.sample_evaluations + 196ull * s.evaluations;
+    // 25 B per sample-evaluation + 196 B per evaluation; the backward update reads a 16-byte
+    // template slot instead of the undeformed pixel: 40 B per sample-evaluation (include/lk_engine.h, lk_set_update)
+    s.algorithmic_bytes = (e->stats_update == LK_UPDATE_BACKWARD ? 40ull : 25ull) * s.sample_evaluations + 196ull * s.evaluations;
     s.solve_ms = e->stats.solve_ms;
     s.pyramid_ms = e->stats.pyramid_ms;
     e->stats = s;

@@ -80,6 +80,10 @@ class HipCorrelationEngine:
         """Bit-identical records to the CPU engine with number_of_threads = threads (0: off)."""
         self._chk(self.lib.lk_set_reference_order(self._h, int(threads)))
 
+    def set_update(self, mode):
+        """UPDATE_FORWARD (default) or UPDATE_BACKWARD, the inverse-compositional solve (lk_set_update)."""
+        self._chk(self.lib.lk_set_update(self._h, int(mode)))
+
     def set_pairs_in_flight(self, n):
         """lk_set_pairs_in_flight: how many engines solve side by side on this GPU (before commit)."""
         self._chk(self.lib.lk_set_pairs_in_flight(self._h, int(n)))
@@ -348,6 +352,17 @@ class HipCorrelationEngine:
         self._chk(self.lib.lk_evaluate(self._h, sector, level, _ffi.fptr(pp), _ffi.fptr(A),
                                        _ffi.fptr(b), C.byref(chi), C.byref(err)))
         return A, b, chi.value, err.value
+
+    def evaluate_backward(self, sector, level, p):
+        """Template pass + one backward-mode evaluation: H (6x6, full), b, chi (unscaled), error."""
+        pp = np.zeros(6, np.float32)
+        pp[:len(p)] = p
+        H = np.zeros((6, 6), np.float32)
+        b = np.zeros(6, np.float32)
+        chi, err = C.c_float(), C.c_int()
+        self._chk(self.lib.lk_evaluate_backward(self._h, sector, level, _ffi.fptr(pp), _ffi.fptr(H),
+                                                _ffi.fptr(b), C.byref(chi), C.byref(err)))
+        return H, b, chi.value, err.value
 
     def sample(self, slot, level, xy):
         a = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)

@@ -137,6 +137,39 @@ int lk_set_batch_invariant(lk_engine *e, int enabled);
  * which differ from the reference by summation order and solver rounding only.
  * May be called at any time; the lane groups are re-chosen before the next solve. */
 int lk_set_reference_order(lk_engine *e, int threads);
+/* Update scheme of the LM solve (updateEnum, enums.hpp:39: the reference's GUI option "Update: Forward / Backward",
+ * which its engine stores and never reads).  May be called at any time; the next solve uses the new mode.
+ * LK_UPDATE_FORWARD (default): the forward-additive scheme of correlation_class.cpp:349-640 - every evaluation samples the
+ *   deformed image with its gradient and rebuilds A; p += dp.
+ * LK_UPDATE_BACKWARD: the inverse-compositional scheme (IC-GN).  For sector s at level L, with the forward solve's
+ *   level-L samples x_i and centre c:
+ *   template  T_i = und_L at the node (int)(x_i + 0.5f) (clamped), grad T_i = the interpolation model's gradient at that
+ *             integer node (what lk_sample(LK_IMG_UND, L, node) returns), G_i = grad T_i . dW/dp at x_i - c,
+ *             H = sum G_i G_i^T - once per sector and level.  A node the sampler flags as out of the image gives the
+ *             record LK_ERROR_INTERPOLATION_OUT_OF_IMAGE, as a failed evaluation #0 does.
+ *   evaluation V_i = T_i - def_L(W(x_i; p)) (the value-only form of the engine's sampler), b = sum G_i V_i,
+ *             chi = sum V_i^2 - the same chi and 1/n scaling as the forward mode.
+ *   step      delta = the damped solve of (H/n, b/n), H_ii *= 1 + lambda (compute_model_parameters,
+ *             correlation_class.cpp:642-700), by the engine's device solver (root-free Cholesky, pivoted-QR fallback, QR on
+ *             starved levels); the new parameters are W(p) o W(-delta)^-1 (lk_compose_inverse).  A singular step
+ *             (|det A_q| < 1e-6) counts as a diverging one: no evaluation, lambda x 10, the next trip starts from the
+ *             last good parameters.
+ *   control   the reference's LM loop otherwise: lambda x 0.4 down to 1e-9 / x 10 up to 1e9, the saved / tentative /
+ *             last-good parameter sets with the look-ahead step, the delta_chi rule, max_iters, error codes, iteration
+ *             counting, level-to-level translation; the record, lk_get_last_evaluated_parameters and the per-sector
+ *             counters as in the forward mode.  A rejected trip evaluates nothing: the kept b of the last good
+ *             parameters and the larger lambda give the next step.  A sector whose first evaluation fails reports the
+ *             iteration count of its own earlier levels (0 at the first), as the forward default mode does.
+ *   counters  lk_stats.evaluations / sample_evaluations count deformed-image passes (template passes are not counted);
+ *             algorithmic_bytes = 40 B per sample evaluation (16 B deformed window, 16 B template slot, 8 B list entry)
+ *             + 196 B per evaluation.
+ *   records   a sector's record depends on that sector, its images and its guess only: bit-identical in any batch, shard,
+ *             single-sector lk_correlate, lk_set_pairs_in_flight setting and sequence window (lk_set_batch_invariant has
+ *             no effect).  Sequence windows run their frames one after the other (lk_sequence_is_pipelined() == 0).
+ * Backward mode and reference-order mode exclude each other: whichever is set second returns LK_ERROR_BAD_DOMAIN. */
+#define LK_UPDATE_FORWARD 0
+#define LK_UPDATE_BACKWARD 1
+int lk_set_update(lk_engine *e, int mode);
 /* Independent image pairs can be solved side by side: one engine per pair in flight, each on
  * its own stream (lk_set_stream).  A solve ends in a tail of slow sectors that leaves most of
  * the GPU idle; the next pair's solve fills it (C2: 0.26 ms per pair one at a time, 0.15 ms
@@ -410,6 +443,15 @@ int lk_sample(lk_engine *e, int slot, int level, const float *xy, int n, float *
  * 16-lane row, as the finisher of parked sectors runs it (bit-identical to 1) */
 int lk_damped_solve(lk_engine *e, int n, const float *A_rowmajor_upper, const float *b,
                     float lambda, float scaling, int reference_solver, float *dp);
+/* backward mode's template pass + one evaluation of one sector at one level (lk_set_update), by the lane group its solve
+ * uses, whatever the mode: H (6x6 row-major, full), b, chi (all unscaled), error flag (template node or deformed sample
+ * out of the image) */
+int lk_evaluate_backward(lk_engine *e, int sector, int level, const float *p, float *H36, float *b6, float *chi,
+                         int *error);
+/* backward mode's parameter update on the host, the kernel's function: p_out = W(p) o W(delta)^-1 (the solve passes
+ * delta = -step).  Returns 1 for a singular delta (|det A_delta| < 1e-6; p_out untouched), 0 otherwise,
+ * LK_ERROR_BAD_DOMAIN for a bad model or a null pointer.  P = 1, 2, 3, 6 floats per parameter set. */
+int lk_compose_inverse(int model, const float *p, const float *delta, float *p_out);
 
 int lk_get_stats(lk_engine *e, lk_stats *out);
 /* the same counters per sector of the last solve, registration order:
