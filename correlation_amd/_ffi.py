@@ -141,6 +141,8 @@ SYMBOLS = {
     "lk_compose_inverse": (C.c_int, [C.c_int, _F, _F, _F]),
     "lk_sample": (C.c_int, [_P, C.c_int, C.c_int, _F, C.c_int, _F]),
     "lk_damped_solve": (C.c_int, [_P, C.c_int, _F, _F, C.c_float, C.c_float, C.c_int, _F]),
+    "lk_step_compare": (C.c_int, [_P, C.c_int, _F, _F]),
+    "lk_reduce_compare": (C.c_int, [_P, C.c_int, C.c_int, _F, _F]),
     "lk_get_stats": (C.c_int, [_P, C.POINTER(LkStats)]),
     "lk_get_sector_stats": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     # include/lk_tracker.h

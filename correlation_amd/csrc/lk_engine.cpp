@@ -37,6 +37,8 @@ hipError_t lk_launch_solve(const LkSolveArgs &a, int model, int interp, int grou
 hipError_t lk_launch_solve_seq(const LkSolveArgs &a, int model, int interp, int group, int flavour, hipStream_t st);
 hipError_t lk_launch_eval(const LkEvalArgs &a, int model, int interp, int group, hipStream_t st);
 hipError_t lk_launch_solve_only(int n, const float *d_in, float *d_out, hipStream_t st);
+hipError_t lk_launch_step_compare(int n, const float *d_in, float *d_out, hipStream_t st);
+hipError_t lk_launch_reduce_compare(int n, int wide, const float *d_in, float *d_out, hipStream_t st);
 hipError_t lk_launch_backward(const LkBackwardArgs &a, int model, int interp, int group, hipStream_t st);
 hipError_t lk_launch_backward_eval(const LkBackwardEvalArgs &a, int model, int interp, int group, hipStream_t st);
 hipError_t lk_launch_sample(int interp, const uint8_t *def, int rows, int cols, const float2 *pts, int n,
@@ -3639,6 +3641,46 @@ int lk_damped_solve(lk_engine *e, int n, const float *A, const float *b, float l
   for (int i = 0; i < n; ++i)
     dp[i] = o[i];
   return LK_ERROR_NONE;
+}
+
+// both known-answer hooks below: host arrays in, one launch, host arrays out (buffers of their own, freed on every path)
+static int compare_launch(lk_engine *e, const float *in, size_t n_in, float *out, size_t n_out,
+                          const std::function<hipError_t(const float *, float *)> &launch) {
+  HIPCHK(hipSetDevice(e->cfg.device));
+  DevBuf<float> d_in, d_out;
+  hipError_t err = d_in.ensure(n_in);
+  if (err == hipSuccess)
+    err = d_out.ensure(n_out);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(d_in.p, in, n_in * sizeof(float), hipMemcpyHostToDevice, e->stream);
+  if (err == hipSuccess)
+    err = launch(d_in.p, d_out.p);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(out, d_out.p, n_out * sizeof(float), hipMemcpyDeviceToHost, e->stream);
+  const hipError_t sync = hipStreamSynchronize(e->stream);
+  d_in.release();
+  d_out.release();
+  HIPCHK(err);
+  HIPCHK(sync);
+  return LK_ERROR_NONE;
+}
+
+int lk_step_compare(lk_engine *e, int n, const float *in40, float *out32) {
+  if (!e)
+    return LK_ERROR_BAD_DOMAIN;
+  if (n < 1 || !in40 || !out32)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_step_compare: n >= 1 systems of 40 floats in, 32 floats out each");
+  return compare_launch(e, in40, (size_t)n * 40, out32, (size_t)n * 32,
+                        [&](const float *i, float *o) { return lk_launch_step_compare(n, i, o, e->stream); });
+}
+
+int lk_reduce_compare(lk_engine *e, int n, int wide, const float *lanes, float *out) {
+  if (!e)
+    return LK_ERROR_BAD_DOMAIN;
+  if (n < 1 || !lanes || !out)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_reduce_compare: n >= 1 wavefronts of 64 x 28 floats in, twice that out");
+  return compare_launch(e, lanes, (size_t)n * 64 * 28, out, (size_t)n * 2 * 64 * 28,
+                        [&](const float *i, float *o) { return lk_launch_reduce_compare(n, wide, i, o, e->stream); });
 }
 
 int lk_get_stats(lk_engine *e, lk_stats *out) {

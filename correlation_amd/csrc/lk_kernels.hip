@@ -173,7 +173,7 @@ __device__ __forceinline__ bool team_all_to_all(SumsT &S, bool any_bad, float *l
   return any_bad;
 }
 
-template <int MODEL, int INTERP, int GROUP, int THREADS>
+template <int MODEL, int INTERP, int GROUP, int THREADS, bool SCATTER = false>
 __device__ __forceinline__ bool evaluate(const LevelCtx &c, const float (&p)[6],
                                          Sums<n_params(MODEL)> &S, float *lds, TeamCtx *team = nullptr,
                                          bool wide = false, bool ordered = false, int width = 0) {
@@ -414,6 +414,27 @@ __device__ __forceinline__ bool evaluate(const LevelCtx &c, const float (&p)[6],
     return bad; // nothing to reduce: the lane owns the whole sector
   // reconverged: all 64 lanes of every wave are active from here on
   const unsigned long long badmask = __ballot(bad);
+  if constexpr (SCATTER) {
+    // the fast 32-lane instance of lk_solve_kernel: the totals stay spread over the lanes of each 16-lane row (two per
+    // lane, S.v[0] and S.v[1]: row16_reduce_scatter28), where damped_step_scattered picks them up; chi, which the LM
+    // control reads before the solve, goes to every lane (S.v[N - 1]).  Same additions per sum as below.
+    static_assert(GROUP == 32 && SumsT::N == 28, "six-parameter models on 32-lane groups");
+    float s0, s1;
+    row16_reduce_scatter28(S.v, s0, s1);
+    s0 = add_partner_row(s0);
+    s1 = add_partner_row(s1);
+    if (wide) {
+      s0 = add_partner_half(s0);
+      s1 = add_partner_half(s1);
+    }
+    S.v[0] = s0;
+    S.v[1] = s1;
+    S.v[SumsT::N - 1] = scattered_sum<SumsT::N - 1>(s0, s1);
+    if (wide)
+      return badmask != 0ull;
+    const int half = ((int)threadIdx.x & 63) >> 5;
+    return ((badmask >> (32 * half)) & 0xffffffffull) != 0ull;
+  }
   // stage by stage over all sums (the same four additions per sum as row16_sum, in the same
   // order): 28 independent DPP adds per stage instead of 28 chains of four dependent ones with
   // the DPP hazard nops in between
@@ -1178,6 +1199,9 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
   using SumsT = Sums<P>;
   constexpr bool COLD_IN_LDS = GROUP > 1 && GROUP <= kWave;
   constexpr bool STARVED = GROUP == 1; // one lane per sector: solves only the starved top levels
+  // the fast 32-lane instance of the six-parameter models: the sums of an evaluation stay spread over the lanes of the
+  // 16-lane rows (reduce-scatter) and the solve collects them there (damped_step_scattered) - same bits, fewer instructions
+  constexpr bool SCATTER = GROUP == 32 && !SAFE && !REF && !SEQ && P == 6;
   // the 16-lane SAFE instance doubles as the finisher of that kernel's stragglers (a.finisher)
   const bool finisher = !REF && SAFE && GROUP == 16 && a.finisher != 0;
   // reference-order mode (lk_set_reference_order): the REF instances solve every level with the ordered sums
@@ -1821,7 +1845,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
       err = a.reference_order > 1 ? evaluate_ordered<MODEL, INTERP, GROUP, true>(ce, p, S, ord_lds, a.reference_order)
                                   : evaluate_ordered<MODEL, INTERP, GROUP, false>(ce, p, S, ord_lds, 1);
     } else {
-      err = evaluate<MODEL, INTERP, GROUP, THREADS>(ce, p, S, lds, &team, wide, row_ordered, GROUP == 16 ? width : 0);
+      err = evaluate<MODEL, INTERP, GROUP, THREADS, SCATTER>(ce, p, S, lds, &team, wide, row_ordered, GROUP == 16 ? width : 0);
     }
 #ifdef LK_TRACE
     tr_eval += __builtin_amdgcn_s_memtime() - tr_e0;
@@ -1919,7 +1943,11 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
         const unsigned long long tr_s0 = __builtin_amdgcn_s_memtime();
 #endif
         const bool step_starved = starved || (UNIFIED && row_ordered); // (an active row's own flag: see row_ordered)
-        const bool wc = damped_step<P, SAFE || STARVED>(S, lam_use, c.scaling, p, step_starved, nullptr, SAFE && GROUP >= 16 && GROUP <= kWave); // p += dp
+        bool wc;
+        if constexpr (SCATTER)
+          wc = damped_step_scattered(S.v[0], S.v[1], lam_use, c.scaling, p); // p += dp
+        else
+          wc = damped_step<P, SAFE || STARVED>(S, lam_use, c.scaling, p, step_starved, nullptr, SAFE && GROUP >= 16 && GROUP <= kWave); // p += dp
 #ifdef LK_TRACE
         tr_solve += __builtin_amdgcn_s_memtime() - tr_s0;
 #endif
@@ -2164,6 +2192,112 @@ template <int P> __global__ void lk_solve_only_kernel(const float *in, float *dp
   if (threadIdx.x == 0 && blockIdx.x == 0)
     for (int i = 0; i < 6; ++i)
       dp_out[i] = i < P ? dp[i] : 0.f;
+}
+
+// known-answer hook of the scattered step (lk_step_compare): one wavefront runs, per system, the register
+// damped_step<6, false> and damped_step_scattered on the same 28 sums - the latter from the layout row16_reduce_scatter28
+// leaves them in (lane scatter_owner(v) holds sums v & ~1 and v | 1; the places of sums 28..31 take whatever the record
+// holds there, nobody reads them).
+// in: [n][40] = 28 sums, lambda, scaling, p[6], 4 unused;  out: [n][2][16] = x[6], p[6], flag, then [0]: unused, [1]: 1 when
+// every lane of the wavefront ended with lane 0's bits, 2 unused
+__global__ void __launch_bounds__(kWave) lk_step_compare_kernel(const float *in, float *out, int n) {
+  const int l = (int)threadIdx.x;
+  const int b0 = l & 1, b1 = (l >> 1) & 1, b2 = (l >> 2) & 1, b3 = (l >> 3) & 1;
+  const int mine = ((b0 ^ b2) << 4) | ((b1 ^ b2) << 3) | ((b2 ^ b3) << 2) | (b3 << 1); // scatter_owner(mine) == l & 15
+  for (int i = (int)blockIdx.x; i < n; i += (int)gridDim.x) {
+    const float *q = in + (size_t)i * 40;
+    Sums<6> S;
+#pragma unroll
+    for (int k = 0; k < 28; ++k)
+      S.v[k] = q[k];
+    const float lambda = q[28], scaling = q[29];
+    float pr[6], ps[6], xr[6], xs[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+      pr[k] = ps[k] = q[30 + k];
+    const bool fr = damped_step<6, false>(S, lambda, scaling, pr, false, xr);
+    const bool fs = damped_step_scattered(q[mine], q[mine + 1], lambda, scaling, ps, xs);
+    bool same = __builtin_amdgcn_readfirstlane((int)fs) == (int)fs;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+      same = same && __builtin_amdgcn_readfirstlane((int)__float_as_uint(xs[k])) == (int)__float_as_uint(xs[k]) &&
+             __builtin_amdgcn_readfirstlane((int)__float_as_uint(ps[k])) == (int)__float_as_uint(ps[k]);
+    const bool all_same = __ballot(same) == ~0ull;
+    if (l == 0) {
+      float *o = out + (size_t)i * 32;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        o[k] = xr[k];
+        o[6 + k] = pr[k];
+        o[16 + k] = xs[k];
+        o[22 + k] = ps[k];
+      }
+      o[12] = fr ? 1.f : 0.f;
+      o[28] = fs ? 1.f : 0.f;
+      o[13] = o[14] = o[15] = o[30] = o[31] = 0.f;
+      o[29] = all_same ? 1.f : 0.f;
+    }
+  }
+}
+
+// the all-reduce of evaluate<>'s 32-lane groups restated for the hook below, statement for statement: the four DPP stages ...
+template <int N> __device__ __forceinline__ void row16_all_reduce(float (&v)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    v[i] = dpp_add<0xB1>(v[i]); // quad_perm [1,0,3,2]
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    v[i] = dpp_add<0x4E>(v[i]); // quad_perm [2,3,0,1]
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    v[i] = dpp_add<0x141>(v[i]); // row_half_mirror
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    v[i] = dpp_add<0x140>(v[i]); // row_mirror
+}
+
+// ... the partner row and, `wide` (solo), the partner half of the wavefront
+template <int N> __device__ __forceinline__ void partner_rows_all_reduce(float (&v)[N], bool wide) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    v[i] += __shfl_xor(v[i], 16, 64);
+  if (wide) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+      v[i] += __shfl_xor(v[i], 32, 64);
+  }
+}
+
+// ... and of the reduce-scatter (lk_reduce_compare): the 64 lanes of a wavefront hold 28 partial sums each; the all-reduce
+// of evaluate<>'s 32-lane groups (four DPP stages, partner row, `wide`: partner half) against the reduce-scatter of the
+// fast instance read back by row_newbcast, every sum in every lane.  in: [n][64][28];  out: [n][2][64][28]
+__global__ void __launch_bounds__(kWave) lk_reduce_compare_kernel(const float *in, float *out, int n, int wide) {
+  const int l = (int)threadIdx.x;
+  for (int i = (int)blockIdx.x; i < n; i += (int)gridDim.x) {
+    const float *q = in + ((size_t)i * kWave + (size_t)l) * 28;
+    float v[28], t[28];
+#pragma unroll
+    for (int k = 0; k < 28; ++k)
+      v[k] = t[k] = q[k];
+    row16_all_reduce(v);
+    partner_rows_all_reduce(v, wide != 0);
+    float s0, s1;
+    row16_reduce_scatter28(t, s0, s1);
+    s0 = add_partner_row(s0);
+    s1 = add_partner_row(s1);
+    if (wide) {
+      s0 = add_partner_half(s0);
+      s1 = add_partner_half(s1);
+    }
+    float g[28];
+    gather_scattered(g, s0, s1, std::make_integer_sequence<int, 28>{});
+    float *o = out + ((size_t)i * 2 * kWave + (size_t)l) * 28;
+#pragma unroll
+    for (int k = 0; k < 28; ++k) {
+      o[k] = v[k];
+      o[(size_t)kWave * 28 + k] = g[k];
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------
@@ -3552,6 +3686,16 @@ hipError_t lk_launch_eval(const LkEvalArgs &a, int model, int interp, int group,
   case LK_FM_UVQ: return launch_eval_m<LK_FM_UVQ>(a, interp, group, st);
   default: return launch_eval_m<LK_FM_UVUXUYVXVY>(a, interp, group, st);
   }
+}
+
+hipError_t lk_launch_step_compare(int n, const float *d_in, float *d_out, hipStream_t st) {
+  hipLaunchKernelGGL(lk_step_compare_kernel, dim3(n < 256 ? n : 256), dim3(kWave), 0, st, d_in, d_out, n);
+  return hipGetLastError();
+}
+
+hipError_t lk_launch_reduce_compare(int n, int wide, const float *d_in, float *d_out, hipStream_t st) {
+  hipLaunchKernelGGL(lk_reduce_compare_kernel, dim3(n < 256 ? n : 256), dim3(kWave), 0, st, d_in, d_out, n, wide);
+  return hipGetLastError();
 }
 
 hipError_t lk_launch_solve_only(int n, const float *d_in, float *d_out, hipStream_t st) {

@@ -9,6 +9,8 @@
 #include <float.h>
 #include <stdint.h>
 
+#include <utility>
+
 // Smallest pivot ratio d_j / A_jj the fast flavour factors through (below it the sector goes to
 // the SAFE kernel and the reference's QR).  1e-3 sent 0.4 % of config 4's solves there and, before
 // that pass existed, cost its 1 % tail a factor of ten against the reference; root-free Cholesky
@@ -43,6 +45,79 @@ template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
 // lane I of the own 16-lane row (row_newbcast, gfx90a and later)
 template <int I> __device__ __forceinline__ float dpp_bcast(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + I, 0xF, 0xF, false));
+}
+
+// ------------------------------------------------------------------------------------
+// reduce-scatter of the 28 sums of a six-parameter model inside a 16-lane row
+// ------------------------------------------------------------------------------------
+// The all-reduce of evaluate<> sends every sum through the same four DPP stages (quad_perm [1,0,3,2], quad_perm
+// [2,3,0,1], row_half_mirror, row_mirror): 4 x 28 adds, after which every lane of the row holds every total.  Here a
+// lane keeps, at each stage, only half of the sums it still carries and adds its partner's copy of those:
+// 28 -> 16 -> 8 -> 4 -> 2 sums per lane, 12 * 3 + 4 + (8 + 4 + 2) * 3 = 82 instructions instead of 112, and - what
+// pays - two sums per lane instead of 28 for the row-to-row additions that follow.  Every sum still goes through
+// the additions (v[l] + v[l^1]) -> (.. + ..[l^2]) -> (quad + mirrored quad) -> (half + mirrored half) of the
+// all-reduce; which of the two operands of an addition is "own" differs from lane to lane there as well
+// (a + b == b + a), so the totals are the all-reduce's, bit for bit.
+// The mirrors pair lane l with lane 7 - l / 15 - l, whose low bits differ from l's: which half a lane keeps at a
+// stage is therefore decided by the bits e0 = b0 ^ b2, e1 = b1 ^ b2, e2 = b2 ^ b3, e3 = b3 of its lane number b3 b2 b1 b0
+// - each stage's partner differs in exactly that stage's bit.  Sum v (of 32: 28..31 do not exist, their places
+// hold copies of sums 12..15) ends in the lane with (e0, e1, e2, e3) = bits (4, 3, 2, 1) of v, in slot v & 1.
+constexpr int scatter_owner(int v) { // the lane of the 16-lane row that ends with sums v & ~1 and v | 1
+  const int e0 = (v >> 4) & 1, e1 = (v >> 3) & 1, e2 = (v >> 2) & 1, e3 = (v >> 1) & 1;
+  const int b3 = e3, b2 = e2 ^ b3, b0 = e0 ^ b2, b1 = e1 ^ b2;
+  return b0 | (b1 << 1) | (b2 << 2) | (b3 << 3);
+}
+
+template <int CTRL, int HALF> __device__ __forceinline__ void scatter_stage(float *t, bool upper) {
+#pragma unroll
+  for (int i = 0; i < HALF; ++i) {
+    const float keep = upper ? t[HALF + i] : t[i], send = upper ? t[i] : t[HALF + i];
+    const int got = __builtin_amdgcn_update_dpp(0, __float_as_int(send), CTRL, 0xF, 0xF, true);
+    t[i] = keep + __int_as_float(got);
+  }
+}
+
+// v[0..27] (one lane's partial sums) -> s0, s1: the row's totals of sums 2m and 2m + 1 in lane scatter_owner(2m)
+__device__ __forceinline__ void row16_reduce_scatter28(const float (&v)[28], float &s0, float &s1) {
+  const int l = (int)threadIdx.x;
+  const bool b2 = (l & 4) != 0, b3 = (l & 8) != 0;
+  float t[16];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) { // quad_perm [1,0,3,2]: sums i and 16 + i
+    const bool upper = ((l & 1) != 0) != b2;
+    const float keep = upper ? v[16 + i] : v[i], send = upper ? v[i] : v[16 + i];
+    const int got = __builtin_amdgcn_update_dpp(0, __float_as_int(send), 0xB1, 0xF, 0xF, true);
+    t[i] = keep + __int_as_float(got);
+  }
+#pragma unroll
+  for (int i = 12; i < 16; ++i) // (no sums 28..31: both lanes of the pair keep sum i)
+    t[i] = dpp_add<0xB1>(v[i]);
+  scatter_stage<0x4E, 8>(t, ((l & 2) != 0) != b2); // quad_perm [2,3,0,1]
+  scatter_stage<0x141, 4>(t, b2 != b3);            // row_half_mirror
+  scatter_stage<0x140, 2>(t, b3);                  // row_mirror
+  s0 = t[0];
+  s1 = t[1];
+}
+
+// v + the same lane's value in the partner row (rows 0/1 and 2/3), and in the partner half of the wavefront:
+// one VALU swap and one add, no LDS crossbar (__shfl_xor: address, ds_bpermute, wait, add)
+__device__ __forceinline__ float add_partner_row(float v) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float add_partner_half(float v) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// lane scatter_owner(V) of the own row's slot for sum V
+template <int V> __device__ __forceinline__ float scattered_sum(float s0, float s1) {
+  return dpp_bcast<scatter_owner(V)>((V & 1) ? s1 : s0);
+}
+
+template <int... V>
+__device__ __forceinline__ void gather_scattered(float *S, float s0, float s1, std::integer_sequence<int, V...>) {
+  ((S[V] = scattered_sum<V>(s0, s1)), ...);
 }
 
 __device__ __forceinline__ uint32_t load_u32_unaligned(gptr<uint8_t> p) {
@@ -795,6 +870,82 @@ __device__ __forceinline__ bool damped_step(const Sums<P> &S, float lambda, floa
       dp_out[i] = x[i];
   }
   return well_conditioned; // false: a pivot was bad (fast flavour: that parameter's step is zero; SAFE: the QR ran)
+}
+
+// The fast flavour (damped_step<6, false>) on sums that row16_reduce_scatter28 left spread over the 16-lane row: s0, s1
+// are the lane's two totals.  The lane scales its own two sums (2 multiplications instead of 27), every lane then
+// collects the 27 scaled values by row_newbcast, and from there on each element sees the operations of damped_step<>
+// in the same order: (1 + lambda) on the diagonal, dmax, the fma chains of the root-free Cholesky, the pivot test,
+// the zeroed step of a bad pivot, both substitutions.  Same bits in x, p and the returned flag
+// (tests/test_distributed_step_gpu.py runs both in one launch).
+__device__ __forceinline__ bool damped_step_scattered(float s0, float s1, float lambda, float scaling, float (&p)[6],
+                                                      float *dp_out = nullptr) {
+  constexpr int P = 6, NA = Sums<P>::NA;
+  s0 *= scaling; // :647-651
+  s1 *= scaling;
+  float S[NA + P];
+  gather_scattered(S, s0, s1, std::make_integer_sequence<int, NA + P>{});
+  float U[P][P], d[P], inv_d[P], y[P], x[P];
+  int idx = 0;
+  float dmax = 0.f;
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+#pragma unroll
+    for (int j = i; j < P; ++j) {
+      float a = S[idx++];
+      if (i == j) {
+        a *= (1.f + lambda); // :664
+        dmax = fmaxf(dmax, a);
+      }
+      U[i][j] = a;
+    }
+    y[i] = S[NA + i];
+  }
+  bool well_conditioned = true;
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    float w[P];
+    const float ajj = U[j][j];
+    float dj = ajj;
+#pragma unroll
+    for (int k = 0; k < j; ++k) {
+      w[k] = U[k][j] * d[k];
+      dj = __builtin_fmaf(-U[k][j], w[k], dj);
+    }
+    const bool ok = dj > ajj * LK_FAST_PIVOT && dj > dmax * 1e-7f; // false for NaN as well
+    well_conditioned = well_conditioned && ok;
+    d[j] = ok ? dj : 0.f;
+    inv_d[j] = ok ? __builtin_amdgcn_rcpf(dj) : 0.f;
+#pragma unroll
+    for (int i = j + 1; i < P; ++i) {
+      float t = U[j][i];
+#pragma unroll
+      for (int k = 0; k < j; ++k)
+        t = __builtin_fmaf(-w[k], U[k][i], t);
+      U[j][i] = t * inv_d[j];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+#pragma unroll
+    for (int k = 0; k < j; ++k)
+      y[j] = __builtin_fmaf(-U[k][j], y[k], y[j]);
+  }
+#pragma unroll
+  for (int j = P - 1; j >= 0; --j) {
+    float t = y[j] * inv_d[j];
+#pragma unroll
+    for (int i = j + 1; i < P; ++i)
+      t = __builtin_fmaf(-U[j][i], x[i], t);
+    x[j] = t;
+  }
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    p[i] += x[i]; // :687-688
+    if (dp_out)
+      dp_out[i] = x[i];
+  }
+  return well_conditioned;
 }
 
 // translate_model_parameters (pyramid_class.cpp:260-287)

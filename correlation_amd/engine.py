@@ -379,6 +379,21 @@ class HipCorrelationEngine:
                                            int(reference_solver), _ffi.fptr(dp)))
         return dp
 
+    def step_compare(self, systems):
+        """[n][40] float32 (28 sums, lambda, scaling, p[6], 4 unused) -> [n][2][16]: x[6], p[6], flag, ... of the register
+        solver and of the scattered one (include/lk_engine.h: lk_step_compare)."""
+        a = np.ascontiguousarray(systems, np.float32).reshape(-1, 40)
+        out = np.zeros((a.shape[0], 2, 16), np.float32)
+        self._chk(self.lib.lk_step_compare(self._h, a.shape[0], _ffi.fptr(a), _ffi.fptr(out)))
+        return out
+
+    def reduce_compare(self, lanes, wide=False):
+        """[n][64][28] float32 partial sums -> [n][2][64][28]: all-reduce and reduce-scatter totals in every lane."""
+        a = np.ascontiguousarray(lanes, np.float32).reshape(-1, 64, 28)
+        out = np.zeros((a.shape[0], 2, 64, 28), np.float32)
+        self._chk(self.lib.lk_reduce_compare(self._h, a.shape[0], int(bool(wide)), _ffi.fptr(a), _ffi.fptr(out)))
+        return out
+
     def stats(self):
         s = LkStats()
         self._chk(self.lib.lk_get_stats(self._h, C.byref(s)))

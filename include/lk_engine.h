@@ -443,6 +443,15 @@ int lk_sample(lk_engine *e, int slot, int level, const float *xy, int n, float *
  * 16-lane row, as the finisher of parked sectors runs it (bit-identical to 1) */
 int lk_damped_solve(lk_engine *e, int n, const float *A_rowmajor_upper, const float *b,
                     float lambda, float scaling, int reference_solver, float *dp);
+/* Known-answer hooks of the fast 32-lane solve instance of the six-parameter models, which leaves the 28 sums of an
+ * evaluation spread over the lanes of a 16-lane row and solves from there.
+ * lk_step_compare: n systems of 40 floats (28 raw sums: upper triangle row-major, b, chi; lambda; scaling; p[6]; 4 unused).
+ * One launch runs the register solver and the scattered one on each; out32 per system: x[6], p[6], flag, 3 unused of the
+ * register solver, then x[6], p[6], flag, "all 64 lanes agree" (1 / 0), 2 unused of the scattered one.
+ * lk_reduce_compare: n wavefronts of 64 lanes x 28 partial sums; out[n][2][64][28]: every lane's totals by the all-reduce
+ * of the 32-lane groups (wide != 0: of the whole wavefront, "solo"), then by the reduce-scatter read back in every lane. */
+int lk_step_compare(lk_engine *e, int n, const float *in40, float *out32);
+int lk_reduce_compare(lk_engine *e, int n, int wide, const float *lanes, float *out);
 /* backward mode's template pass + one evaluation of one sector at one level (lk_set_update), by the lane group its solve
  * uses, whatever the mode: H (6x6 row-major, full), b, chi (all unscaled), error flag (template node or deformed sample
  * out of the image) */
