@@ -122,6 +122,8 @@ struct LkSolveArgs {
   const uint32_t *seq_gate;     // the SAFE pass behind a window's fast flavour: that pass's seq_flags[1] - the launch does
                                 //   nothing while it is 0 (nullptr: no gate)
   int seq_fault;                // test hook (LK_SEQ_FAULT = f + 1): frame f of the launch's first sector never publishes - the bounded wait's exit
+  int slot_step;                // test hook (LK_STEP_STATE=0), fast 32-lane instance of the six-parameter models: 1 = every step moves the whole
+                                //   cold slot through LDS (the earlier form of the step, kept for the side-by-side test) - same records
 };
 
 // ROI -> level-0 sample lists on the device (cudaPolygon's mask + compaction, cuda_polygon.cuh:180-292,

@@ -285,7 +285,7 @@ struct lk_engine {
   DevBuf<uint32_t> d_mid, d_finish_list, d_finish_count; // stragglers of the starved-level kernel
   DevBuf<uint32_t> d_ill_list, d_ill_count;              // sectors whose damped system met a bad pivot
   DevBuf<uint32_t> d_mean_scratch;                       // chunk table / sums / maps of lk_mean_center_int_kernel
-  int starved_max = -1; // LK_STARVED_MAX as read by the last commit (-1: the default, 2 P)
+  int starved_max = -1; // LK_STARVED_MAX as read by the last commit (-1: the default, 2 P; kStarvedNone: no level is starved)
   int eval_cap = 20; // evaluations a lane of the starved-level kernel spends on one sector (0: no cap; config 4: 12 / 16 / 20 / 24 / 32 -> 2.00 / 1.91 / 1.88 / 1.92 / 2.08 ms)
   int team_w = 0; // workgroups per sector of the team class
   int team_min_samples = 0; // per-sector team sizing (0: every team has team_w workgroups)
@@ -1041,12 +1041,15 @@ int lk_set_sector_points(lk_engine *e, int sector, const float *xy, int n, int u
 // h_rect and h_off of the coarsest level.
 // (the tuning hook LK_STARVED_MAX is read at every commit and kept with the engine: the host's class table and
 // the kernel's hand-over rule must agree)
-static int starved_max(const lk_engine *e) { return e->starved_max >= 0 ? e->starved_max : 2 * e->P; }
+// (LK_STARVED_MAX=none: no level is starved - "at most -1 samples" - so that the lane groups solve every level themselves, a level
+// without a sample included; tests/test_step_state_gpu.py)
+constexpr int kStarvedNone = -2;
+static int starved_max(const lk_engine *e) { return e->starved_max == kStarvedNone ? -1 : e->starved_max >= 0 ? e->starved_max : 2 * e->P; }
 static int refresh_starved(lk_engine *e) {
   const int S = (int)e->h_class.size();
   {
     const char *f = std::getenv("LK_STARVED_MAX"); // tuning hook (tests/tools/c4_parity.py)
-    e->starved_max = f ? std::atoi(f) : -1;
+    e->starved_max = !f ? -1 : std::strcmp(f, "none") == 0 ? kStarvedNone : std::atoi(f) >= 0 ? std::atoi(f) : -1;
   }
   for (int c = 0; c < kNumClasses; ++c)
     e->class_starved[c] = false;
@@ -2356,6 +2359,8 @@ static LkSolveArgs base_args(lk_engine *e, const float *d_guess, lk_result *d_re
   a.align = align;
   const char *ks = std::getenv("LK_KEEP_SUMS"); // test hook, read per call
   a.keep_sums = ks ? (std::atoi(ks) != 0 ? 1 : 0) : 1;
+  const char *ss = std::getenv("LK_STEP_STATE"); // test hook, read per call (tests/test_step_state_gpu.py)
+  a.slot_step = ss && std::atoi(ss) == 0 ? 1 : 0;
   a.starved_max = starved_max(e);
   return a;
 }

@@ -1162,6 +1162,28 @@ template <bool IN_LDS, bool VEC = false> struct ColdStore {
   }
 };
 
+// The words of the cold state that EVERY step reads and writes - damping, last good chi, the trip count and the three counters -
+// stay in registers across the evaluation in the fast 32-lane instance of the six-parameter models (six VGPRs: the instance
+// stays under the 128 of four wavefronts per SIMD); the slot in LDS holds the words that only a rejection, a level change, an
+// error, a parked sector or the final record reads, and their copies of these six are brought up to date wherever the slot is read.
+template <bool ON> struct HotState {
+  __device__ __forceinline__ void take(const Cold &) {}
+  __device__ __forceinline__ void give(Cold &) const {}
+};
+template <> struct HotState<true> {
+  float lambda = 0.f, lg_chi = 0.f;
+  int iteration = 0;
+  uint32_t n_evals = 0u, n_sample_evals = 0u, n_point_iters = 0u;
+  __device__ __forceinline__ void take(const Cold &k) {
+    lambda = k.lambda, lg_chi = k.lg_chi, iteration = k.iteration;
+    n_evals = k.n_evals, n_sample_evals = k.n_sample_evals, n_point_iters = k.n_point_iters;
+  }
+  __device__ __forceinline__ void give(Cold &k) const {
+    k.lambda = lambda, k.lg_chi = lg_chi, k.iteration = iteration;
+    k.n_evals = n_evals, k.n_sample_evals = n_sample_evals, k.n_point_iters = n_point_iters;
+  }
+};
+
 #ifndef LK_MIN_WAVES
 #define LK_MIN_WAVES 1
 #endif
@@ -1229,6 +1251,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
   __shared__ __attribute__((aligned(16))) uint32_t cold_lds[COLD_IN_LDS ? (THREADS / GROUP) * kSlotWords : 4];
   uint32_t *cold_slot = cold_lds + (COLD_IN_LDS ? ((int)threadIdx.x / GROUP) * kSlotWords : 0);
   ColdStore<COLD_IN_LDS, GROUP == 32> cold;
+  HotState<SCATTER> hot; // (see HotState; a.slot_step: the whole slot through LDS at every step instead, tests only)
   // (one lane per sector: a column of LDS per lane - 28 more registers would cost the kernel a wavefront per SIMD,
   // and config 5's 3100 wavefronts of it a second round)
   __shared__ float kept_lds[KEEP_SUMS && !COLD_IN_LDS ? SumsT::N * THREADS : 1];
@@ -1557,6 +1580,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
           k.sums_kept = 0; // (the sums did not travel with the parked sector)
           level_context(k);
           cold.store(cold_slot, k);
+          hot.take(k);
         } else {
           phase = PH_EXIT;
         }
@@ -1594,6 +1618,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
         } else {
           enter_level(k);
           cold.store(cold_slot, k);
+          hot.take(k);
         }
       } else {
         phase = PH_EXIT;
@@ -1741,6 +1766,10 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
           take_ptr(c.und), take_ptr(c.def), take_ptr(c.xy);
           take(phase);
           take(cur_level);
+          if constexpr (SCATTER) {
+            take(hot.lambda), take(hot.lg_chi), take(hot.iteration);
+            take(hot.n_evals), take(hot.n_sample_evals), take(hot.n_point_iters);
+          }
           if (!active)
             cold_slot = cold_lds + (((int)threadIdx.x / GROUP) ^ 1) * kSlotWords;
           active = true;
@@ -1869,7 +1898,124 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
         continue;
       }
     }
-    if (active) {
+    if constexpr (SCATTER) {
+      // The step of this instance (no kept sums, no starved levels, no hand-over: what is left of the state machine below).  A
+      // step that stays inside its level - evaluation #0, or a tentative evaluation that has not converged - reads no word of
+      // the slot: chi, the verdict on it and the convergence test are formed BEFORE the solve (they need chi alone, so their
+      // division runs in the shadow of the factorisation's chains instead of behind them), the updates are selects, and the
+      // slot sees three stores (lg_p on an accepted trip, use_saved, reached).  Errors, the bad-pivot park, level changes and
+      // the final record take the whole slot, with the register words laid over it, through the code of the general form.
+      // What mirrors what in the general form below (a fix to one has to reach the other): the selects of PH_EVAL0 / PH_TENT = its
+      // phase ladder after the solve plus its `if (iter_start)` block; `ill` = its `ill_parked` block; the `err` branch, `maxed` and
+      // the `level_end` / `finished` blocks of the rare part = its blocks of the same names.  Not here because this instance never
+      // compiles them in: `redo` / keep_sums (KEEP_SUMS), `handed` and the eval_cap park (STARVED), the SEQ flag.
+      if (active && a.slot_step == 0) {
+        constexpr int W_LG_P = (int)(offsetof(Cold, lg_p) / 4), W_REACHED = (int)(offsetof(Cold, reached) / 4);
+        constexpr int W_USE_SAVED = (int)(offsetof(Cold, use_saved) / 4), W_N_ILL = (int)(offsetof(Cold, n_ill) / 4);
+        static_assert(W_LG_P == 0, "lg_p: one 128-bit and one 64-bit access at the head of the slot");
+        float evaluated[6]; // the parameters this evaluation ran at = where the solve starts from
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+          evaluated[i] = p[i];
+        const int evaluated_level = cur_level;
+        ++hot.n_evals;
+        hot.n_sample_evals += (uint32_t)c.n;
+        bool level_end = false, finished = false, maxed = false, ill = false;
+        if (!err) {
+          const float chi = S.v[SumsT::N - 1] * c.scaling;
+          const bool eval0 = phase == PH_EVAL0, tent = phase == PH_TENT;
+          const float lam_down = fmaxf(hot.lambda * 0.4f, min_lambda);
+          const float lam_use = tent ? lam_down : hot.lambda;
+          const bool accept = eval0 || chi <= hot.lg_chi;
+          const float delta_chi = __builtin_fabsf((hot.lg_chi - chi) / (fmaxf(hot.lg_chi, chi) + a.precision));
+          const bool conv = tent && delta_chi < a.precision;
+#ifdef LK_TRACE
+          const unsigned long long tr_s0 = __builtin_amdgcn_s_memtime();
+#endif
+          const bool wc = damped_step_scattered(S.v[0], S.v[1], lam_use, c.scaling, p); // p += dp
+#ifdef LK_TRACE
+          tr_solve += __builtin_amdgcn_s_memtime() - tr_s0;
+#endif
+          if (!wc && a.ill_list) {
+            ill = true; // a bad pivot: the sector goes to the SAFE kernel as it was before this evaluation (below)
+          } else {
+            if (!wc)
+              ++cold_slot[W_N_ILL];
+            if (phase == PH_REEVAL) {
+              phase = PH_TENT; // p now holds the tentative parameters
+            } else { // PH_EVAL0 (:410-437) and PH_TENT (:503-529; p now holds the look-ahead parameters), then the top of the iteration loop (:441-499)
+              if (tent && accept) {
+                *reinterpret_cast<uint4 *>(cold_slot) = make_uint4(__float_as_uint(evaluated[0]), __float_as_uint(evaluated[1]),
+                                                                   __float_as_uint(evaluated[2]), __float_as_uint(evaluated[3]));
+                *reinterpret_cast<uint2 *>(cold_slot + 4) = make_uint2(__float_as_uint(evaluated[4]), __float_as_uint(evaluated[5]));
+              }
+              hot.lambda = eval0 ? hot.lambda : accept ? lam_down : fminf(hot.lambda * 10.0f, max_lambda);
+              hot.lg_chi = accept ? chi : hot.lg_chi;
+              hot.iteration = eval0 ? 1 : conv ? hot.iteration : hot.iteration + 1;
+              hot.n_point_iters += eval0 ? 1u : 0u;
+              cold_slot[W_USE_SAVED] = accept ? 1u : 0u;
+              maxed = !conv && (hot.iteration > a.max_iters || hot.lambda >= max_lambda);
+              level_end = conv || maxed;
+              if (!level_end) {
+                cold_slot[W_REACHED] = (uint32_t)hot.iteration;
+                ++hot.n_point_iters;
+                phase = accept ? PH_TENT : PH_REEVAL; // tentative = saved = p, or back to the last good parameters
+                if (!accept) {
+#pragma unroll
+                  for (int i = 0; i < P; ++i)
+                    p[i] = __uint_as_float(cold_slot[W_LG_P + i]);
+                }
+              }
+            }
+          }
+        }
+        if (err || ill || level_end) {
+          Cold k = cold.load(cold_slot);
+          hot.give(k);
+          if (err) { // :413-419 (evaluation #0: return at once), :484-489, :511-516 (break)
+            k.error = LK_ERROR_INTERPOLATION_OUT_OF_IMAGE;
+            if (phase == PH_EVAL0) {
+              ++k.n_point_iters;
+              translate<P>(p, k.level, 0);
+              finished = true;
+            } else {
+              level_end = true;
+            }
+          }
+          if (ill) { // undo the step; the evaluation is the SAFE kernel's to repeat
+            ++k.n_ill;
+#pragma unroll
+            for (int i = 0; i < P; ++i)
+              p[i] = evaluated[i];
+            --k.n_evals;
+            k.n_sample_evals -= (uint32_t)c.n;
+            k.sums_kept = 0;
+            park(k, a.ill_list, a.ill_count);
+          } else {
+            if (maxed)
+              k.error = LK_ERROR_CORRELATION_MAX_ITERS_REACHED;
+            if (level_end) { // :589-591, :638
+              k.level_old = k.level;
+              k.level -= a.py_step;
+              if (k.level < a.py_start) {
+                translate<P>(p, k.level_old, 0);
+                finished = true;
+              } else {
+                enter_level(k);
+              }
+            }
+            if (finished) {
+              translate<P>(evaluated, evaluated_level, 0);
+              finish_sector(k, evaluated);
+            } else {
+              cold.store(cold_slot, k);
+              hot.take(k);
+            }
+          }
+        }
+      }
+    }
+    if (active && (!SCATTER || a.slot_step != 0)) {
       Cold k = cold.load(cold_slot);
       float evaluated[6]; // the parameters this evaluation ran at (rescaled to level 0 only if the sector ends here)
 #pragma unroll
