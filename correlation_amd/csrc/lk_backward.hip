@@ -13,6 +13,7 @@
 // readlane across rows, LDS across wavefronts) have one fixed order: a sector's record is the same bits in any launch.
 #include "lk_device.hpp"
 #include "lk_compose.hpp"
+#include "lk_launch.hpp"
 #include "lk_solver_common.hpp"
 
 #include <type_traits>

@@ -17,6 +17,7 @@
 #include "lk_compose.hpp"
 #include "lk_device.hpp"
 #include "lk_internal.hpp"
+#include "lk_launch.hpp"
 #include "lk_roi.hpp"
 
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -32,41 +33,6 @@
 #include <string>
 #include <thread>
 #include <vector>
-
-hipError_t lk_launch_solve(const LkSolveArgs &a, int model, int interp, int group, hipStream_t st);
-hipError_t lk_launch_solve_seq(const LkSolveArgs &a, int model, int interp, int group, int flavour, hipStream_t st);
-hipError_t lk_launch_eval(const LkEvalArgs &a, int model, int interp, int group, hipStream_t st);
-hipError_t lk_launch_solve_only(int n, const float *d_in, float *d_out, hipStream_t st);
-hipError_t lk_launch_step_compare(int n, const float *d_in, float *d_out, hipStream_t st);
-hipError_t lk_launch_reduce_compare(int n, int wide, const float *d_in, float *d_out, hipStream_t st);
-hipError_t lk_launch_backward(const LkBackwardArgs &a, int model, int interp, int group, hipStream_t st);
-hipError_t lk_launch_backward_eval(const LkBackwardEvalArgs &a, int model, int interp, int group, hipStream_t st);
-hipError_t lk_launch_sample(int interp, const uint8_t *def, int rows, int cols, const float2 *pts, int n,
-                            float4 *out, hipStream_t st);
-hipError_t lk_launch_pyramid(const uint8_t *src, int srows, int scols, uint8_t *dst, hipStream_t st);
-hipError_t lk_launch_set_views(const LkLevelView *h_views, LkLevelView *d_views, hipStream_t st);
-hipError_t lk_launch_pyramid2(int n_images, const uint8_t *const *src, const int *step, int rows, int cols,
-                              uint8_t *const *l0, uint8_t *const *l1, uint8_t *const *l2, hipStream_t st);
-hipError_t lk_launch_guess(const float2 *center, const float *last_p, float *prev_p, float *guess,
-                           const float *global_guess, float gcx, float gcy, int n_sectors, int model,
-                           int frame, int constant_velocity, hipStream_t st);
-hipError_t lk_launch_warp_points(const float2 *xy, int n, float cx, float cy, int model, const float *d_p,
-                                 float2 *out, hipStream_t st);
-hipError_t lk_launch_rewarp(const LkRewarpArgs &a, int model, hipStream_t st);
-int lk_decimate_tiles(uint32_t n_max);
-hipError_t lk_launch_decimate(const float2 *xy_prev, const uint32_t *off_prev, const uint32_t *n_prev, uint32_t n_max,
-                              int level_delta, int n_sectors, uint32_t *pos, uint32_t *tiles, float2 *xy_out,
-                              uint32_t *off_out, uint32_t *n_out, hipStream_t st);
-hipError_t lk_launch_roi_count(const LkRoiSector *sectors, const LkRoiFlat *flats, const uint32_t *tile_begin, int n_sectors,
-                               uint32_t n_tiles, uint32_t *tiles, uint32_t *n_out, hipStream_t st, int rows = 0);
-hipError_t lk_launch_roi_fill(const LkRoiSector *sectors, const LkRoiFlat *flats, const uint32_t *tile_begin, int n_sectors,
-                              uint32_t n_tiles, const uint32_t *tiles, float2 *xy, uint32_t *off, hipStream_t st, int rows = 0);
-hipError_t lk_launch_stale_iterations(lk_result *r, int n, const int *carry_in, int *carry_out, hipStream_t st);
-hipError_t lk_launch_append_sector(const LkAppendArgs &a, hipStream_t st);
-hipError_t lk_launch_mean_center(const float2 *xy, const uint32_t *off, int n_sectors, float2 *center, hipStream_t st);
-size_t lk_mean_center_int_scratch_bytes(uint32_t n_samples, int n_sectors);
-hipError_t lk_launch_mean_center_int(const float2 *xy, const uint32_t *off, uint32_t n_samples, int n_sectors, void *scratch,
-                                     float2 *center, hipStream_t st);
 
 namespace {
 

@@ -44,6 +44,7 @@
 
 #include "../../include/lk_group.h"
 #include "lk_internal.hpp"
+#include "lk_launch.hpp"
 
 namespace {
 

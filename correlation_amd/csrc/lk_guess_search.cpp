@@ -8,9 +8,8 @@
 #include "../../include/lk_tracker.h"
 #include "lk_device.hpp"
 #include "lk_internal.hpp"
+#include "lk_launch.hpp"
 
-hipError_t lk_launch_guess_search(const LkGuessSearchArgs &a, hipStream_t st);
-int lk_guess_search_window_budget(int radius, int has_v);
 // lk_tracker.cpp: the search the sequence functions run on frame 0 (nullptr: none)
 extern "C" int lk_tracker_internal_set_search(lk_tracker *t, const lk_guess_search *cfg,
                                    int (*search)(lk_engine *, const lk_guess_search *, float *));

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "lk_device.hpp"
+#include "lk_launch.hpp"
 
 static_assert(offsetof(lk_guess_match, score) == 32 && sizeof(lk_guess_match) == 48, "lk_guess_match layout");
 

@@ -9,13 +9,9 @@
 // records unresolved (see lk_stale_iterations_kernel); the group resolves them over the gathered records in
 // GLOBAL sector order with one group-level carry, so that a shard whose first sectors fail their very
 // first evaluation reports what the last sector of the shard before it left behind - as the serial
-// reference does (correlation_class.cpp:413-419, :870).
+// reference does (correlation_class.cpp:413-419, :870; lk_launch.hpp: lk_launch_stale_iterations_blocks / _window).
 int lk_internal_set_defer_stale(lk_engine *e, int on);
 int lk_internal_reference_order(const lk_engine *e);
-
-// the same resolution over n_ranks padded blocks of `cap` records holding the shards [r*S/G, (r+1)*S/G)
-hipError_t lk_launch_stale_iterations_blocks(lk_result *all, int n_sectors, int n_ranks, int cap, const int *carry_in,
-                                             int *carry_out, hipStream_t st);
 
 // Frames that reach a member through a collective on the group's communication stream: the engine's fill (upload copy +
 // pyramid, on the engine's stream or - LK_IMG_NXT, ring slots - its next-frame stream) waits for `after` on the device
@@ -28,10 +24,6 @@ int lk_internal_sequence_set_frame_device_after(lk_engine *e, int slot, const vo
 // 1: a solve of this engine launches teams of workgroups that wait for each other (collectives stay in stream order then)
 int lk_internal_team_launches(const lk_engine *e);
 int lk_internal_sector_count(const lk_engine *e);
-// reference-order mode, a window of `frames` frames gathered as n_ranks blocks of [frames][cap] records: the stale
-// iteration counts resolved in the order the reference solves - frame by frame, sector by sector
-hipError_t lk_launch_stale_iterations_window(lk_result *all, int n_sectors, int n_ranks, int cap, int frames, const int *carry_in,
-                                             int *carry_out, hipStream_t st);
 
 // Automatic initial guess (lk_guess_search.cpp): what the search needs of the engine.  The accessor finishes pending
 // rebuilds of the lists, makes the engine's stream wait for a ring slot's pyramid, and sizes the match buffer [S].

@@ -42,7 +42,7 @@
 // (the bicubic coefficient build, see bicubic_sample) or where only the summation order
 // already differs from the reference (the A/b/chi accumulators).
 #include "lk_device.hpp"
-#include "lk_internal.hpp"
+#include "lk_launch.hpp"
 
 #include <float.h>
 #include <stdlib.h>

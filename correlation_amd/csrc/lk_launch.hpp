@@ -1,0 +1,76 @@
+// lk_launch.hpp - the kernel launchers: what the host code (lk_engine.cpp, lk_group.cpp, lk_guess_search.cpp) calls
+// and the .hip files define.  Every file on either side includes this header, so each declaration meets its definition
+// in front of a compiler.  Same shared library; nothing here is part of include/*.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "lk_device.hpp"
+
+// ---- lk_kernels.hip: the forward solve and the known-answer entry points
+hipError_t lk_launch_solve(const LkSolveArgs &a, int model, int interp, int group, hipStream_t st);
+// flavour: 0 fast (root-free Cholesky; a bad pivot raises the gate of the SAFE pass behind it), 1 SAFE (the QR inside the
+// kernel), 2 reference order (a.reference_order = T)
+hipError_t lk_launch_solve_seq(const LkSolveArgs &a, int model, int interp, int group, int flavour, hipStream_t st);
+hipError_t lk_launch_eval(const LkEvalArgs &a, int model, int interp, int group, hipStream_t st);
+hipError_t lk_launch_solve_only(int n, const float *d_in, float *d_out, hipStream_t st);
+hipError_t lk_launch_step_compare(int n, const float *d_in, float *d_out, hipStream_t st);
+hipError_t lk_launch_reduce_compare(int n, int wide, const float *d_in, float *d_out, hipStream_t st);
+hipError_t lk_launch_sample(int interp, const uint8_t *def, int rows, int cols, const float2 *pts, int n,
+                            float4 *out, hipStream_t st);
+
+// ---- lk_backward.hip: the inverse-compositional solve
+hipError_t lk_launch_backward(const LkBackwardArgs &a, int model, int interp, int group, hipStream_t st);
+hipError_t lk_launch_backward_eval(const LkBackwardEvalArgs &a, int model, int interp, int group, hipStream_t st);
+
+// ---- lk_guess_search.hip: the integer-pixel ZNCC search
+hipError_t lk_launch_guess_search(const LkGuessSearchArgs &a, hipStream_t st);
+// LDS left for the staged window: 64 KB per workgroup minus the scores, the template chunk and the reduction arrays
+int lk_guess_search_window_budget(int radius, int has_v);
+
+// ---- lk_kernels.hip: pyramids and the level table
+hipError_t lk_launch_pyramid(const uint8_t *src, int srows, int scols, uint8_t *dst, hipStream_t st);
+hipError_t lk_launch_set_views(const LkLevelView *h_views, LkLevelView *d_views, hipStream_t st);
+// copy (src -> l0, skipped when src == l0) + levels 1 and 2 in one launch
+hipError_t lk_launch_pyramid2(int n_images, const uint8_t *const *src, const int *step, int rows, int cols,
+                              uint8_t *const *l0, uint8_t *const *l1, uint8_t *const *l2, hipStream_t st);
+
+// ---- lk_kernels.hip: sample lists on the device
+hipError_t lk_launch_warp_points(const float2 *xy, int n, float cx, float cy, int model, const float *d_p,
+                                 float2 *out, hipStream_t st);
+hipError_t lk_launch_rewarp(const LkRewarpArgs &a, int model, hipStream_t st);
+int lk_decimate_tiles(uint32_t n_max);
+// One level of pyramid_class.cpp:289-323 for all sectors: xy_prev[*n_prev] (at most n_max) ->
+// xy_out, off_prev[S+1] -> off_out[S+1], *n_out = samples kept.  pos: n_max words,
+// tiles: lk_decimate_tiles(n_max) + 1 words.
+hipError_t lk_launch_decimate(const float2 *xy_prev, const uint32_t *off_prev, const uint32_t *n_prev, uint32_t n_max,
+                              int level_delta, int n_sectors, uint32_t *pos, uint32_t *tiles, float2 *xy_out,
+                              uint32_t *off_out, uint32_t *n_out, hipStream_t st);
+// pass 1: per-tile counts -> exclusive prefix in place (tiles[n_tiles] = total, also *n_out)
+hipError_t lk_launch_roi_count(const LkRoiSector *sectors, const LkRoiFlat *flats, const uint32_t *tile_begin, int n_sectors,
+                               uint32_t n_tiles, uint32_t *tiles, uint32_t *n_out, hipStream_t st, int rows = 0);
+// pass 2: the samples and the per-sector offsets
+hipError_t lk_launch_roi_fill(const LkRoiSector *sectors, const LkRoiFlat *flats, const uint32_t *tile_begin, int n_sectors,
+                              uint32_t n_tiles, const uint32_t *tiles, float2 *xy, uint32_t *off, hipStream_t st, int rows = 0);
+hipError_t lk_launch_mean_center(const float2 *xy, const uint32_t *off, int n_sectors, float2 *center, hipStream_t st);
+// integer, non-negative sample lists (device-masked annular / blob sectors): the same mean, evaluated in parallel
+// scratch: lk_mean_center_int_scratch_bytes(total, n_sectors) bytes (chunk table, exact chunk sums, chunk maps)
+size_t lk_mean_center_int_scratch_bytes(uint32_t n_samples, int n_sectors);
+hipError_t lk_launch_mean_center_int(const float2 *xy, const uint32_t *off, uint32_t n_samples, int n_sectors, void *scratch,
+                                     float2 *center, hipStream_t st);
+
+// ---- lk_kernels.hip: per-sector state
+hipError_t lk_launch_guess(const float2 *center, const float *last_p, float *prev_p, float *guess,
+                           const float *global_guess, float gcx, float gcy, int n_sectors, int model,
+                           int frame, int constant_velocity, hipStream_t st);
+hipError_t lk_launch_append_sector(const LkAppendArgs &a, hipStream_t st);
+// reference-order mode: the stale iteration counts of n records resolved in sector order (lk_stale_iterations_kernel)
+hipError_t lk_launch_stale_iterations(lk_result *r, int n, const int *carry_in, int *carry_out, hipStream_t st);
+// the same resolution over n_ranks padded blocks of `cap` records holding the shards [r*S/G, (r+1)*S/G)
+hipError_t lk_launch_stale_iterations_blocks(lk_result *all, int n_sectors, int n_ranks, int cap, const int *carry_in,
+                                             int *carry_out, hipStream_t st);
+// reference-order mode, a window of `frames` frames gathered as n_ranks blocks of [frames][cap] records: the stale
+// iteration counts resolved in the order the reference solves - frame by frame, sector by sector
+hipError_t lk_launch_stale_iterations_window(lk_result *all, int n_sectors, int n_ranks, int cap, int frames, const int *carry_in,
+                                             int *carry_out, hipStream_t st);
