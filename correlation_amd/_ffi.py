@@ -63,6 +63,19 @@ GUESS_MATCH_DTYPE = np.dtype({"names": [f for f, _ in LkGuessMatch._fields_],
                               "offsets": [getattr(LkGuessMatch, f).offset for f, _ in LkGuessMatch._fields_],
                               "itemsize": C.sizeof(LkGuessMatch)})
 
+# recovery pass (include/lk_engine.h: lk_reseed_failed)
+RESEED_GOOD, RESEED_RECOVERED, RESEED_NO_NEIGHBOUR, RESEED_NOT_IMPROVED, RESEED_PLANNED = range(5)
+
+
+class LkReseedConfig(C.Structure):
+    _fields_ = [("chi_max", C.c_float), ("radius", C.c_float), ("min_neighbours", C.c_int), ("max_rounds", C.c_int)]
+
+
+# lk_reseed_info as a numpy record
+RESEED_INFO_DTYPE = np.dtype([("status", np.int32), ("round", np.int32), ("neighbours", np.int32),
+                              ("chi_before", np.float32)])
+assert RESEED_INFO_DTYPE.itemsize == 16
+
 # layout of lk_result == CorrelationResult (domains.hpp:110-118), 48 bytes
 RESULT_DTYPE = np.dtype([("p", np.float32, (6,)), ("chi", np.float32),
                          ("n_points", np.int32), ("iterations", np.int32),
@@ -136,6 +149,9 @@ SYMBOLS = {
     "lk_get_guesses": (C.c_int, [_P, _F]),
     "lk_search_guesses": (C.c_int, [_P, C.POINTER(LkGuessSearch), _F]),
     "lk_get_guess_search_info": (C.c_int, [_P, _P]),
+    "lk_reseed_failed": (C.c_int, [_P, C.POINTER(LkReseedConfig), _P, _I]),
+    "lk_get_reseed_info": (C.c_int, [_P, _P]),
+    "lk_reseed_plan": (C.c_int, [_P, C.POINTER(LkReseedConfig), _P, _F, _P]),
     "lk_evaluate": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_evaluate_backward": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_compose_inverse": (C.c_int, [C.c_int, _F, _F, _F]),

@@ -235,3 +235,54 @@ struct LkBackwardEvalArgs { // lk_evaluate_backward: template pass + one evaluat
 constexpr int kLkBwSmall = 512;   // level-0 samples up to which a 16-lane row owns a sector
 constexpr int kLkBwMedium = 8192; // ... a wavefront; above: a 512-thread workgroup
 __host__ __device__ inline int lk_bw_group(int n0) { return n0 <= kLkBwSmall ? 16 : n0 <= kLkBwMedium ? 64 : 512; }
+
+// Recovery of failed sectors (lk_reseed.hip, include/lk_engine.h: lk_reseed_failed): the uniform cell grid over the sector
+// centres and the per-sector words of one call.
+struct LkReseedGrid {
+  double x0, y0, cell; // origin (the centres' minimum) and cell size (>= radius)
+  int nx, ny;          // cells; cell index = iy * nx + ix, so the cells ix - 1 .. ix + 1 of a row are neighbours in memory
+  const uint32_t *start;   // [nx * ny + 1] first member of each cell
+  const uint32_t *members; // [S] sector indices, ascending within a cell
+  const uint32_t *cell_of; // [S]
+};
+struct LkReseedPlanArgs {
+  LkReseedGrid grid;
+  const float2 *center;    // [S]
+  const lk_result *rec;    // [S] the records the neighbours' parameters are read from
+  const uint8_t *good;     // [S]
+  const int32_t *tried;    // [S] good neighbours behind the last guess that was tried (0: none)
+  float *guess;            // [S][6] out, for the sectors to retry
+  int32_t *nbrs;           // [S] out: good neighbours found (failed sectors)
+  uint8_t *retry;          // [S] out: 1 = solve this sector in this round
+  lk_reseed_info *plan_info; // lk_reseed_plan: status / neighbours of every sector (else null)
+  int n_sectors, model, min_neighbours;
+  double radius;
+};
+struct LkReseedRange { // one class's range of an order table: src[begin .. end) -> the flagged ones to dst[begin ..], in order
+  const uint32_t *src;
+  uint32_t *dst;
+  int begin, end;
+};
+constexpr int kLkReseedRanges = 9; // six size classes + the backward mode's three lane-group ranges
+struct LkReseedCompactArgs {
+  LkReseedRange range[kLkReseedRanges];
+  const uint8_t *retry; // [S]
+  uint32_t *count;      // [kLkReseedRanges]
+};
+struct LkReseedMergeArgs {
+  const uint8_t *retry;      // [S] the sectors this round solved
+  uint8_t *good;             // [S]
+  int32_t *tried;            // [S]
+  const int32_t *nbrs;       // [S]
+  const lk_result *fresh;    // [S] the retry's records
+  lk_result *rec;            // [S] the engine-held records
+  float *last_p, *last_eval_p;            // [S][6] as the retry left them; restored from the copies for a rejected sector
+  const float *keep_last_p, *keep_last_eval_p;
+  uint32_t *stats;           // [S][4] likewise
+  const uint32_t *keep_stats;
+  lk_reseed_info *info;      // [S]
+  unsigned long long *totals; // [6]: retry solves, their four counters summed, sectors recovered
+  int n_sectors, n_params, round;
+  float chi_max;
+};
+constexpr int kLkReseedGroup = 16; // lanes per failed sector of the planning kernel

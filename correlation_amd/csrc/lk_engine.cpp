@@ -294,6 +294,8 @@ struct lk_engine {
   bool results_pending = false;
   bool stats_valid = false;
   lk_stats stats{};
+  int records_S = 0;        // sectors the engine-held records of a batch solve cover (0: no solve since the commit)
+  void *reseed = nullptr;   // lk_reseed.cpp's buffers (lk_reseed_failed / lk_reseed_plan), released by lk_destroy
 
   int fail(int code, const std::string &what) {
     err = what;
@@ -358,6 +360,8 @@ void lk_destroy(lk_engine *e) {
     return;
   (void)hipSetDevice(e->cfg.device);
   (void)hipDeviceSynchronize();
+  lk_internal_reseed_release(e->reseed);
+  e->reseed = nullptr;
   for (auto &im : e->img)
     for (auto &p : im.lvl)
       if (p)
@@ -1564,6 +1568,8 @@ static int commit_impl(lk_engine *e, bool keep_state) {
     e->eval_cap = std::atoi(f);
   HIPCHK(e->d_scratch.ensure(64));
   e->S = S;
+  if (!keep_state)
+    e->records_S = 0;
   e->committed = true;
   e->lv_dirty = true;
   e->stats_valid = false;
@@ -2458,8 +2464,9 @@ static LkBackwardArgs bw_args(lk_engine *e, const float *d_guess, lk_result *d_r
   return b;
 }
 
-// every sector of the domain with the backward update: one launch per lane group, on the engine's stream
-static int launch_all_backward(lk_engine *e, const float *d_guess, lk_result *d_result) {
+// the sectors of `set` (nullptr: every sector of the domain - the engine's own table, bw_begin differences) with the
+// backward update: one launch per lane group, on the engine's stream
+static int launch_all_backward(lk_engine *e, const float *d_guess, lk_result *d_result, const LkSectorSet *set = nullptr) {
   if (int rc = bw_tables(e))
     return rc;
   Range range_("lk:solve backward");
@@ -2467,8 +2474,8 @@ static int launch_all_backward(lk_engine *e, const float *d_guess, lk_result *d_
     HIPCHK(hipEventRecord(e->ev_s0, e->stream));
   LkBackwardArgs b = bw_args(e, d_guess, d_result);
   for (int g = 0; g < 3; ++g) {
-    b.order = e->d_bw_order.p + e->bw_begin[g];
-    b.n_sectors = e->bw_begin[g + 1] - e->bw_begin[g];
+    b.order = (set ? set->bw_order : e->d_bw_order.p) + e->bw_begin[g];
+    b.n_sectors = set ? set->bw_count[g] : e->bw_begin[g + 1] - e->bw_begin[g];
     if (b.n_sectors > 0)
       HIPCHK(lk_launch_backward(b, e->cfg.fitting_model, e->cfg.interpolation, kBwGroups[g], e->stream));
   }
@@ -2482,16 +2489,25 @@ static int launch_all_backward(lk_engine *e, const float *d_guess, lk_result *d_
   return LK_ERROR_NONE;
 }
 
-static int launch_all(lk_engine *e, const float *d_guess, lk_result *d_result) {
+// `set`: the sectors to solve - an order table with the layout of d_order (class c's sectors at the front of class c's own
+// range, so that every per-class offset derived from class_begin[c] stays valid) and per-class counts.  nullptr: the
+// engine's own table and the class_begin differences, i.e. every sector of the domain.
+static int launch_all(lk_engine *e, const float *d_guess, lk_result *d_result, const LkSectorSet *set = nullptr) {
   if (e->classes_dirty) { // sectors were appended since the last analysis of the whole domain
     HIPCHK(hipStreamSynchronize(e->stream)); // (earlier launches may still read the order table)
     int rc = classify_sectors(e);
     if (rc)
       return rc;
   }
+  if (!set && d_result == e->d_result.p)
+    e->records_S = e->S;
   if (e->update == LK_UPDATE_BACKWARD)
-    return launch_all_backward(e, d_guess, d_result);
+    return launch_all_backward(e, d_guess, d_result, set);
   e->stats_update = LK_UPDATE_FORWARD;
+  const uint32_t *order = set ? set->order : e->d_order.p;
+  int count[kNumClasses];
+  for (int c = 0; c < kNumClasses; ++c)
+    count[c] = set ? set->count[c] : e->class_begin[c + 1] - e->class_begin[c];
   Range range_("lk:solve");
   if (e->timing)
     HIPCHK(hipEventRecord(e->ev_s0, e->stream));
@@ -2502,14 +2518,14 @@ static int launch_all(lk_engine *e, const float *d_guess, lk_result *d_result) {
   static const bool overlap = [] { const char *f = std::getenv("LK_CLASS_STREAMS"); return f ? std::atoi(f) != 0 : true; }();
   int n_classes = 0, n_launched = 0;
   for (int c = 0; c < kNumClasses; ++c)
-    n_classes += e->class_begin[c + 1] > e->class_begin[c];
+    n_classes += count[c] > 0;
   if (n_classes > 1 && overlap) { // guesses, views and images are ready at this point of the engine's stream
     if (!e->ev_fork)
       HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
     HIPCHK(hipEventRecord(e->ev_fork, e->stream));
   }
   for (int c = 0; c < kNumClasses; ++c) {
-    int n = e->class_begin[c + 1] - e->class_begin[c];
+    int n = count[c];
     if (n <= 0)
       continue;
     hipStream_t st = e->stream;
@@ -2522,7 +2538,7 @@ static int launch_all(lk_engine *e, const float *d_guess, lk_result *d_result) {
       HIPCHK(hipStreamWaitEvent(st, e->ev_fork, 0));
     }
     LkSolveArgs a = base_args(e, d_guess, d_result);
-    a.order = e->d_order.p + e->class_begin[c];
+    a.order = order + e->class_begin[c];
     a.n_sectors = n;
     a.queue = e->d_queue.p + 8 * c;
     a.safe = safe_flavour(e) ? 1 : 0;
@@ -2794,6 +2810,80 @@ int lk_internal_guess_search_view(lk_engine *e, int level, int def_slot, LkGuess
   v->d_match = e->d_gs_match.p;
   return LK_ERROR_NONE;
 }
+
+int lk_internal_reseed_view(lk_engine *e, int need_solve, const char *who, LkReseedView *v) {
+  const std::string w(who);
+  if (!e->committed || e->S <= 0)
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": no committed sectors (call lk_commit_sectors)");
+  if (e->reference_order > 0)
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": reference-order mode is on - its records are the CPU engine's, which has no such pass");
+  if (e->results_pending)
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": the outstanding solve has not been waited for (lk_wait_results)");
+  if (e->seq.outstanding)
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": a sequence window is outstanding (lk_wait_sequence)");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  if (need_solve) {
+    if (e->records_S != e->S)
+      return e->fail(LK_ERROR_BAD_DOMAIN, w + ": no solve of the committed sectors yet (lk_correlate_all*)");
+    if (int rc = refresh_level_views(e))
+      return rc;
+  } else if (e->recommit_pending) { // lk_update_sector moved lists: rebuild them (and the centres) as the next solve would
+    e->recommit_pending = false;
+    if (int rc = commit_impl(e, true))
+      return rc;
+  }
+  if (e->classes_dirty) { // (as launch_all does)
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (int rc = classify_sectors(e))
+      return rc;
+  }
+  v->stream = e->stream;
+  v->S = e->S;
+  v->model = e->cfg.fitting_model;
+  v->backward = e->update == LK_UPDATE_BACKWARD ? 1 : 0;
+  v->center = e->d_center.p;
+  v->result = e->d_result.p;
+  v->last_p = e->d_last_p.p;
+  v->last_eval_p = e->d_last_eval_p.p;
+  v->stats = e->d_stats.p;
+  v->order = e->d_order.p;
+  for (int c = 0; c <= kNumClasses; ++c)
+    v->class_begin[c] = e->class_begin[c];
+  v->bw_order = nullptr;
+  for (int g = 0; g < 4; ++g)
+    v->bw_begin[g] = 0;
+  if (v->backward && need_solve) {
+    if (int rc = bw_tables(e))
+      return rc;
+    v->bw_order = e->d_bw_order.p;
+    for (int g = 0; g < 4; ++g)
+      v->bw_begin[g] = e->bw_begin[g];
+  }
+  return LK_ERROR_NONE;
+}
+
+int lk_internal_solve_set(lk_engine *e, const LkSectorSet *set, const float *d_guess, lk_result *d_result) {
+  if (int rc = refresh_level_views(e))
+    return rc;
+  return launch_all(e, d_guess, d_result, set);
+}
+
+int lk_internal_reseed_stats(lk_engine *e, const unsigned long long totals[5]) {
+  lk_stats s{};
+  s.sectors = totals[0];
+  s.evaluations = totals[1];
+  s.sample_evaluations = totals[2];
+  s.point_iterations = totals[3];
+  s.ill_conditioned_solves = totals[4];
+  s.algorithmic_bytes = (e->update == LK_UPDATE_BACKWARD ? 40ull : 25ull) * s.sample_evaluations + 196ull * s.evaluations;
+  s.solve_ms = e->stats.solve_ms;
+  s.pyramid_ms = e->stats.pyramid_ms;
+  e->stats = s;
+  e->stats_valid = true;
+  e->stats_frames = 1;
+  return LK_ERROR_NONE;
+}
+void **lk_internal_reseed_slot(lk_engine *e) { return &e->reseed; }
 
 extern "C" {
 

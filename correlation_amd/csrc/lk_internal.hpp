@@ -47,3 +47,37 @@ int lk_internal_fail(lk_engine *e, int code, const char *what);
 int lk_internal_hipfail(lk_engine *e, hipError_t err, const char *where);
 // the sector count the match buffer holds results for (set by lk_search_guesses; 0: none yet)
 int *lk_internal_guess_search_count(lk_engine *e);
+
+// ---- recovery of failed sectors (lk_reseed.cpp) ------------------------------------------------------------------
+// A subset of the committed sectors for one solve, in the layout of the engine's own order tables: the retries of size
+// class c (forward modes) at order[class_begin[c] ..], count[c] of them; of backward lane-group range g at
+// bw_order[bw_begin[g] ..], bw_count[g] of them.  Only the tables of the engine's current update mode are read.
+struct LkSectorSet {
+  const uint32_t *order;
+  int count[6];
+  const uint32_t *bw_order;
+  int bw_count[3];
+};
+// What the recovery pass needs of the engine.  The accessor finishes pending rebuilds of the lists and of the size
+// classes (so that the tables below are the ones the next solve uses); need_solve: the engine must hold the records of a
+// batch solve of the committed sectors.
+struct LkReseedView {
+  hipStream_t stream;
+  int S, model, backward;
+  const float2 *center;     // [S]
+  lk_result *result;        // [S] the engine-held records
+  float *last_p, *last_eval_p; // [S][6]
+  uint32_t *stats;          // [S][4]
+  const uint32_t *order;    // [S] sectors by size class, class c at [class_begin[c], class_begin[c + 1])
+  int class_begin[7];
+  const uint32_t *bw_order; // [S] sectors by backward lane group (backward mode only, else null)
+  int bw_begin[4];
+};
+int lk_internal_reseed_view(lk_engine *e, int need_solve, const char *who, LkReseedView *v);
+// the engine's own solve (launch_all: its current mode, its streams, its launch chain) on the sectors of `set`
+int lk_internal_solve_set(lk_engine *e, const LkSectorSet *set, const float *d_guess, lk_result *d_result);
+// lk_get_stats after the pass: the counters of the retry solves {sectors, evaluations, sample evaluations, point
+// iterations, ill-conditioned solves}
+int lk_internal_reseed_stats(lk_engine *e, const unsigned long long totals[5]);
+void **lk_internal_reseed_slot(lk_engine *e);
+void lk_internal_reseed_release(void *state); // (lk_reseed.cpp; called by lk_destroy)

@@ -74,3 +74,18 @@ hipError_t lk_launch_stale_iterations_blocks(lk_result *all, int n_sectors, int 
 // iteration counts resolved in the order the reference solves - frame by frame, sector by sector
 hipError_t lk_launch_stale_iterations_window(lk_result *all, int n_sectors, int n_ranks, int cap, int frames, const int *carry_in,
                                              int *carry_out, hipStream_t st);
+
+// ---- lk_reseed.hip: the recovery pass around the solve (lk_reseed_failed / lk_reseed_plan)
+// {min x, min y, max x, max y} of the centres
+hipError_t lk_launch_reseed_bbox(const float2 *center, int n_sectors, float *out4, hipStream_t st);
+// good / failed flags, tried = 0, info initialised, *n_failed += failed sectors (zero it first)
+hipError_t lk_launch_reseed_classify(const lk_result *rec, int n_sectors, int n_params, float chi_max, uint8_t *good,
+                                     int32_t *tried, lk_reseed_info *info, uint32_t *n_failed, hipStream_t st);
+// the cell grid: count -> exclusive scan -> scatter -> members ordered by sector index within a cell.
+// cell_of, unordered, members: [S]; start, cursor: [nx * ny + 1]
+hipError_t lk_launch_reseed_grid(const float2 *center, int n_sectors, double x0, double y0, double cell, int nx, int ny,
+                                 uint32_t *cell_of, uint32_t *start, uint32_t *cursor, uint32_t *unordered, uint32_t *members,
+                                 hipStream_t st);
+hipError_t lk_launch_reseed_plan(const LkReseedPlanArgs &a, hipStream_t st);
+hipError_t lk_launch_reseed_compact(const LkReseedCompactArgs &a, hipStream_t st);
+hipError_t lk_launch_reseed_merge(const LkReseedMergeArgs &a, hipStream_t st);

@@ -1,0 +1,347 @@
+// lk_reseed.cpp - host side of the recovery pass (include/lk_engine.h: lk_reseed_failed, lk_get_reseed_info,
+// lk_reseed_plan).  The kernels are lk_reseed.hip; the retries are solved by the engine's own launch code
+// (lk_internal_solve_set -> launch_all) on a sector set this file compacts on the device.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "../../include/lk_engine.h"
+#include "lk_device.hpp"
+#include "lk_internal.hpp"
+#include "lk_launch.hpp"
+
+#define RSCHK(call)                                                                                   \
+  do {                                                                                                \
+    hipError_t _e = (call);                                                                           \
+    if (_e != hipSuccess)                                                                             \
+      return lk_internal_hipfail(e, _e, #call);                                                       \
+  } while (0)
+
+namespace {
+
+struct Buf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  hipError_t ensure(size_t want) {
+    if (p && want <= bytes)
+      return hipSuccess;
+    if (p)
+      (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    const hipError_t err = hipMalloc(&p, std::max<size_t>(want, 16));
+    if (err == hipSuccess)
+      bytes = want;
+    return err;
+  }
+  void release() {
+    if (p)
+      (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  template <class T> T *as() const { return (T *)p; }
+};
+
+// the words that travel to the host once per round (and the bounding box once per call)
+struct Words {
+  uint32_t count[kLkReseedRanges]; // sectors to retry per class / backward lane-group range
+  uint32_t n_failed;               // failed sectors the call found
+  uint32_t pad[2];
+  unsigned long long totals[6];    // retry solves, their four counters, sectors recovered
+  float bbox[4];
+};
+
+struct ReseedState {
+  Buf good, tried, nbrs, retry, guess, info, plan_info, fresh, keep_last_p, keep_last_eval_p, keep_stats, retry_order,
+      bw_retry_order, cell_of, start, cursor, unordered, members, words;
+  Words *h_words = nullptr; // pinned
+  int info_S = 0;           // sectors `info` describes (0: no lk_reseed_failed yet)
+  Buf *all[19] = {&good, &tried, &nbrs, &retry, &guess, &info, &plan_info, &fresh, &keep_last_p, &keep_last_eval_p,
+                  &keep_stats, &retry_order, &bw_retry_order, &cell_of, &start, &cursor, &unordered, &members, &words};
+};
+
+int n_params_of(int model) { return model == LK_FM_U ? 1 : model == LK_FM_UV ? 2 : model == LK_FM_UVQ ? 3 : 6; }
+
+int check_config(lk_engine *e, const lk_reseed_config *cfg, const char *who, bool with_rounds) {
+  const std::string w(who);
+  if (!cfg)
+    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, (w + ": no configuration").c_str());
+  if (!std::isfinite(cfg->radius) || !(cfg->radius > 0.f))
+    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, (w + ": radius must be finite and positive").c_str());
+  if (!std::isfinite(cfg->chi_max))
+    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, (w + ": chi_max must be finite (<= 0: the error code alone decides)").c_str());
+  if (cfg->min_neighbours < 1)
+    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, (w + ": min_neighbours must be at least 1").c_str());
+  if (with_rounds && (cfg->max_rounds < 1 || cfg->max_rounds > 64))
+    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, (w + ": max_rounds must be in 1 .. 64").c_str());
+  return LK_ERROR_NONE;
+}
+
+int get_state(lk_engine *e, ReseedState **out) {
+  void **slot = lk_internal_reseed_slot(e);
+  if (!*slot) {
+    ReseedState *st = new ReseedState();
+    const hipError_t err = hipHostMalloc((void **)&st->h_words, sizeof(Words), hipHostMallocDefault);
+    if (err != hipSuccess) {
+      delete st;
+      return lk_internal_hipfail(e, err, "hipHostMalloc (lk_reseed)");
+    }
+    *slot = st;
+  }
+  *out = (ReseedState *)*slot;
+  return LK_ERROR_NONE;
+}
+
+int ensure_common(lk_engine *e, ReseedState *st, int S) {
+  const size_t n = (size_t)S;
+  RSCHK(st->good.ensure(n));
+  RSCHK(st->tried.ensure(n * sizeof(int32_t)));
+  RSCHK(st->nbrs.ensure(n * sizeof(int32_t)));
+  RSCHK(st->retry.ensure(n));
+  RSCHK(st->guess.ensure(n * 6 * sizeof(float)));
+  RSCHK(st->fresh.ensure(n * sizeof(lk_result)));
+  RSCHK(st->cell_of.ensure(n * sizeof(uint32_t)));
+  RSCHK(st->unordered.ensure(n * sizeof(uint32_t)));
+  RSCHK(st->members.ensure(n * sizeof(uint32_t)));
+  RSCHK(st->words.ensure(sizeof(Words)));
+  return LK_ERROR_NONE;
+}
+
+// The cell grid over the centres, cell size = radius (a hair more, so that two centres within `radius` of each other
+// are at most one cell apart whatever the rounding of the quotients).  A radius that is tiny against the domain would
+// ask for more cells than there are sectors to put into them: the cells then grow (a larger cell only means more
+// candidates per cell) until the table is a few words per sector.
+int build_grid(lk_engine *e, ReseedState *st, const LkReseedView &v, float radius, const float bbox[4], LkReseedGrid *g) {
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(bbox[i]))
+      return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_reseed: a sector centre is not finite");
+  const double w = (double)bbox[2] - (double)bbox[0], h = (double)bbox[3] - (double)bbox[1];
+  const double limit = 4.0 * (double)v.S + 1024.0;
+  double cell = (double)radius * (1.0 + 1e-6);
+  double nx = std::floor(w / cell) + 1.0, ny = std::floor(h / cell) + 1.0;
+  while (nx * ny > limit) {
+    cell *= std::max(1.01, std::sqrt(nx * ny / limit));
+    nx = std::floor(w / cell) + 1.0;
+    ny = std::floor(h / cell) + 1.0;
+  }
+  g->x0 = (double)bbox[0];
+  g->y0 = (double)bbox[1];
+  g->cell = cell;
+  g->nx = (int)nx;
+  g->ny = (int)ny;
+  const size_t n_cells = (size_t)g->nx * (size_t)g->ny;
+  RSCHK(st->start.ensure((n_cells + 1) * sizeof(uint32_t)));
+  RSCHK(st->cursor.ensure((n_cells + 1) * sizeof(uint32_t)));
+  RSCHK(lk_launch_reseed_grid(v.center, v.S, g->x0, g->y0, g->cell, g->nx, g->ny, st->cell_of.as<uint32_t>(),
+                              st->start.as<uint32_t>(), st->cursor.as<uint32_t>(), st->unordered.as<uint32_t>(),
+                              st->members.as<uint32_t>(), v.stream));
+  g->start = st->start.as<uint32_t>();
+  g->members = st->members.as<uint32_t>();
+  g->cell_of = st->cell_of.as<uint32_t>();
+  return LK_ERROR_NONE;
+}
+
+int fetch_words(lk_engine *e, ReseedState *st, hipStream_t stream) {
+  RSCHK(hipMemcpyAsync(st->h_words, st->words.p, sizeof(Words), hipMemcpyDeviceToHost, stream));
+  RSCHK(hipStreamSynchronize(stream));
+  return LK_ERROR_NONE;
+}
+
+LkReseedPlanArgs plan_args(ReseedState *st, const LkReseedView &v, const LkReseedGrid &g, const lk_reseed_config *cfg,
+                           const lk_result *rec) {
+  LkReseedPlanArgs a{};
+  a.grid = g;
+  a.center = v.center;
+  a.rec = rec;
+  a.good = st->good.as<uint8_t>();
+  a.tried = st->tried.as<int32_t>();
+  a.guess = st->guess.as<float>();
+  a.nbrs = st->nbrs.as<int32_t>();
+  a.retry = st->retry.as<uint8_t>();
+  a.plan_info = nullptr;
+  a.n_sectors = v.S;
+  a.model = v.model;
+  a.min_neighbours = cfg->min_neighbours;
+  a.radius = (double)cfg->radius;
+  return a;
+}
+
+} // namespace
+
+void lk_internal_reseed_release(void *state) {
+  ReseedState *st = (ReseedState *)state;
+  if (!st)
+    return;
+  for (Buf *b : st->all)
+    b->release();
+  if (st->h_words)
+    (void)hipHostFree(st->h_words);
+  delete st;
+}
+
+extern "C" {
+
+int lk_reseed_failed(lk_engine *e, const lk_reseed_config *cfg, lk_result *out, int *n_recovered) {
+  if (!e)
+    return LK_ERROR_BAD_DOMAIN;
+  if (n_recovered)
+    *n_recovered = 0;
+  if (int rc = check_config(e, cfg, "lk_reseed_failed", true))
+    return rc;
+  LkReseedView v{};
+  if (int rc = lk_internal_reseed_view(e, 1, "lk_reseed_failed", &v))
+    return rc;
+  ReseedState *st = nullptr;
+  if (int rc = get_state(e, &st))
+    return rc;
+  st->info_S = 0;
+  const int S = v.S, P = n_params_of(v.model);
+  const size_t n = (size_t)S;
+  if (int rc = ensure_common(e, st, S))
+    return rc;
+  RSCHK(st->info.ensure(n * sizeof(lk_reseed_info)));
+  RSCHK(st->keep_last_p.ensure(n * 6 * sizeof(float)));
+  RSCHK(st->keep_last_eval_p.ensure(n * 6 * sizeof(float)));
+  RSCHK(st->keep_stats.ensure(n * 4 * sizeof(uint32_t)));
+  RSCHK(st->retry_order.ensure(n * sizeof(uint32_t)));
+  RSCHK(st->bw_retry_order.ensure(n * sizeof(uint32_t)));
+  Words *d_words = st->words.as<Words>();
+
+  // classify, and the centres' bounding box: the one round trip before the rounds
+  RSCHK(hipMemsetAsync(d_words, 0, sizeof(Words), v.stream));
+  RSCHK(lk_launch_reseed_classify(v.result, S, P, cfg->chi_max, st->good.as<uint8_t>(), st->tried.as<int32_t>(),
+                                  st->info.as<lk_reseed_info>(), &d_words->n_failed, v.stream));
+  RSCHK(lk_launch_reseed_bbox(v.center, S, d_words->bbox, v.stream));
+  if (int rc = fetch_words(e, st, v.stream))
+    return rc;
+  st->info_S = S;
+  if (st->h_words->n_failed > 0) {
+    LkReseedGrid grid{};
+    if (int rc = build_grid(e, st, v, cfg->radius, st->h_words->bbox, &grid))
+      return rc;
+    // everything a solve writes per sector besides its record: kept, and put back for a retry that is rejected
+    RSCHK(hipMemcpyAsync(st->keep_last_p.p, v.last_p, n * 6 * sizeof(float), hipMemcpyDeviceToDevice, v.stream));
+    RSCHK(hipMemcpyAsync(st->keep_last_eval_p.p, v.last_eval_p, n * 6 * sizeof(float), hipMemcpyDeviceToDevice, v.stream));
+    RSCHK(hipMemcpyAsync(st->keep_stats.p, v.stats, n * 4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, v.stream));
+
+    LkReseedCompactArgs ca{};
+    ca.retry = st->retry.as<uint8_t>();
+    ca.count = d_words->count;
+    if (v.backward) {
+      for (int g = 0; g < 3; ++g)
+        ca.range[6 + g] = LkReseedRange{v.bw_order, st->bw_retry_order.as<uint32_t>(), v.bw_begin[g], v.bw_begin[g + 1]};
+    } else {
+      for (int c = 0; c < 6; ++c)
+        ca.range[c] = LkReseedRange{v.order, st->retry_order.as<uint32_t>(), v.class_begin[c], v.class_begin[c + 1]};
+    }
+    LkReseedMergeArgs ma{};
+    ma.retry = st->retry.as<uint8_t>();
+    ma.good = st->good.as<uint8_t>();
+    ma.tried = st->tried.as<int32_t>();
+    ma.nbrs = st->nbrs.as<int32_t>();
+    ma.fresh = st->fresh.as<lk_result>();
+    ma.rec = v.result;
+    ma.last_p = v.last_p;
+    ma.last_eval_p = v.last_eval_p;
+    ma.keep_last_p = st->keep_last_p.as<float>();
+    ma.keep_last_eval_p = st->keep_last_eval_p.as<float>();
+    ma.stats = v.stats;
+    ma.keep_stats = st->keep_stats.as<uint32_t>();
+    ma.info = st->info.as<lk_reseed_info>();
+    ma.totals = d_words->totals;
+    ma.n_sectors = S;
+    ma.n_params = P;
+    ma.chi_max = cfg->chi_max;
+    const LkReseedPlanArgs pa = plan_args(st, v, grid, cfg, v.result);
+
+    for (int round = 0; round < cfg->max_rounds; ++round) {
+      RSCHK(lk_launch_reseed_plan(pa, v.stream));
+      RSCHK(lk_launch_reseed_compact(ca, v.stream));
+      if (int rc = fetch_words(e, st, v.stream)) // the round's one trip to the host: the counts that size the launches
+        return rc;
+      LkSectorSet set{};
+      set.order = st->retry_order.as<uint32_t>();
+      set.bw_order = st->bw_retry_order.as<uint32_t>();
+      long long total = 0;
+      for (int c = 0; c < 6; ++c)
+        total += set.count[c] = v.backward ? 0 : (int)st->h_words->count[c];
+      for (int g = 0; g < 3; ++g)
+        total += set.bw_count[g] = v.backward ? (int)st->h_words->count[6 + g] : 0;
+      if (total == 0) // nothing new to try: the last round recovered nothing that is anybody's neighbour
+        break;
+      if (int rc = lk_internal_solve_set(e, &set, st->guess.as<float>(), st->fresh.as<lk_result>()))
+        return rc;
+      ma.round = round;
+      RSCHK(lk_launch_reseed_merge(ma, v.stream));
+    }
+    if (int rc = fetch_words(e, st, v.stream))
+      return rc;
+  }
+  unsigned long long totals[5];
+  for (int i = 0; i < 5; ++i)
+    totals[i] = st->h_words->totals[i];
+  lk_internal_reseed_stats(e, totals);
+  if (n_recovered)
+    *n_recovered = (int)st->h_words->totals[5];
+  if (out) {
+    RSCHK(hipMemcpyAsync(out, v.result, n * sizeof(lk_result), hipMemcpyDeviceToHost, v.stream));
+    RSCHK(hipStreamSynchronize(v.stream));
+  }
+  return LK_ERROR_NONE;
+}
+
+int lk_get_reseed_info(lk_engine *e, lk_reseed_info *out) {
+  if (!e)
+    return LK_ERROR_BAD_DOMAIN;
+  ReseedState *st = (ReseedState *)*lk_internal_reseed_slot(e);
+  if (!out || !st || st->info_S <= 0 || st->info_S != lk_internal_sector_count(e))
+    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_get_reseed_info: no lk_reseed_failed of the committed sectors");
+  RSCHK(hipMemcpy(out, st->info.p, (size_t)st->info_S * sizeof(lk_reseed_info), hipMemcpyDeviceToHost));
+  return LK_ERROR_NONE;
+}
+
+int lk_reseed_plan(lk_engine *e, const lk_reseed_config *cfg, const lk_result *records, float *guesses_out,
+                   lk_reseed_info *info_out) {
+  if (!e)
+    return LK_ERROR_BAD_DOMAIN;
+  if (int rc = check_config(e, cfg, "lk_reseed_plan", false))
+    return rc;
+  if (!records || !guesses_out || !info_out)
+    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_reseed_plan: null argument");
+  LkReseedView v{};
+  if (int rc = lk_internal_reseed_view(e, 0, "lk_reseed_plan", &v))
+    return rc;
+  ReseedState *st = nullptr;
+  if (int rc = get_state(e, &st))
+    return rc;
+  const int S = v.S, P = n_params_of(v.model);
+  const size_t n = (size_t)S;
+  if (int rc = ensure_common(e, st, S))
+    return rc;
+  RSCHK(st->plan_info.ensure(n * sizeof(lk_reseed_info)));
+  Words *d_words = st->words.as<Words>();
+  RSCHK(hipMemsetAsync(d_words, 0, sizeof(Words), v.stream));
+  RSCHK(hipMemcpyAsync(st->fresh.p, records, n * sizeof(lk_result), hipMemcpyHostToDevice, v.stream));
+  RSCHK(hipMemsetAsync(st->guess.p, 0, n * 6 * sizeof(float), v.stream));
+  RSCHK(lk_launch_reseed_classify(st->fresh.as<lk_result>(), S, P, cfg->chi_max, st->good.as<uint8_t>(),
+                                  st->tried.as<int32_t>(), st->plan_info.as<lk_reseed_info>(), &d_words->n_failed, v.stream));
+  RSCHK(lk_launch_reseed_bbox(v.center, S, d_words->bbox, v.stream));
+  if (int rc = fetch_words(e, st, v.stream))
+    return rc;
+  LkReseedGrid grid{};
+  if (int rc = build_grid(e, st, v, cfg->radius, st->h_words->bbox, &grid))
+    return rc;
+  LkReseedPlanArgs pa = plan_args(st, v, grid, cfg, st->fresh.as<lk_result>());
+  pa.plan_info = st->plan_info.as<lk_reseed_info>();
+  RSCHK(lk_launch_reseed_plan(pa, v.stream));
+  RSCHK(hipMemcpyAsync(guesses_out, st->guess.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
+  RSCHK(hipMemcpyAsync(info_out, st->plan_info.p, n * sizeof(lk_reseed_info), hipMemcpyDeviceToHost, v.stream));
+  RSCHK(hipStreamSynchronize(v.stream));
+  return LK_ERROR_NONE;
+}
+
+} // extern "C"

@@ -342,6 +342,33 @@ class HipCorrelationEngine:
         self._chk(self.lib.lk_get_guess_search_info(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # ---- recovery pass: failed sectors re-solved from their converged neighbours ---------------
+    def reseed_failed(self, radius, chi_max=0.0, min_neighbours=1, max_rounds=8, want_records=True):
+        """lk_reseed_failed on the records of the last correlate_all: returns (records [S] or None, sectors recovered)."""
+        cfg = _ffi.LkReseedConfig(float(chi_max), float(radius), int(min_neighbours), int(max_rounds))
+        out = np.zeros(self.n_sectors, RESULT_DTYPE) if want_records else None
+        n = C.c_int()
+        self._chk(self.lib.lk_reseed_failed(self._h, C.byref(cfg), out.ctypes.data_as(C.c_void_p) if want_records else None,
+                                            C.byref(n)))
+        return out, n.value
+
+    def reseed_info(self):
+        """What the last reseed_failed did: a RESEED_INFO_DTYPE array [S]."""
+        out = np.zeros(self.n_sectors, _ffi.RESEED_INFO_DTYPE)
+        self._chk(self.lib.lk_get_reseed_info(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def reseed_plan(self, records, radius, chi_max=0.0, min_neighbours=1):
+        """lk_reseed_plan: one round's planning step on the caller's records [S]: (guesses [S][6], info [S]); nothing is
+        solved and no engine state changes."""
+        cfg = _ffi.LkReseedConfig(float(chi_max), float(radius), int(min_neighbours), 1)
+        rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        g = np.zeros((self.n_sectors, 6), np.float32)
+        info = np.zeros(self.n_sectors, _ffi.RESEED_INFO_DTYPE)
+        self._chk(self.lib.lk_reseed_plan(self._h, C.byref(cfg), rec.ctypes.data_as(C.c_void_p), _ffi.fptr(g),
+                                          info.ctypes.data_as(C.c_void_p)))
+        return g, info
+
     # ---- stand-alone pieces -------------------------------------------------------------
     def evaluate(self, sector, level, p):
         pp = np.zeros(6, np.float32)

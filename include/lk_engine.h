@@ -427,6 +427,78 @@ int lk_search_guesses(lk_engine *e, const lk_guess_search *cfg, float *guesses_i
 /* the matches of the last lk_search_guesses, [S] (waits for it) */
 int lk_get_guess_search_info(lk_engine *e, lk_guess_match *out);
 
+/* ---- recovery pass: re-solve failed sectors from their converged neighbours ------------- */
+/* lk_reseed_failed repairs the engine-held records of the last lk_correlate_all* / lk_wait_results after the fact: a sector
+ * that failed is given a guess extrapolated from neighbours that converged and is solved again; what was recovered seeds
+ * the next ring in the next round.  Everything stays on the device between the rounds (csrc/lk_reseed.hip); the host reads
+ * ten small integers per round to size the launches.
+ *   good      a sector is GOOD when its record has LK_ERROR_NONE, finite parameters (the model's P) and finite chi and,
+ *             if chi_max > 0, chi <= chi_max.  Every other sector is FAILED.
+ *   rounds    each round computes a guess for every failed sector that has at least min_neighbours good sectors within
+ *             `radius` (centre to centre, level-0 pixels, distance <= radius, tested in double) and has not been tried with
+ *             that very neighbour set; the sectors that got a guess are solved in ONE batch.  The neighbours are the sectors
+ *             good at the start of the round, so a sector recovered in round r seeds others from round r + 1 on.  The call
+ *             ends after max_rounds, or earlier when a round finds nothing to try (which is what follows a round that
+ *             recovered nothing).
+ *   guess     the plain mean, over the sector's good neighbours, of each neighbour's parameters carried to the sector's
+ *             centre by the rule lk_adjust_initial_guess applies to the global guess (manager_class.cpp:2602-2707), with
+ *             (dx, dy) = c_sector - c_neighbour:
+ *               LK_FM_UVUXUYVXVY  g0 = p0 + dx p2 + dy p3, g1 = p1 + dx p4 + dy p5, g2..g5 = p2..p5
+ *               LK_FM_UVQ         g0 = p0 - dy p2, g1 = p1 + dx p2, g2 = p2
+ *               LK_FM_U / _UV     g = p
+ *             Differences, products and sums are formed in double from the float centres and parameters (no fused
+ *             multiply-add: each product and each sum is rounded to double); the mean sum / count is rounded to float once.
+ *             A float64 restatement reproduces it up to the order of the double sum.  That order is fixed: the neighbours
+ *             are visited cell by cell of a grid of cell size `radius` over the centres (rows iy - 1, iy, iy + 1, each from
+ *             ix - 1 to ix + 1), by ascending sector index within a cell, dealt to 16 lanes in turn and summed by a
+ *             fixed butterfly - the same bits on every run.
+ *   retry     the solve is the engine's own in its current mode (forward default, batch-invariant or backward) through its
+ *             ordinary launch code, on the retried sectors only.  The new record replaces the old one only if it is good
+ *             by the rule above and, if the old record had LK_ERROR_NONE and a finite chi, its chi is lower than the old one.
+ *             Otherwise the sector is LK_RESEED_NOT_IMPROVED and is tried again only if a later round gives it more good
+ *             neighbours.
+ *   kept      for a sector that was not replaced - never tried, tried and rejected, or good - the record, the engine-held
+ *             last parameters (which lk_adjust_initial_guess continues from), lk_get_last_evaluated_parameters and the
+ *             per-sector counters (lk_get_sector_stats) are byte for byte what they were before the call.  For a replaced
+ *             sector they are the retry's.  The engine-held guesses (lk_get_guesses) never change.
+ *   counters  lk_get_stats after the call describes the retry solves, summed over the rounds (sectors = solves, a sector
+ *             tried twice counts twice; all zero when nothing was tried); solve_ms is the last round's solve.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message: no committed sectors; no batch solve of them yet (or one not waited for);
+ *             a bad configuration (radius or chi_max not finite, radius <= 0, min_neighbours < 1, max_rounds outside
+ *             1..64); reference-order mode is on - that mode's records are by definition the CPU engine's, and the CPU
+ *             engine has no such pass.
+ *   scope     one engine, one pair.  Sequence windows (lk_correlate_sequence_async), lk_tracker / lk_sequence_run, lk_group
+ *             and the CudaClass adapter do not call it and are not changed by it. */
+enum {
+  LK_RESEED_GOOD = 0,          /* good when the call began: never touched */
+  LK_RESEED_RECOVERED = 1,     /* a retry was accepted */
+  LK_RESEED_NO_NEIGHBOUR = 2,  /* failed, and never had min_neighbours good neighbours: never tried */
+  LK_RESEED_NOT_IMPROVED = 3,  /* failed, tried, every retry rejected */
+  LK_RESEED_PLANNED = 4        /* lk_reseed_plan only: failed, and guesses_out holds a guess for it */
+};
+typedef struct lk_reseed_config {
+  float chi_max;       /* a record with error_none and chi > chi_max counts as failed; <= 0: the error code alone decides */
+  float radius;        /* neighbours of a sector: sectors whose centre lies within this many level-0 pixels of its centre */
+  int min_neighbours;  /* >= 1; a failed sector with fewer good neighbours waits for a later round */
+  int max_rounds;      /* 1..64 */
+} lk_reseed_config;
+typedef struct lk_reseed_info {   /* one per sector */
+  int32_t status;      /* LK_RESEED_* */
+  int32_t round;       /* round (from 0) in which the sector was recovered, else -1 */
+  int32_t neighbours;  /* good neighbours behind the last guess that was tried (0 if none was); lk_reseed_plan: good
+                        * neighbours found (failed sectors; 0 for good ones) */
+  float chi_before;    /* chi of the record the call found */
+} lk_reseed_info;
+/* out: [S] the records after the pass, or NULL; n_recovered: sectors replaced, or NULL.  Synchronous. */
+int lk_reseed_failed(lk_engine *e, const lk_reseed_config *cfg, lk_result *out, int *n_recovered);
+/* [S] what the last lk_reseed_failed did (also after a call that found nothing to do) */
+int lk_get_reseed_info(lk_engine *e, lk_reseed_info *out);
+/* the planning step of one round alone, on records the caller supplies [S]: nothing is solved and no engine state
+ * changes (max_rounds is not used).  guesses_out [S][6]: the guess of every LK_RESEED_PLANNED sector, zeros elsewhere;
+ * info_out [S]: status GOOD / NO_NEIGHBOUR / PLANNED, round -1.  Needs committed sectors only. */
+int lk_reseed_plan(lk_engine *e, const lk_reseed_config *cfg, const lk_result *records, float *guesses_out,
+                   lk_reseed_info *info_out);
+
 /* ---- stand-alone pieces (known-answer tests, same kernels as the batch path) ------- */
 /* one evaluation of one sector at one level: raw sums A (6x6 row-major, upper valid),
  * b, chi (unscaled), error flag (apply_model_and_interpolate, correlation_class.cpp:131) */
