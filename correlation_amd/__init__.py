@@ -14,6 +14,8 @@ from ._ffi import (GS_NO_CANDIDATE, GS_OK, GS_TEXTURELESS, GS_TOO_FEW, GS_TOO_LA
                    GUESS_MATCH_DTYPE)
 from ._ffi import (RESEED_GOOD, RESEED_INFO_DTYPE, RESEED_NO_NEIGHBOUR, RESEED_NOT_IMPROVED, RESEED_PLANNED,  # noqa: F401
                    RESEED_RECOVERED)
+from ._ffi import (STRAIN_DEGENERATE, STRAIN_DTYPE, STRAIN_FILLED, STRAIN_GREEN_LAGRANGE, STRAIN_OK, STRAIN_SMALL,  # noqa: F401
+                   STRAIN_TOO_FEW, strain_from_gradient)
 from .engine import HipCorrelationEngine, LkError  # noqa: F401
 from . import speckle  # noqa: F401
 from . import tracker  # noqa: F401

@@ -76,6 +76,21 @@ RESEED_INFO_DTYPE = np.dtype([("status", np.int32), ("round", np.int32), ("neigh
                               ("chi_before", np.float32)])
 assert RESEED_INFO_DTYPE.itemsize == 16
 
+# strain field (include/lk_engine.h: lk_strain_field)
+STRAIN_OK, STRAIN_FILLED, STRAIN_TOO_FEW, STRAIN_DEGENERATE = range(4)
+STRAIN_GREEN_LAGRANGE, STRAIN_SMALL = 0, 1
+
+
+class LkStrainConfig(C.Structure):
+    _fields_ = [("radius", C.c_float), ("chi_max", C.c_float), ("min_neighbours", C.c_int), ("tensor", C.c_int)]
+
+
+# lk_strain as a numpy record
+STRAIN_DTYPE = np.dtype([(k, np.float32) for k in ("u", "v", "ux", "uy", "vx", "vy", "exx", "eyy", "exy", "e1", "e2", "theta",
+                                                   "residual")] +
+                        [("neighbours", np.int32), ("status", np.int32), ("reserved", np.int32)])
+assert STRAIN_DTYPE.itemsize == 64
+
 # layout of lk_result == CorrelationResult (domains.hpp:110-118), 48 bytes
 RESULT_DTYPE = np.dtype([("p", np.float32, (6,)), ("chi", np.float32),
                          ("n_points", np.int32), ("iterations", np.int32),
@@ -152,6 +167,8 @@ SYMBOLS = {
     "lk_reseed_failed": (C.c_int, [_P, C.POINTER(LkReseedConfig), _P, _I]),
     "lk_get_reseed_info": (C.c_int, [_P, _P]),
     "lk_reseed_plan": (C.c_int, [_P, C.POINTER(LkReseedConfig), _P, _F, _P]),
+    "lk_strain_field": (C.c_int, [_P, C.POINTER(LkStrainConfig), _P, _P]),
+    "lk_strain_from_gradient": (C.c_int, [C.c_int, _F, _F]),
     "lk_evaluate": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_evaluate_backward": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_compose_inverse": (C.c_int, [C.c_int, _F, _F, _F]),
@@ -278,4 +295,17 @@ def compose_inverse(model, p, delta):
         return None
     if rc != 0:
         raise ValueError(f"lk_compose_inverse: bad model {model}")
+    return out
+
+
+def strain_from_gradient(tensor, grad4):
+    """lk_strain_from_gradient (host, the kernel's function): {exx, eyy, exy, e1, e2, theta} as float32 [6] of the
+    displacement gradient {ux, uy, vx, vy}."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    g = np.ascontiguousarray(grad4, np.float32).reshape(4)
+    out = np.zeros(6, np.float32)
+    if _compose_lib.lk_strain_from_gradient(int(tensor), fptr(g), fptr(out)) != 0:
+        raise ValueError(f"lk_strain_from_gradient: bad tensor {tensor}")
     return out

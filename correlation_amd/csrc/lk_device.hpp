@@ -286,3 +286,16 @@ struct LkReseedMergeArgs {
   float chi_max;
 };
 constexpr int kLkReseedGroup = 16; // lanes per failed sector of the planning kernel
+
+// Strain field (lk_strain.hip, include/lk_engine.h: lk_strain_field): a windowed plane fit of (u, v) over the good sectors
+// within `radius` of each sector, on the recovery pass's cell grid.
+struct LkStrainArgs {
+  LkReseedGrid grid;
+  const float2 *center;  // [S]
+  const lk_result *rec;  // [S]
+  const uint8_t *good;   // [S] the good rule, evaluated once per call (lk_strain_prep_kernel)
+  const float4 *pack;    // [S] {cx, cy, u, v} of a good sector, cx = NaN for a failed one (the packed variants)
+  lk_strain *out;        // [S]
+  int n_sectors, has_v, min_neighbours, tensor;
+  double radius;
+};

@@ -15,6 +15,7 @@
 // (16 / 32 / 64 lanes, 4 / 8 wavefronts, teams) on one stream, preceded by the one-lane kernel
 // and its finisher when the class has a starved pyramid level.
 #include "lk_compose.hpp"
+#include "lk_strain.hpp"
 #include "lk_device.hpp"
 #include "lk_internal.hpp"
 #include "lk_launch.hpp"
@@ -296,6 +297,7 @@ struct lk_engine {
   lk_stats stats{};
   int records_S = 0;        // sectors the engine-held records of a batch solve cover (0: no solve since the commit)
   void *reseed = nullptr;   // lk_reseed.cpp's buffers (lk_reseed_failed / lk_reseed_plan), released by lk_destroy
+  void *strain = nullptr;   // lk_strain.cpp's buffers (lk_strain_field), released by lk_destroy
 
   int fail(int code, const std::string &what) {
     err = what;
@@ -362,6 +364,8 @@ void lk_destroy(lk_engine *e) {
   (void)hipDeviceSynchronize();
   lk_internal_reseed_release(e->reseed);
   e->reseed = nullptr;
+  lk_internal_strain_release(e->strain);
+  e->strain = nullptr;
   for (auto &im : e->img)
     for (auto &p : im.lvl)
       if (p)
@@ -508,6 +512,12 @@ int lk_compose_inverse(int model, const float *p, const float *delta, float *p_o
   if (model < LK_FM_U || model > LK_FM_UVUXUYVXVY || !p || !delta || !p_out)
     return LK_ERROR_BAD_DOMAIN;
   return lk_compose_inverse_impl(model, p, delta, p_out);
+}
+
+int lk_strain_from_gradient(int tensor, const float *grad4, float *out6) {
+  if (!grad4 || !out6 || lk_strain_tensor_impl(tensor, grad4, out6) != 0)
+    return LK_ERROR_BAD_DOMAIN;
+  return LK_ERROR_NONE;
 }
 
 int lk_set_pairs_in_flight(lk_engine *e, int n) {
@@ -2884,6 +2894,29 @@ int lk_internal_reseed_stats(lk_engine *e, const unsigned long long totals[5]) {
   return LK_ERROR_NONE;
 }
 void **lk_internal_reseed_slot(lk_engine *e) { return &e->reseed; }
+
+int lk_internal_strain_view(lk_engine *e, int need_records, LkStrainView *v) {
+  if (!e->committed || e->S <= 0)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_strain_field: no committed sectors (call lk_commit_sectors)");
+  if (need_records) {
+    if (e->results_pending)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_strain_field: the outstanding solve has not been waited for (lk_wait_results)");
+    if (e->seq.outstanding)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_strain_field: a sequence window is outstanding (lk_wait_sequence)");
+    if (e->records_S != e->S)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_strain_field: no solve of the committed sectors yet (lk_correlate_all*); pass records");
+  }
+  HIPCHK(hipSetDevice(e->cfg.device));
+  // (a rebuild of the lists that is pending - lk_update_sector, a change of mode - stays pending: the call is read-only, and
+  // the centres held until then are the ones the engine-held records were solved at)
+  v->stream = e->stream;
+  v->S = e->S;
+  v->model = e->cfg.fitting_model;
+  v->center = e->d_center.p;
+  v->result = e->d_result.p;
+  return LK_ERROR_NONE;
+}
+void **lk_internal_strain_slot(lk_engine *e) { return &e->strain; }
 
 extern "C" {
 

@@ -81,3 +81,20 @@ int lk_internal_solve_set(lk_engine *e, const LkSectorSet *set, const float *d_g
 int lk_internal_reseed_stats(lk_engine *e, const unsigned long long totals[5]);
 void **lk_internal_reseed_slot(lk_engine *e);
 void lk_internal_reseed_release(void *state); // (lk_reseed.cpp; called by lk_destroy)
+
+// ---- strain field (lk_strain.cpp) ------------------------------------------------------------------------------------
+// What lk_strain_field needs of the engine: read-only.  need_records: the engine must hold the records of a finished
+// batch solve of the committed sectors (allowed in every mode, reference-order included).
+struct LkStrainView {
+  hipStream_t stream;
+  int S, model;
+  const float2 *center;    // [S]
+  const lk_result *result; // [S] the engine-held records
+};
+int lk_internal_strain_view(lk_engine *e, int need_records, LkStrainView *v);
+void **lk_internal_strain_slot(lk_engine *e);
+void lk_internal_strain_release(void *state); // (lk_strain.cpp; called by lk_destroy)
+// Bench hook (scripts/strain_bench.py; exported, not part of include/*.h): of the last lk_strain_field, the HIP-event time
+// of its device part (bounding box with its round trip, grid kernels, prep, fit), the lane group and variant that ran and
+// the expected members of a sector's 3 x 3 cells.  The two events are recorded by every call; the time is read here.
+extern "C" int lk_internal_strain_last(lk_engine *e, float *device_ms, int *group, int *packed, double *members);

@@ -89,3 +89,10 @@ hipError_t lk_launch_reseed_grid(const float2 *center, int n_sectors, double x0,
 hipError_t lk_launch_reseed_plan(const LkReseedPlanArgs &a, hipStream_t st);
 hipError_t lk_launch_reseed_compact(const LkReseedCompactArgs &a, hipStream_t st);
 hipError_t lk_launch_reseed_merge(const LkReseedMergeArgs &a, hipStream_t st);
+
+// ---- lk_strain.hip: the strain field (lk_strain_field)
+// good[s] by the recovery pass's rule and pack[s] = {cx, cy, u, v} (cx = NaN for a failed sector; v = 0 without one)
+hipError_t lk_launch_strain_prep(const lk_result *rec, const float2 *center, int n_sectors, int model, float chi_max,
+                                 uint8_t *good, float4 *pack, hipStream_t st);
+// group: 16 or 64 lanes per sector; packed != 0: the neighbours' data come from a.pack, else from a.center / a.good / a.rec
+hipError_t lk_launch_strain(const LkStrainArgs &a, int group, int packed, hipStream_t st);

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/lk_engine.h"
+#include "lk_cell_grid.hpp"
 #include "lk_device.hpp"
 #include "lk_internal.hpp"
 #include "lk_launch.hpp"
@@ -22,29 +23,7 @@
 
 namespace {
 
-struct Buf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  hipError_t ensure(size_t want) {
-    if (p && want <= bytes)
-      return hipSuccess;
-    if (p)
-      (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    const hipError_t err = hipMalloc(&p, std::max<size_t>(want, 16));
-    if (err == hipSuccess)
-      bytes = want;
-    return err;
-  }
-  void release() {
-    if (p)
-      (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <class T> T *as() const { return (T *)p; }
-};
+using Buf = LkDevBytes;
 
 // the words that travel to the host once per round (and the bounding box once per call)
 struct Words {
@@ -57,11 +36,12 @@ struct Words {
 
 struct ReseedState {
   Buf good, tried, nbrs, retry, guess, info, plan_info, fresh, keep_last_p, keep_last_eval_p, keep_stats, retry_order,
-      bw_retry_order, cell_of, start, cursor, unordered, members, words;
+      bw_retry_order, words;
+  LkCellGridBufs grid;
   Words *h_words = nullptr; // pinned
   int info_S = 0;           // sectors `info` describes (0: no lk_reseed_failed yet)
   Buf *all[19] = {&good, &tried, &nbrs, &retry, &guess, &info, &plan_info, &fresh, &keep_last_p, &keep_last_eval_p,
-                  &keep_stats, &retry_order, &bw_retry_order, &cell_of, &start, &cursor, &unordered, &members, &words};
+                  &keep_stats, &retry_order, &bw_retry_order, &grid.cell_of, &grid.start, &grid.cursor, &grid.unordered, &grid.members, &words};
 };
 
 int n_params_of(int model) { return model == LK_FM_U ? 1 : model == LK_FM_UV ? 2 : model == LK_FM_UVQ ? 3 : 6; }
@@ -104,44 +84,15 @@ int ensure_common(lk_engine *e, ReseedState *st, int S) {
   RSCHK(st->retry.ensure(n));
   RSCHK(st->guess.ensure(n * 6 * sizeof(float)));
   RSCHK(st->fresh.ensure(n * sizeof(lk_result)));
-  RSCHK(st->cell_of.ensure(n * sizeof(uint32_t)));
-  RSCHK(st->unordered.ensure(n * sizeof(uint32_t)));
-  RSCHK(st->members.ensure(n * sizeof(uint32_t)));
   RSCHK(st->words.ensure(sizeof(Words)));
   return LK_ERROR_NONE;
 }
 
-// The cell grid over the centres, cell size = radius (a hair more, so that two centres within `radius` of each other
-// are at most one cell apart whatever the rounding of the quotients).  A radius that is tiny against the domain would
-// ask for more cells than there are sectors to put into them: the cells then grow (a larger cell only means more
-// candidates per cell) until the table is a few words per sector.
+// the cell grid over the centres (lk_cell_grid.hpp: cell size = radius, table capped at a few words per sector)
 int build_grid(lk_engine *e, ReseedState *st, const LkReseedView &v, float radius, const float bbox[4], LkReseedGrid *g) {
-  for (int i = 0; i < 4; ++i)
-    if (!std::isfinite(bbox[i]))
-      return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_reseed: a sector centre is not finite");
-  const double w = (double)bbox[2] - (double)bbox[0], h = (double)bbox[3] - (double)bbox[1];
-  const double limit = 4.0 * (double)v.S + 1024.0;
-  double cell = (double)radius * (1.0 + 1e-6);
-  double nx = std::floor(w / cell) + 1.0, ny = std::floor(h / cell) + 1.0;
-  while (nx * ny > limit) {
-    cell *= std::max(1.01, std::sqrt(nx * ny / limit));
-    nx = std::floor(w / cell) + 1.0;
-    ny = std::floor(h / cell) + 1.0;
-  }
-  g->x0 = (double)bbox[0];
-  g->y0 = (double)bbox[1];
-  g->cell = cell;
-  g->nx = (int)nx;
-  g->ny = (int)ny;
-  const size_t n_cells = (size_t)g->nx * (size_t)g->ny;
-  RSCHK(st->start.ensure((n_cells + 1) * sizeof(uint32_t)));
-  RSCHK(st->cursor.ensure((n_cells + 1) * sizeof(uint32_t)));
-  RSCHK(lk_launch_reseed_grid(v.center, v.S, g->x0, g->y0, g->cell, g->nx, g->ny, st->cell_of.as<uint32_t>(),
-                              st->start.as<uint32_t>(), st->cursor.as<uint32_t>(), st->unordered.as<uint32_t>(),
-                              st->members.as<uint32_t>(), v.stream));
-  g->start = st->start.as<uint32_t>();
-  g->members = st->members.as<uint32_t>();
-  g->cell_of = st->cell_of.as<uint32_t>();
+  if (!lk_cell_grid_bbox_finite(bbox))
+    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_reseed: a sector centre is not finite");
+  RSCHK(lk_cell_grid_build(st->grid, v.center, v.S, radius, bbox, v.stream, g));
   return LK_ERROR_NONE;
 }
 

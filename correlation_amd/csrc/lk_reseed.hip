@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "lk_device.hpp"
+#include "lk_good.hpp"
 #include "lk_launch.hpp"
 
 namespace {
@@ -24,22 +25,6 @@ namespace {
 constexpr int kWave = 64;
 constexpr int kBlock = 256;
 constexpr int kWide = 1024; // the one-workgroup kernels (bounding box, scan, compaction)
-
-__device__ inline bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// include/lk_engine.h, "good": error_none, finite parameters and chi, chi <= chi_max when chi_max > 0
-__device__ inline bool reseed_good(const lk_result &r, int n_params, float chi_max) {
-  if (r.errorCode != LK_ERROR_NONE || !finite_bits(r.chi))
-    return false;
-  for (int i = 0; i < n_params; ++i)
-    if (!finite_bits(r.resultingParameters[i]))
-      return false;
-  return !(chi_max > 0.f) || r.chi <= chi_max;
-}
-
-__device__ inline int n_params_of(int model) {
-  return model == LK_FM_U ? 1 : model == LK_FM_UV ? 2 : model == LK_FM_UVQ ? 3 : 6;
-}
 
 // ---- bounding box of the centres: one workgroup, {min x, min y, max x, max y} ---------------------------------------
 __global__ __launch_bounds__(kWide) void lk_reseed_bbox_kernel(const float2 *center, int n, float *out4) {

@@ -369,6 +369,19 @@ class HipCorrelationEngine:
                                           info.ctypes.data_as(C.c_void_p)))
         return g, info
 
+    # ---- strain field: windowed plane fit of the solved displacements ------------------------------
+    def strain_field(self, radius, chi_max=0.0, min_neighbours=3, tensor=_ffi.STRAIN_GREEN_LAGRANGE, records=None):
+        """lk_strain_field: a STRAIN_DTYPE array [S] from the engine-held records of the last batch solve (after
+        reseed_failed: the repaired ones) or, records given, from those [S]; no engine state changes."""
+        cfg = _ffi.LkStrainConfig(float(radius), float(chi_max), int(min_neighbours), int(tensor))
+        rec = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        out = np.zeros(self.n_sectors, _ffi.STRAIN_DTYPE)
+        self._chk(self.lib.lk_strain_field(self._h, C.byref(cfg), rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
+                                           out.ctypes.data_as(C.c_void_p)))
+        return out
+
     # ---- stand-alone pieces -------------------------------------------------------------
     def evaluate(self, sector, level, p):
         pp = np.zeros(6, np.float32)

@@ -499,6 +499,75 @@ int lk_get_reseed_info(lk_engine *e, lk_reseed_info *out);
 int lk_reseed_plan(lk_engine *e, const lk_reseed_config *cfg, const lk_result *records, float *guesses_out,
                    lk_reseed_info *info_out);
 
+/* ---- strain field: a windowed plane fit of the solved displacements ----------------------- */
+/* lk_strain_field turns one displacement record per sector into one strain record per sector: a pointwise least-squares
+ * plane fit of (u, v) over the good sectors of a strain window, the displacement gradients of that plane, the strain
+ * tensor of the gradients and its principal values (csrc/lk_strain.hip).
+ *   data      of a sector: position = the engine's committed centre c (lk_get_sector_info), not undCenterX/Y of the record;
+ *             displacement u = p[0] and v = p[1]; LK_FM_U has v = 0 everywhere, hence vx = vy = 0.  The per-sector
+ *             gradient parameters of LK_FM_UVUXUYVXVY are not used.
+ *   good      the recovery pass's rule (one shared device function): LK_ERROR_NONE, finite parameters (the model's P),
+ *             finite chi and, if chi_max > 0, chi <= chi_max.
+ *   window    of sector s: every good sector j, s itself included when good, with dx^2 + dy^2 <= r^2, where
+ *             (dx, dy) = c_j - c_s is formed in double from the float centres and r = (double)radius.  Each product and
+ *             each sum is rounded to double (no fused multiply-add).  n = the number of such sectors.
+ *   fit       all in double, in the window's coordinates x = dx, y = dy: the sums Sx, Sy, Sxx, Sxy, Syy, Su, Sxu, Syu,
+ *             Sv, Sxv, Syv; the centred moments Cxx = Sxx - Sx Sx / n, Cxy = Sxy - Sx Sy / n, Cyy = Syy - Sy Sy / n,
+ *             Cxu = Sxu - Sx Su / n, Cyu = Syu - Sy Su / n, Cxv, Cyv alike; D = Cxx Cyy - Cxy Cxy;
+ *               ux = (Cyy Cxu - Cxy Cyu) / D,  uy = (Cxx Cyu - Cxy Cxu) / D,  vx, vy by the same formulas from Cxv, Cyv;
+ *               u = Su / n - ux (Sx / n) - uy (Sy / n)  (the plane at c_s),  v alike.
+ *             A second walk over the same window sums the squared residuals ru = u_j - (u + ux dx + uy dy), rv alike;
+ *             residual = sqrt(sum(ru^2 + rv^2) / n).  Each output is rounded to float once.
+ *   tensor    lk_strain_from_gradient (one function for the kernel and the host, csrc/lk_strain.hpp) of the four float
+ *             gradients as stored, computed in double, each result rounded to float:
+ *               Green-Lagrange  exx = ux + (ux^2 + vx^2) / 2,  eyy = vy + (uy^2 + vy^2) / 2,
+ *                               exy = (uy + vx) / 2 + (ux uy + vx vy) / 2
+ *               small           exx = ux,  eyy = vy,  exy = (uy + vx) / 2
+ *               e1, e2 = (exx + eyy) / 2 +- sqrt(((exx - eyy) / 2)^2 + exy^2),  theta = atan2(2 exy, exx - eyy) / 2.
+ *             A record's six tensor fields are a function of its four gradient fields alone.
+ *   status    checked in this order: TOO_FEW  n < min_neighbours;  DEGENERATE  Cxx Cyy == 0 or D <= 1e-6 Cxx Cyy (the
+ *             centres of the window on a line: one minus their squared correlation is at most 1e-6; scale-free);
+ *             FILLED  the fit is valid but s itself is not good - its values are interpolated from its neighbours;
+ *             OK  otherwise.  TOO_FEW and DEGENERATE: every float field is 0, neighbours = n.
+ *   order     fixed, as for the recovery pass: the window is visited cell by cell of a grid of cell size `radius` over the
+ *             centres (rows iy - 1, iy, iy + 1, each from ix - 1 to ix + 1), by ascending sector index within a cell,
+ *             dealt to the lanes of a group (16 or 64, chosen from the sector count and the number of cells) in turn and
+ *             summed by a fixed butterfly: the same bytes on every run for the same domain, records and configuration.
+ *             A float64 restatement reproduces it up to the order of the double sums.
+ *   modes     allowed in every mode, reference-order mode included: the call reads records and writes nothing of the
+ *             engine's - records, guesses, last parameters, counters and lk_get_reseed_info stay byte for byte.  It also
+ *             starts nothing the engine has put off: a rebuild of the sample lists that waits for the next solve (after
+ *             lk_update_sector turned a sector into a list, or after a change of mode) keeps waiting, and the centres are
+ *             the ones the engine holds at the time of the call.  Sectors that lk_translate_sectors, lk_rewarp_sectors or
+ *             lk_update_sector have already moved are fitted at their new centres: for records solved before the move,
+ *             call lk_strain_field before moving the sectors.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message: null configuration or output; no committed sectors; records == NULL
+ *             before any batch solve of the committed sectors, or with one still in flight; radius not finite or <= 0;
+ *             chi_max not finite; min_neighbours < 3; unknown tensor.
+ *   scope     one engine.  lk_group, lk_tracker, the report CSV and the CudaClass adapter do not call it; per-frame strain
+ *             of a sequence window is had by passing each frame's records. */
+enum { LK_STRAIN_OK = 0, LK_STRAIN_FILLED = 1, LK_STRAIN_TOO_FEW = 2, LK_STRAIN_DEGENERATE = 3 };
+enum { LK_STRAIN_GREEN_LAGRANGE = 0, LK_STRAIN_SMALL = 1 };
+typedef struct lk_strain_config {
+  float radius;        /* strain window: sectors whose centre lies within this many level-0 pixels (<=, tested in double) */
+  float chi_max;       /* the recovery pass's "good" rule; <= 0: the error code alone decides */
+  int min_neighbours;  /* >= 3, counting the sector itself when it is good */
+  int tensor;          /* LK_STRAIN_GREEN_LAGRANGE / LK_STRAIN_SMALL */
+} lk_strain_config;
+typedef struct lk_strain {     /* 64 bytes, one per sector */
+  float u, v;                  /* the fitted plane at the sector's centre */
+  float ux, uy, vx, vy;        /* displacement gradients */
+  float exx, eyy, exy, e1, e2, theta;  /* tensor, principal strains e1 >= e2, angle of e1 in radians */
+  float residual;              /* sqrt(sum(ru^2 + rv^2) / n) of the fit, pixels */
+  int32_t neighbours, status, reserved;
+} lk_strain;
+/* records: host [S], or NULL = the engine-held records of the last batch solve (after lk_reseed_failed: the repaired ones).
+ * Synchronous.  Changes no engine state. */
+int lk_strain_field(lk_engine *e, const lk_strain_config *cfg, const lk_result *records, lk_strain *out);
+/* the kernel's own tensor function compiled for the host, like lk_compose_inverse: grad = {ux, uy, vx, vy},
+ * out6 = {exx, eyy, exy, e1, e2, theta}.  LK_ERROR_BAD_DOMAIN for an unknown tensor or a null pointer. */
+int lk_strain_from_gradient(int tensor, const float *grad4, float *out6);
+
 /* ---- stand-alone pieces (known-answer tests, same kernels as the batch path) ------- */
 /* one evaluation of one sector at one level: raw sums A (6x6 row-major, upper valid),
  * b, chi (unscaled), error flag (apply_model_and_interpolate, correlation_class.cpp:131) */
