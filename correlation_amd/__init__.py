@@ -16,6 +16,8 @@ from ._ffi import (RESEED_GOOD, RESEED_INFO_DTYPE, RESEED_NO_NEIGHBOUR, RESEED_N
                    RESEED_RECOVERED)
 from ._ffi import (STRAIN_DEGENERATE, STRAIN_DTYPE, STRAIN_FILLED, STRAIN_GREEN_LAGRANGE, STRAIN_OK, STRAIN_SMALL,  # noqa: F401
                    STRAIN_TOO_FEW, strain_from_gradient)
+from ._ffi import (UNC_BAD_RECORD, UNC_OK, UNC_OUT_OF_IMAGE, UNC_SINGULAR, UNC_SUMS, UNC_TOO_FEW,  # noqa: F401
+                   UNCERTAINTY_DTYPE, uncertainty_from_sums)
 from .engine import HipCorrelationEngine, LkError  # noqa: F401
 from . import speckle  # noqa: F401
 from . import tracker  # noqa: F401

@@ -91,6 +91,22 @@ STRAIN_DTYPE = np.dtype([(k, np.float32) for k in ("u", "v", "ux", "uy", "vx", "
                         [("neighbours", np.int32), ("status", np.int32), ("reserved", np.int32)])
 assert STRAIN_DTYPE.itemsize == 64
 
+# per-sector uncertainty (include/lk_engine.h: lk_parameter_uncertainty)
+UNC_OK, UNC_BAD_RECORD, UNC_OUT_OF_IMAGE, UNC_TOO_FEW, UNC_SINGULAR = range(5)
+UNC_SUMS = 28   # doubles per sector: A (upper triangle, row-major), b, chi, zeros
+
+
+class LkUncertaintyConfig(C.Structure):
+    _fields_ = [("def_slot", C.c_int), ("reserved", C.c_int)]
+
+
+# lk_uncertainty as a numpy record
+UNCERTAINTY_DTYPE = np.dtype([("sigma", np.float32, (6,))] +
+                             [(k, np.float32) for k in ("noise", "rho_uv", "sigma_major", "sigma_minor", "theta", "sssig_x",
+                                                        "sssig_y")] +
+                             [("n_points", np.int32), ("status", np.int32), ("reserved", np.int32)])
+assert UNCERTAINTY_DTYPE.itemsize == 64
+
 # layout of lk_result == CorrelationResult (domains.hpp:110-118), 48 bytes
 RESULT_DTYPE = np.dtype([("p", np.float32, (6,)), ("chi", np.float32),
                          ("n_points", np.int32), ("iterations", np.int32),
@@ -169,6 +185,8 @@ SYMBOLS = {
     "lk_reseed_plan": (C.c_int, [_P, C.POINTER(LkReseedConfig), _P, _F, _P]),
     "lk_strain_field": (C.c_int, [_P, C.POINTER(LkStrainConfig), _P, _P]),
     "lk_strain_from_gradient": (C.c_int, [C.c_int, _F, _F]),
+    "lk_parameter_uncertainty": (C.c_int, [_P, C.POINTER(LkUncertaintyConfig), _P, _P, _P]),
+    "lk_uncertainty_from_sums": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P]),
     "lk_evaluate": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_evaluate_backward": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_compose_inverse": (C.c_int, [C.c_int, _F, _F, _F]),
@@ -309,3 +327,17 @@ def strain_from_gradient(tensor, grad4):
     if _compose_lib.lk_strain_from_gradient(int(tensor), fptr(g), fptr(out)) != 0:
         raise ValueError(f"lk_strain_from_gradient: bad tensor {tensor}")
     return out
+
+
+def uncertainty_from_sums(model, n, sums28, level=0):
+    """lk_uncertainty_from_sums (host, the kernel's function): the UNCERTAINTY_DTYPE record of n samples whose 28 sums
+    (A upper triangle row-major, b, chi, zeros) were evaluated at pyramid `level`."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.ascontiguousarray(sums28, np.float64).reshape(UNC_SUMS)
+    out = np.zeros(1, UNCERTAINTY_DTYPE)
+    if _compose_lib.lk_uncertainty_from_sums(int(model), int(n), s.ctypes.data_as(_P), int(level),
+                                             out.ctypes.data_as(_P)) != 0:
+        raise ValueError(f"lk_uncertainty_from_sums: bad model {model} or level {level}")
+    return out[0]

@@ -299,3 +299,20 @@ struct LkStrainArgs {
   int n_sectors, has_v, min_neighbours, tensor;
   double radius;
 };
+
+// Per-sector uncertainty (lk_uncertainty.hip, include/lk_engine.h: lk_parameter_uncertainty): one evaluation of every
+// sector at its record's parameters, at pyramid level `level` (the finest level the solve reaches).  The images, lists and
+// rectangles are that level's (LkLevelView's fields; `def` may be a ring slot's pyramid).
+struct LkUncertaintyArgs {
+  const uint8_t *und, *def; // level-L images, pitch == cols
+  int urows, ucols, drows, dcols;
+  const float2 *xy;         // level-L lists in the reference's order, [S+1] offsets, [S] implicit rectangles
+  const uint32_t *off;
+  const int4 *rect;
+  const float2 *center;     // [S] level-0 centres
+  const lk_result *rec;     // [S]
+  const uint32_t *order;    // [n_sectors] the sectors of this launch (one lane group's)
+  lk_uncertainty *out;      // [S]
+  double *sums;             // [S][28] or null: A (upper triangle, row-major), b, chi in the layout of Sums<P>, then zeros
+  int n_sectors, level;
+};

@@ -298,6 +298,7 @@ struct lk_engine {
   int records_S = 0;        // sectors the engine-held records of a batch solve cover (0: no solve since the commit)
   void *reseed = nullptr;   // lk_reseed.cpp's buffers (lk_reseed_failed / lk_reseed_plan), released by lk_destroy
   void *strain = nullptr;   // lk_strain.cpp's buffers (lk_strain_field), released by lk_destroy
+  void *uncertainty = nullptr; // lk_uncertainty.cpp's buffers (lk_parameter_uncertainty), released by lk_destroy
 
   int fail(int code, const std::string &what) {
     err = what;
@@ -366,6 +367,8 @@ void lk_destroy(lk_engine *e) {
   e->reseed = nullptr;
   lk_internal_strain_release(e->strain);
   e->strain = nullptr;
+  lk_internal_uncertainty_release(e->uncertainty);
+  e->uncertainty = nullptr;
   for (auto &im : e->img)
     for (auto &p : im.lvl)
       if (p)
@@ -2917,6 +2920,59 @@ int lk_internal_strain_view(lk_engine *e, int need_records, LkStrainView *v) {
   return LK_ERROR_NONE;
 }
 void **lk_internal_strain_slot(lk_engine *e) { return &e->strain; }
+
+int lk_internal_uncertainty_view(lk_engine *e, int need_records, int def_slot, LkUncertaintyView *v) {
+  if (!e->committed || e->S <= 0)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: no committed sectors (call lk_commit_sectors)");
+  if (need_records) {
+    if (e->results_pending)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: the outstanding solve has not been waited for (lk_wait_results)");
+    if (e->seq.outstanding)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: a sequence window is outstanding (lk_wait_sequence)");
+    if (e->records_S != e->S)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: no solve of the committed sectors yet (lk_correlate_all*); pass records");
+  }
+  HIPCHK(hipSetDevice(e->cfg.device));
+  if (e->recommit_pending) { // lk_update_sector moved lists: rebuild them as the next solve would (the pass walks them)
+    e->recommit_pending = false;
+    if (int rc = commit_impl(e, true))
+      return rc;
+  }
+  const int level = e->cfg.py_start; // a level the commit builds lists for (commit_impl: level 0 and py_start, ...)
+  const DevImage &u = e->img[LK_IMG_UND];
+  const DevImage *d = &e->img[LK_IMG_DEF];
+  if (def_slot >= 0) {
+    if (def_slot >= (int)e->ring.size())
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: unknown ring slot (lk_sequence_reserve)");
+    d = &e->ring[(size_t)def_slot];
+    if (d->valid)
+      HIPCHK(hipStreamWaitEvent(e->stream, e->ring_ready[(size_t)def_slot], 0));
+  } else if (def_slot != -1) {
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: def_slot must be -1 (LK_IMG_DEF) or a ring slot");
+  }
+  if (!u.valid || !d->valid || !u.lvl[level] || !d->lvl[level])
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: the undeformed and the deformed image must be set");
+  v->stream = e->stream;
+  v->S = e->S;
+  v->model = e->cfg.fitting_model;
+  v->interp = e->cfg.interpolation;
+  v->level = level;
+  v->und = u.lvl[level];
+  v->def = d->lvl[level];
+  v->urows = u.rows >> level;
+  v->ucols = u.cols >> level;
+  v->drows = d->rows >> level;
+  v->dcols = d->cols >> level;
+  v->xy = e->d_xy[level].p;
+  v->off = e->d_off[level].p;
+  v->rect = e->d_rect[level].p;
+  v->h_rect0 = e->h_rect[0].data();
+  v->h_off0 = e->h_off[0].data();
+  v->center = e->d_center.p;
+  v->result = e->d_result.p;
+  return LK_ERROR_NONE;
+}
+void **lk_internal_uncertainty_slot(lk_engine *e) { return &e->uncertainty; }
 
 extern "C" {
 

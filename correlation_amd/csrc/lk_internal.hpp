@@ -98,3 +98,28 @@ void lk_internal_strain_release(void *state); // (lk_strain.cpp; called by lk_de
 // of its device part (bounding box with its round trip, grid kernels, prep, fit), the lane group and variant that ran and
 // the expected members of a sector's 3 x 3 cells.  The two events are recorded by every call; the time is read here.
 extern "C" int lk_internal_strain_last(lk_engine *e, float *device_ms, int *group, int *packed, double *members);
+
+// ---- per-sector uncertainty (lk_uncertainty.cpp) -----------------------------------------------------------------------
+// What lk_parameter_uncertainty needs of the engine: read-only, at level L = py_start (the finest level the solve reaches).
+// The accessor finishes a pending rebuild of the lists as lk_internal_guess_search_view does (the pass walks them), and makes
+// the engine's stream wait for a ring slot's pyramid.  need_records: the engine must hold the records of a finished batch
+// solve of the committed sectors.  Allowed in every mode, reference-order included.
+struct LkUncertaintyView {
+  hipStream_t stream;
+  int S, model, interp, level;
+  const uint8_t *und, *def; // level-L images (def: LK_IMG_DEF or the ring slot)
+  int urows, ucols, drows, dcols;
+  const float2 *xy;         // level-L lists in the reference's order, [S+1] offsets, [S] implicit rectangles (device)
+  const uint32_t *off;
+  const int4 *rect;
+  const int4 *h_rect0;      // [S] the level-0 rectangles on the host (width 0: explicit list)
+  const uint32_t *h_off0;   // [S+1] the level-0 offsets on the host
+  const float2 *center;     // [S]
+  const lk_result *result;  // [S] the engine-held records
+};
+int lk_internal_uncertainty_view(lk_engine *e, int need_records, int def_slot, LkUncertaintyView *v);
+void **lk_internal_uncertainty_slot(lk_engine *e);
+void lk_internal_uncertainty_release(void *state); // (lk_uncertainty.cpp; called by lk_destroy)
+// Bench hook (scripts/uncertainty_bench.py; exported, not part of include/*.h): of the last lk_parameter_uncertainty, the
+// HIP-event time of its kernels and the sectors each lane group (16, 64, 512 lanes) took.
+extern "C" int lk_internal_uncertainty_last(lk_engine *e, float *device_ms, int *count3);

@@ -96,3 +96,7 @@ hipError_t lk_launch_strain_prep(const lk_result *rec, const float2 *center, int
                                  uint8_t *good, float4 *pack, hipStream_t st);
 // group: 16 or 64 lanes per sector; packed != 0: the neighbours' data come from a.pack, else from a.center / a.good / a.rec
 hipError_t lk_launch_strain(const LkStrainArgs &a, int group, int packed, hipStream_t st);
+
+// ---- lk_uncertainty.hip: per-sector uncertainty (lk_parameter_uncertainty)
+// group: 16, 64 or 512 lanes per sector (lk_bw_group of the level-0 sample count); a.order lists that group's sectors
+hipError_t lk_launch_uncertainty(const LkUncertaintyArgs &a, int model, int interp, int group, hipStream_t st);

@@ -382,6 +382,23 @@ class HipCorrelationEngine:
                                            out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # ---- per-sector uncertainty: covariance of the solved parameters ----------------------------------
+    def parameter_uncertainty(self, records=None, def_slot=-1, return_sums=False):
+        """lk_parameter_uncertainty: an UNCERTAINTY_DTYPE array [S] from the engine-held records of the last batch solve
+        or, records given, from those [S]; with return_sums also the 28 double sums of every sector [S][28].  No engine
+        state changes."""
+        cfg = _ffi.LkUncertaintyConfig(int(def_slot), 0)
+        rec = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        out = np.zeros(self.n_sectors, _ffi.UNCERTAINTY_DTYPE)
+        sums = np.zeros((self.n_sectors, _ffi.UNC_SUMS), np.float64) if return_sums else None
+        self._chk(self.lib.lk_parameter_uncertainty(self._h, C.byref(cfg),
+                                                    rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
+                                                    out.ctypes.data_as(C.c_void_p),
+                                                    sums.ctypes.data_as(C.c_void_p) if return_sums else None))
+        return (out, sums) if return_sums else out
+
     # ---- stand-alone pieces -------------------------------------------------------------
     def evaluate(self, sector, level, p):
         pp = np.zeros(6, np.float32)

@@ -568,6 +568,70 @@ int lk_strain_field(lk_engine *e, const lk_strain_config *cfg, const lk_result *
  * out6 = {exx, eyy, exy, e1, e2, theta}.  LK_ERROR_BAD_DOMAIN for an unknown tensor or a null pointer. */
 int lk_strain_from_gradient(int tensor, const float *grad4, float *out6);
 
+/* ---- per-sector uncertainty: the covariance of the solved parameters ---------------------- */
+/* lk_parameter_uncertainty gives every sector the standard deviation of each solved parameter: one evaluation at the
+ * record's parameters, the Gauss-Newton normal matrix A and the residual chi of that evaluation, Cov(p) = s^2 A^-1 with
+ * s^2 = chi / (n - P) (csrc/lk_uncertainty.hip).  chi alone is a residual, not an error bar: a sector on a one-directional
+ * texture converges with a small chi and a useless u (the aperture problem) - and a long uncertainty ellipse.
+ *   level     L = py_start, the finest level the solve reaches.  p = the record's resultingParameters brought to level L's
+ *             scale by the rule the solve uses between levels (translate_model_parameters, pyramid_class.cpp:260-287:
+ *             p[0] and p[1] times 2^-L).  The samples are the sector's level-L list or implicit rectangle (a rectangle row
+ *             by row, a list in its order), the centre is the committed centre times 2^-L as in the solve.
+ *   sample    the forward evaluation, whatever lk_set_update says: (xd, yd) = W(x_i; p) by the model, the deformed image's
+ *             value and gradient there by the engine's interpolation, V_i = und(node) - def(xd, yd), J_i = gradient times
+ *             dW/dp - the device functions and the float arithmetic of the forward solve.  The products J_a J_b, J_a V and
+ *             V^2 are formed in double from those floats and summed in double (no fused multiply-add).  A (upper
+ *             triangle, row-major), b and chi are the 28 sums of a sector, in that order, padded with zeros for P < 6.
+ *   order     the lane group is fixed by the sector's own level-0 sample count: 16 lanes up to 512 samples, 64 up to 8192,
+ *             512 above (the backward solve's groups).  Lane j takes the samples j, j + G, j + 2G, ...; the lanes' sums
+ *             are added by a fixed butterfly, then in a fixed order across rows and wavefronts.  A sector's sums and
+ *             record are the same bytes in any batch, shard or mode.  A float64 restatement reproduces the sums up to the
+ *             order of the double sums.
+ *   record    lk_uncertainty_from_sums (one function for the kernel and the host, csrc/lk_uncertainty.hpp), all in double:
+ *             C_ab = A_ab / sqrt(A_aa A_bb); an unpivoted L D L^T of C and from it C^-1;
+ *             Cov_ab = s^2 (C^-1)_ab / sqrt(A_aa A_bb); sigma[k] = sqrt(Cov_kk), times 2^L for k < 2 (level-0 pixels).
+ *             The ellipse is that of the 2 x 2 block (c00, c01, c11) of u and v in level-0 pixels (Cov times 4^L), by the
+ *             formulas of the strain tensor's principal values: sigma_major, sigma_minor = sqrt((c00 + c11) / 2 +-
+ *             sqrt(((c00 - c11) / 2)^2 + c01^2)), theta = atan2(2 c01, c00 - c11) / 2, rho_uv = c01 / sqrt(c00 c11).
+ *             LK_FM_U: sigma_major = sigma[0], rho_uv = sigma_minor = theta = sssig_y = 0.  noise = sqrt(s^2);
+ *             sssig_x = A_00 / n, sssig_y = A_11 / n.  Each output is rounded to float once.
+ *   status    checked in this order: BAD_RECORD  the record is not LK_ERROR_NONE or has a non-finite parameter or chi (the
+ *             recovery pass's "good" rule with chi_max = 0; the sector is not evaluated);  OUT_OF_IMAGE  the sampler
+ *             flagged a sample;  TOO_FEW  n <= P;  SINGULAR  some A_aa == 0, or a pivot of the L D L^T of the
+ *             unit-diagonal C is <= 1e-10 (scale-free).  For every status but OK the float fields are 0, n_points = n; the
+ *             sums of a BAD_RECORD or OUT_OF_IMAGE sector are reported as 0.
+ *   modes     allowed in every mode, reference-order mode included.  The call reads records and images and writes nothing
+ *             of the engine's: records, guesses, last parameters, counters, lk_get_reseed_info and the strain field stay
+ *             byte for byte.  A rebuild of the sample lists that waits for the next solve (lk_update_sector) is carried
+ *             out first, as lk_search_guesses does: the pass walks the lists.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message: null configuration or output; no committed sectors; records == NULL
+ *             before any batch solve of the committed sectors, or with one still in flight; the images are not set; a bad
+ *             def_slot.
+ *   scope     one engine, the undeformed image is LK_IMG_UND.  lk_group, lk_tracker, the report CSV, the CudaClass
+ *             adapter, lk_reseed_failed and lk_strain_field do not call it.  Windows with reference_previous are not
+ *             covered (their undeformed image is the previous frame). */
+enum { LK_UNC_OK = 0, LK_UNC_BAD_RECORD = 1, LK_UNC_OUT_OF_IMAGE = 2, LK_UNC_TOO_FEW = 3, LK_UNC_SINGULAR = 4 };
+typedef struct lk_uncertainty_config {
+  int def_slot;   /* -1: LK_IMG_DEF; k >= 0: ring slot k (lk_sequence_set_frame), as for lk_search_guesses */
+  int reserved;
+} lk_uncertainty_config;
+typedef struct lk_uncertainty {          /* 64 bytes, one per sector */
+  float sigma[6];                        /* standard deviation of p[k], level-0 scale; 0 for k >= P */
+  float noise;                           /* s = sqrt(chi / (n - P)), grey levels */
+  float rho_uv;                          /* Cov01 / (sigma0 sigma1); 0 for LK_FM_U */
+  float sigma_major, sigma_minor, theta; /* principal axes of the 2x2 (u, v) covariance, level-0 pixels; angle of the major axis */
+  float sssig_x, sssig_y;                /* A00 / n, and A11 / n for models with v (mean squared image gradient) */
+  int32_t n_points, status, reserved;
+} lk_uncertainty;
+/* records: host [S], or NULL = the engine-held records of the last finished batch solve.  out: [S].  sums_out: [S][28]
+ * doubles or NULL.  Synchronous.  Changes no engine state. */
+int lk_parameter_uncertainty(lk_engine *e, const lk_uncertainty_config *cfg, const lk_result *records, lk_uncertainty *out,
+                             double *sums_out);
+/* the kernel's own function compiled for the host: the record of n samples with the 28 sums `sums28` evaluated at `level`
+ * (status OK, TOO_FEW or SINGULAR).  LK_ERROR_BAD_DOMAIN for an unknown model, a level outside 0 .. LK_MAX_LEVELS - 1 or a
+ * null pointer. */
+int lk_uncertainty_from_sums(int model, int n, const double *sums28, int level, lk_uncertainty *out);
+
 /* ---- stand-alone pieces (known-answer tests, same kernels as the batch path) ------- */
 /* one evaluation of one sector at one level: raw sums A (6x6 row-major, upper valid),
  * b, chi (unscaled), error flag (apply_model_and_interpolate, correlation_class.cpp:131) */
