@@ -18,6 +18,8 @@ from ._ffi import (STRAIN_DEGENERATE, STRAIN_DTYPE, STRAIN_FILLED, STRAIN_GREEN_
                    STRAIN_TOO_FEW, strain_from_gradient)
 from ._ffi import (UNC_BAD_RECORD, UNC_OK, UNC_OUT_OF_IMAGE, UNC_SINGULAR, UNC_SUMS, UNC_TOO_FEW,  # noqa: F401
                    UNCERTAINTY_DTYPE, uncertainty_from_sums)
+from ._ffi import (ERROR_OUTLIER, OUTLIER_DEGENERATE, OUTLIER_DTYPE, OUTLIER_FLAGGED, OUTLIER_NOT_GOOD, OUTLIER_OK,  # noqa: F401
+                   OUTLIER_TOO_FEW, outlier_from_window)
 from .engine import HipCorrelationEngine, LkError  # noqa: F401
 from . import speckle  # noqa: F401
 from . import tracker  # noqa: F401

@@ -22,6 +22,8 @@ IMG_UND, IMG_DEF, IMG_NXT = 0, 1, 2
  ERROR_CORRELATION_MAX_ITERS_REACHED, ERROR_BAD_DOMAIN, ERROR_SOLVER, ERROR_DEVICE,
  ERROR_MULTITHREAD) = range(8)
 
+ERROR_OUTLIER = 8   # extension: set by lk_flag_outliers with mark = 1 (include/lk_engine.h)
+
 N_PARAMS = {FM_U: 1, FM_UV: 2, FM_UVQ: 3, FM_UVUXUYVXVY: 6}
 UPDATE_FORWARD, UPDATE_BACKWARD = 0, 1   # lk_set_update (updateEnum, enums.hpp:39)
 
@@ -107,6 +109,20 @@ UNCERTAINTY_DTYPE = np.dtype([("sigma", np.float32, (6,))] +
                              [("n_points", np.int32), ("status", np.int32), ("reserved", np.int32)])
 assert UNCERTAINTY_DTYPE.itemsize == 64
 
+# outlier flags (include/lk_engine.h: lk_flag_outliers)
+OUTLIER_OK, OUTLIER_FLAGGED, OUTLIER_TOO_FEW, OUTLIER_DEGENERATE, OUTLIER_NOT_GOOD = range(5)
+
+
+class LkOutlierConfig(C.Structure):
+    _fields_ = [("radius", C.c_float), ("chi_max", C.c_float), ("eps", C.c_float), ("threshold", C.c_float),
+                ("min_neighbours", C.c_int), ("detrend", C.c_int), ("passes", C.c_int), ("mark", C.c_int)]
+
+
+# lk_outlier as a numpy record
+OUTLIER_DTYPE = np.dtype([(k, np.float32) for k in ("med_u", "med_v", "mad_u", "mad_v", "ratio_u", "ratio_v")] +
+                         [("neighbours", np.int32), ("status", np.int32)])
+assert OUTLIER_DTYPE.itemsize == 32
+
 # layout of lk_result == CorrelationResult (domains.hpp:110-118), 48 bytes
 RESULT_DTYPE = np.dtype([("p", np.float32, (6,)), ("chi", np.float32),
                          ("n_points", np.int32), ("iterations", np.int32),
@@ -187,6 +203,8 @@ SYMBOLS = {
     "lk_strain_from_gradient": (C.c_int, [C.c_int, _F, _F]),
     "lk_parameter_uncertainty": (C.c_int, [_P, C.POINTER(LkUncertaintyConfig), _P, _P, _P]),
     "lk_uncertainty_from_sums": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P]),
+    "lk_flag_outliers": (C.c_int, [_P, C.POINTER(LkOutlierConfig), _P, _P, _P, _I]),
+    "lk_outlier_from_window": (C.c_int, [C.c_int, _F, _F, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "lk_evaluate": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_evaluate_backward": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_compose_inverse": (C.c_int, [C.c_int, _F, _F, _F]),
@@ -340,4 +358,21 @@ def uncertainty_from_sums(model, n, sums28, level=0):
     if _compose_lib.lk_uncertainty_from_sums(int(model), int(n), s.ctypes.data_as(_P), int(level),
                                              out.ctypes.data_as(_P)) != 0:
         raise ValueError(f"lk_uncertainty_from_sums: bad model {model} or level {level}")
+    return out[0]
+
+
+def outlier_from_window(e_u, e_v, es_u, es_v, eps, threshold):
+    """lk_outlier_from_window (host, the kernel's selection and ratio arithmetic): the OUTLIER_DTYPE record of a sector
+    whose window holds the values e_u, e_v [n] and whose own values are es_u, es_v."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    u = np.ascontiguousarray(e_u, np.float32).reshape(-1)
+    v = np.ascontiguousarray(e_v, np.float32).reshape(-1)
+    if len(u) != len(v):
+        raise ValueError("lk_outlier_from_window: e_u and e_v differ in length")
+    out = np.zeros(1, OUTLIER_DTYPE)
+    if _compose_lib.lk_outlier_from_window(len(u), fptr(u), fptr(v), float(es_u), float(es_v), float(eps), float(threshold),
+                                           out.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_outlier_from_window: an empty window, a value that is not finite, or eps / threshold <= 0")
     return out[0]

@@ -300,6 +300,20 @@ struct LkStrainArgs {
   double radius;
 };
 
+// Outlier flags (lk_outlier.hip, include/lk_engine.h: lk_flag_outliers): one pass of the (detrended) normalised median test.
+struct LkOutlierArgs {
+  LkReseedGrid grid;
+  const float2 *center;  // [S]
+  const uint8_t *good;   // [S] the good rule, evaluated once per call (lk_outlier_prep_kernel)
+  const float4 *pack;    // [S] {cx, cy, u, v}; cx = NaN for a sector that is not good or was flagged in the pass before
+  lk_outlier *out;       // [S]
+  int n_sectors, min_neighbours, detrend;
+  int lds_rows;          // floats of a component a lane may stash (0 .. kLkOutlierRows); a fuller window is re-walked
+  float eps, threshold;
+  double radius;
+};
+constexpr int kLkOutlierRows = 16;
+
 // Per-sector uncertainty (lk_uncertainty.hip, include/lk_engine.h: lk_parameter_uncertainty): one evaluation of every
 // sector at its record's parameters, at pyramid level `level` (the finest level the solve reaches).  The images, lists and
 // rectangles are that level's (LkLevelView's fields; `def` may be a ring slot's pyramid).

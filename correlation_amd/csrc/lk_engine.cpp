@@ -299,6 +299,7 @@ struct lk_engine {
   void *reseed = nullptr;   // lk_reseed.cpp's buffers (lk_reseed_failed / lk_reseed_plan), released by lk_destroy
   void *strain = nullptr;   // lk_strain.cpp's buffers (lk_strain_field), released by lk_destroy
   void *uncertainty = nullptr; // lk_uncertainty.cpp's buffers (lk_parameter_uncertainty), released by lk_destroy
+  void *outlier = nullptr;  // lk_outlier.cpp's buffers (lk_flag_outliers), released by lk_destroy
 
   int fail(int code, const std::string &what) {
     err = what;
@@ -369,6 +370,8 @@ void lk_destroy(lk_engine *e) {
   e->strain = nullptr;
   lk_internal_uncertainty_release(e->uncertainty);
   e->uncertainty = nullptr;
+  lk_internal_outlier_release(e->outlier);
+  e->outlier = nullptr;
   for (auto &im : e->img)
     for (auto &p : im.lvl)
       if (p)
@@ -2973,6 +2976,28 @@ int lk_internal_uncertainty_view(lk_engine *e, int need_records, int def_slot, L
   return LK_ERROR_NONE;
 }
 void **lk_internal_uncertainty_slot(lk_engine *e) { return &e->uncertainty; }
+
+int lk_internal_outlier_view(lk_engine *e, int need_records, LkOutlierView *v) {
+  if (!e->committed || e->S <= 0)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_flag_outliers: no committed sectors (call lk_commit_sectors)");
+  if (need_records) {
+    if (e->results_pending)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_flag_outliers: the outstanding solve has not been waited for (lk_wait_results)");
+    if (e->seq.outstanding)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_flag_outliers: a sequence window is outstanding (lk_wait_sequence)");
+    if (e->records_S != e->S)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_flag_outliers: no solve of the committed sectors yet (lk_correlate_all*); pass records");
+  }
+  HIPCHK(hipSetDevice(e->cfg.device));
+  // (as lk_internal_strain_view: a pending rebuild of the lists stays pending)
+  v->stream = e->stream;
+  v->S = e->S;
+  v->model = e->cfg.fitting_model;
+  v->center = e->d_center.p;
+  v->result = e->d_result.p;
+  return LK_ERROR_NONE;
+}
+void **lk_internal_outlier_slot(lk_engine *e) { return &e->outlier; }
 
 extern "C" {
 

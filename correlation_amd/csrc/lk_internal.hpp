@@ -123,3 +123,20 @@ void lk_internal_uncertainty_release(void *state); // (lk_uncertainty.cpp; calle
 // Bench hook (scripts/uncertainty_bench.py; exported, not part of include/*.h): of the last lk_parameter_uncertainty, the
 // HIP-event time of its kernels and the sectors each lane group (16, 64, 512 lanes) took.
 extern "C" int lk_internal_uncertainty_last(lk_engine *e, float *device_ms, int *count3);
+
+// ---- outlier flags (lk_outlier.cpp) --------------------------------------------------------------------------------------
+// What lk_flag_outliers needs of the engine: lk_internal_strain_view's rules (a pending rebuild of the lists keeps waiting),
+// but `result` may be written - the errorCode words of the flagged sectors, and only with mark = 1 on engine-held records.
+struct LkOutlierView {
+  hipStream_t stream;
+  int S, model;
+  const float2 *center; // [S]
+  lk_result *result;    // [S] the engine-held records
+};
+int lk_internal_outlier_view(lk_engine *e, int need_records, LkOutlierView *v);
+void **lk_internal_outlier_slot(lk_engine *e);
+void lk_internal_outlier_release(void *state); // (lk_outlier.cpp; called by lk_destroy)
+// Bench hook (scripts/outlier_bench.py; exported, not part of include/*.h): of the last lk_flag_outliers, the HIP-event time
+// of its device part (bounding box with its round trip, grid kernels, prep, every pass, the mark), the lane group, the LDS
+// rows a lane may stash and the expected members of a sector's 3 x 3 cells.
+extern "C" int lk_internal_outlier_last(lk_engine *e, float *device_ms, int *group, int *lds_rows, double *members);

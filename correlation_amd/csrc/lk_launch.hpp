@@ -100,3 +100,15 @@ hipError_t lk_launch_strain(const LkStrainArgs &a, int group, int packed, hipStr
 // ---- lk_uncertainty.hip: per-sector uncertainty (lk_parameter_uncertainty)
 // group: 16, 64 or 512 lanes per sector (lk_bw_group of the level-0 sample count); a.order lists that group's sectors
 hipError_t lk_launch_uncertainty(const LkUncertaintyArgs &a, int model, int interp, int group, hipStream_t st);
+
+// ---- lk_outlier.hip: the outlier flags (lk_flag_outliers)
+// good[s] by the shared rule and pack[s] = {cx, cy, u + 0, v + 0} (cx = NaN for a sector that is not good; v = 0 without one)
+hipError_t lk_launch_outlier_prep(const lk_result *rec, const float2 *center, int n_sectors, int model, float chi_max,
+                                  uint8_t *good, float4 *pack, hipStream_t st);
+// between two passes: pack[s].x = NaN for a sector that is not good or that `flags` (the pass before) has flagged, else cx
+hipError_t lk_launch_outlier_exclude(const lk_outlier *flags, const float2 *center, const uint8_t *good, int n_sectors,
+                                     float4 *pack, hipStream_t st);
+// one pass; group: 16 or 64 lanes per sector
+hipError_t lk_launch_outlier(const LkOutlierArgs &a, int group, hipStream_t st);
+// errorCode = LK_ERROR_OUTLIER in the records of the flagged sectors
+hipError_t lk_launch_outlier_mark(const lk_outlier *flags, int n_sectors, lk_result *rec, hipStream_t st);

@@ -399,6 +399,33 @@ class HipCorrelationEngine:
                                                     sums.ctypes.data_as(C.c_void_p) if return_sums else None))
         return (out, sums) if return_sums else out
 
+    # ---- outlier flags: the (detrended) normalised median test ----------------------------------------
+    def flag_outliers(self, radius, chi_max=0.0, eps=0.02, threshold=3.0, min_neighbours=None, detrend=True, passes=1,
+                      mark=False, records=None, return_records=False):
+        """lk_flag_outliers: (OUTLIER_DTYPE array [S], sectors flagged) from the engine-held records of the last batch
+        solve or, records given, from those [S]; with return_records also the records that were read, the flagged ones
+        carrying ERROR_OUTLIER when mark is set.  mark on the engine-held records writes that code into them: the only
+        engine state the call changes."""
+        if min_neighbours is None:
+            min_neighbours = 4 if detrend else 3
+        cfg = _ffi.LkOutlierConfig(float(radius), float(chi_max), float(eps), float(threshold), int(min_neighbours),
+                                   int(detrend), int(passes), int(mark))
+        rec = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        out = np.zeros(self.n_sectors, _ffi.OUTLIER_DTYPE)
+        rec_out = np.zeros(self.n_sectors, RESULT_DTYPE) if return_records else None
+        n = C.c_int()
+        self._chk(self.lib.lk_flag_outliers(self._h, C.byref(cfg), rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
+                                            out.ctypes.data_as(C.c_void_p),
+                                            rec_out.ctypes.data_as(C.c_void_p) if return_records else None, C.byref(n)))
+        return (out, n.value, rec_out) if return_records else (out, n.value)
+
+    @staticmethod
+    def outlier_from_window(e_u, e_v, es_u, es_v, eps, threshold):
+        """lk_outlier_from_window: the kernel's selection and ratio arithmetic on the host (no engine needed)."""
+        return _ffi.outlier_from_window(e_u, e_v, es_u, es_v, eps, threshold)
+
     # ---- stand-alone pieces -------------------------------------------------------------
     def evaluate(self, sector, level, p):
         pp = np.zeros(6, np.float32)

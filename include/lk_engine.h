@@ -40,7 +40,11 @@ typedef enum {
   LK_ERROR_BAD_DOMAIN = 4,
   LK_ERROR_SOLVER = 5, /* error_cuSolver */
   LK_ERROR_DEVICE = 6, /* error_cuda: any HIP failure */
-  LK_ERROR_MULTITHREAD = 7
+  LK_ERROR_MULTITHREAD = 7,
+  /* Extension (not a value of the reference's errorEnum): the record converged, but lk_flag_outliers with mark = 1 found
+   * its displacement inconsistent with its neighbourhood.  No solve produces it.  It is not LK_ERROR_NONE, so the "good"
+   * rule of the recovery pass, the strain field and the uncertainty pass rejects such a record. */
+  LK_ERROR_OUTLIER = 8
 } lk_error;
 
 /* interpolationModelEnum, enums.hpp:10-15 */
@@ -567,6 +571,83 @@ int lk_strain_field(lk_engine *e, const lk_strain_config *cfg, const lk_result *
 /* the kernel's own tensor function compiled for the host, like lk_compose_inverse: grad = {ux, uy, vx, vy},
  * out6 = {exx, eyy, exy, e1, e2, theta}.  LK_ERROR_BAD_DOMAIN for an unknown tensor or a null pointer. */
 int lk_strain_from_gradient(int tensor, const float *grad4, float *out6);
+
+/* ---- outlier flags: the (detrended) normalised median test of the solved field ------------- */
+/* lk_flag_outliers is the spatial validity check of the solved displacements: a sector that converged cleanly to the wrong
+ * place (a neighbouring speckle, a reflection, a crack edge) has LK_ERROR_NONE and an unremarkable chi, and the "good" rule
+ * passes it.  The test compares each sector's displacement with the median of its neighbours', normalised by their median
+ * absolute deviation (Westerweel & Scarano 2005) - by default after taking the window's least-squares plane out of both,
+ * since a displacement gradient of a few percent otherwise hides half-pixel outliers and flags healthy edge sectors
+ * (csrc/lk_outlier.hip).
+ *   data      of a sector: position = the engine's committed centre c; displacement u = p[0] + 0.0f and v = p[1] + 0.0f
+ *             (v = 0 for LK_FM_U), so -0 enters as +0.
+ *   good      the shared rule of the recovery pass and the strain field (one device function): LK_ERROR_NONE, finite
+ *             parameters (the model's P), finite chi and, if chi_max > 0, chi <= chi_max.
+ *   window    of sector s: every sector j != s that is good, was not flagged in the pass before, and has
+ *             dx^2 + dy^2 <= r^2, where (dx, dy) = c_j - c_s is formed in double from the float centres and
+ *             r = (double)radius.  n = the number of such sectors; s itself is never counted.
+ *   detrend   = 1: the plane of lk_strain_field's `fit` paragraph over that window - the same sums, moments, D and
+ *             DEGENERATE rule, all in double without fused multiply-add: u0 = Su / n - ux (Sx / n) - uy (Sy / n);
+ *             e_j = (float)(u_j - (u0 + ux dx_j + uy dy_j)), e_s = (float)(u_s - u0); v alike.
+ *             = 0: e_j = u_j, e_s = u_s (the plain Westerweel-Scarano test); no fit, and no DEGENERATE status.
+ *   median    of n floats x: (float)(((double)x[(n - 1) / 2] + (double)x[n / 2]) / 2) of the values sorted as IEEE numbers
+ *             (a zero of either sign counts as +0).  It does not depend on the order the window is visited in.
+ *   test      per component: med = median(e_j); mad = median((float)fabs((double)e_j - (double)med));
+ *             ratio = (float)(fabs((double)e_s - (double)med) / ((double)mad + (double)eps)).  The sector is flagged when
+ *             max(ratio_u, ratio_v) > threshold, compared on the double values before the rounding to float.
+ *   status    checked in this order: TOO_FEW  n < min_neighbours;  DEGENERATE  detrend only: Cxx Cyy == 0 or
+ *             D <= 1e-6 Cxx Cyy (the window's centres on a line);  NOT_GOOD  s itself fails the good rule: med and mad are
+ *             reported, both ratios are 0, the sector is never flagged;  FLAGGED;  OK.  TOO_FEW and DEGENERATE: every float
+ *             field is 0.  neighbours = n always.
+ *   passes    pass 0 excludes nothing; pass k leaves the sectors flagged in pass k - 1 (and only those) out of every
+ *             window - they are still tested themselves.  The records and flags returned are the last pass's, and
+ *             n_flagged counts them.  Two passes cure the usual false flag: a healthy neighbour whose plane was bent by
+ *             the outlier next to it.
+ *   order     plain mode: every float field is independent of the visiting order, hence of the lane group and of whether
+ *             the window was kept in LDS.  Detrended mode: the plane's sums are added in lk_strain_field's fixed order
+ *             (cell by cell, by ascending sector index within a cell, dealt to 16 or 64 lanes, a fixed butterfly): the same
+ *             bytes on every run; a float64 restatement reproduces them up to the order of the double sums.
+ *   records   records == NULL reads the engine-held records of the last batch solve (after lk_reseed_failed: the repaired
+ *             ones), else the caller's [S].  records_out, if not NULL, receives the records that were read, with
+ *             errorCode = LK_ERROR_OUTLIER in the flagged sectors when mark = 1.  mark = 1 with records == NULL writes that
+ *             code into the engine-held records of the flagged sectors as well: the only engine state the call ever
+ *             changes.  A following lk_reseed_failed then retries those sectors and keeps them out of its neighbour means;
+ *             a following lk_strain_field(records = NULL) fills them from their neighbours.  With mark = 0 nothing of the
+ *             engine moves - records, guesses, last parameters, counters, lk_get_reseed_info - and, as for
+ *             lk_strain_field, a rebuild of the sample lists that waits for the next solve keeps waiting.
+ *   modes     allowed in every mode, reference-order mode included; but mark = 1 on engine-held records is refused in
+ *             reference-order mode: that mode's records are by definition the CPU engine's.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message: null configuration or output; no committed sectors; records == NULL
+ *             before any batch solve of the committed sectors, or with one still in flight; radius not finite or <= 0;
+ *             chi_max not finite; eps or threshold not finite or <= 0; min_neighbours < 4 with detrend (a plane has three
+ *             unknowns and the sector itself is not counted), < 3 without; detrend or mark not 0 / 1; passes outside 1..4.
+ *   scope     one engine.  lk_group, lk_tracker, the report CSV and the CudaClass adapter do not call it.  No weights inside
+ *             the window; lk_parameter_uncertainty's sigma does not enter eps. */
+enum { LK_OUTLIER_OK = 0, LK_OUTLIER_FLAGGED = 1, LK_OUTLIER_TOO_FEW = 2, LK_OUTLIER_DEGENERATE = 3, LK_OUTLIER_NOT_GOOD = 4 };
+typedef struct lk_outlier_config {
+  float radius;        /* window: sectors whose centre lies within this many level-0 pixels (<=, tested in double) */
+  float chi_max;       /* the shared "good" rule; <= 0: the error code alone decides */
+  float eps;           /* noise floor of the normalisation, pixels; > 0 */
+  float threshold;     /* flagged when max(ratio_u, ratio_v) > threshold; > 0 */
+  int min_neighbours;  /* >= 4 with detrend, >= 3 without; the sector itself is never counted */
+  int detrend;         /* 1: test the residual to the window's plane; 0: the plain Westerweel-Scarano test */
+  int passes;          /* 1..4: pass k leaves the sectors flagged in pass k - 1 out of every window */
+  int mark;            /* 1: flagged sectors get errorCode = LK_ERROR_OUTLIER in the records the call returns / holds */
+} lk_outlier_config;
+typedef struct lk_outlier {       /* 32 bytes, one per sector, of the last pass */
+  float med_u, med_v;             /* median of the window's (detrended) u, v */
+  float mad_u, mad_v;             /* median of |e_j - med| */
+  float ratio_u, ratio_v;
+  int32_t neighbours, status;
+} lk_outlier;
+/* records: host [S] or NULL; out: [S]; records_out: host [S] or NULL; n_flagged: or NULL.  Synchronous. */
+int lk_flag_outliers(lk_engine *e, const lk_outlier_config *cfg, const lk_result *records, lk_outlier *out,
+                     lk_result *records_out, int *n_flagged);
+/* the kernel's own selection and ratio arithmetic compiled for the host (csrc/lk_outlier.hpp): the record of a sector whose
+ * window holds the n values e_u, e_v and whose own values are es_u, es_v (status OK or FLAGGED, neighbours = n).
+ * LK_ERROR_BAD_DOMAIN for a null pointer, n < 1, a value that is not finite, or eps / threshold not finite or <= 0. */
+int lk_outlier_from_window(int n, const float *e_u, const float *e_v, float es_u, float es_v, float eps, float threshold,
+                           lk_outlier *out);
 
 /* ---- per-sector uncertainty: the covariance of the solved parameters ---------------------- */
 /* lk_parameter_uncertainty gives every sector the standard deviation of each solved parameter: one evaluation at the
