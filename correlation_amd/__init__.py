@@ -20,6 +20,9 @@ from ._ffi import (UNC_BAD_RECORD, UNC_OK, UNC_OUT_OF_IMAGE, UNC_SINGULAR, UNC_S
                    UNCERTAINTY_DTYPE, uncertainty_from_sums)
 from ._ffi import (ERROR_OUTLIER, OUTLIER_DEGENERATE, OUTLIER_DTYPE, OUTLIER_FLAGGED, OUTLIER_NOT_GOOD, OUTLIER_OK,  # noqa: F401
                    OUTLIER_TOO_FEW, outlier_from_window)
+from ._ffi import (TRACK_BAD_POINT, TRACK_DEGENERATE, TRACK_DTYPE, TRACK_INCREMENTAL, TRACK_LOST, TRACK_OK,  # noqa: F401
+                   TRACK_RECORDS_CALLER, TRACK_RECORDS_ENGINE, TRACK_RECORDS_WINDOW, TRACK_TOO_FEW, TRACK_TOTAL,
+                   gauges_from_tracks, track_step)
 from .engine import HipCorrelationEngine, LkError  # noqa: F401
 from . import speckle  # noqa: F401
 from . import tracker  # noqa: F401

@@ -123,6 +123,23 @@ OUTLIER_DTYPE = np.dtype([(k, np.float32) for k in ("med_u", "med_v", "mad_u", "
                          [("neighbours", np.int32), ("status", np.int32)])
 assert OUTLIER_DTYPE.itemsize == 32
 
+# material-point tracks (include/lk_engine.h: lk_track_points)
+TRACK_OK, TRACK_TOO_FEW, TRACK_DEGENERATE, TRACK_LOST, TRACK_BAD_POINT = range(5)
+TRACK_TOTAL, TRACK_INCREMENTAL = 0, 1
+TRACK_RECORDS_CALLER, TRACK_RECORDS_ENGINE, TRACK_RECORDS_WINDOW = range(3)
+
+
+class LkTrackConfig(C.Structure):
+    _fields_ = [("radius", C.c_float), ("chi_max", C.c_float), ("min_neighbours", C.c_int), ("tensor", C.c_int),
+                ("mode", C.c_int), ("source", C.c_int)]
+
+
+# lk_track as a numpy record
+TRACK_DTYPE = np.dtype([(k, np.float32) for k in ("x", "y", "u", "v", "ux", "uy", "vx", "vy", "exx", "eyy", "exy", "e1", "e2",
+                                                  "theta")] +
+                       [("neighbours", np.int32), ("status", np.int32)])
+assert TRACK_DTYPE.itemsize == 64
+
 # layout of lk_result == CorrelationResult (domains.hpp:110-118), 48 bytes
 RESULT_DTYPE = np.dtype([("p", np.float32, (6,)), ("chi", np.float32),
                          ("n_points", np.int32), ("iterations", np.int32),
@@ -205,6 +222,9 @@ SYMBOLS = {
     "lk_uncertainty_from_sums": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P]),
     "lk_flag_outliers": (C.c_int, [_P, C.POINTER(LkOutlierConfig), _P, _P, _P, _I]),
     "lk_outlier_from_window": (C.c_int, [C.c_int, _F, _F, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "lk_track_points": (C.c_int, [_P, C.POINTER(LkTrackConfig), C.c_int, _F, C.c_int, _P, _P, _P]),
+    "lk_track_step": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
+    "lk_gauges_from_tracks": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, _F]),
     "lk_evaluate": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_evaluate_backward": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_compose_inverse": (C.c_int, [C.c_int, _F, _F, _F]),
@@ -376,3 +396,35 @@ def outlier_from_window(e_u, e_v, es_u, es_v, eps, threshold):
                                            out.ctypes.data_as(_P)) != 0:
         raise ValueError("lk_outlier_from_window: an empty window, a value that is not finite, or eps / threshold <= 0")
     return out[0]
+
+
+def track_step(mode, min_neighbours, n, sums11, state8, tensor=STRAIN_GREEN_LAGRANGE):
+    """lk_track_step (host, the kernel's per-frame function): the window's count n and 11 sums and the state
+    {X, Y, x, y, Fxx, Fxy, Fyx, Fyy} -> (the TRACK_DTYPE record, the new state as float64 [8])."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.ascontiguousarray(sums11, np.float64).reshape(11)
+    st = np.array(state8, np.float64).reshape(8)
+    out = np.zeros(1, TRACK_DTYPE)
+    if _compose_lib.lk_track_step(int(mode), int(min_neighbours), int(n), s.ctypes.data_as(_P), st.ctypes.data_as(_P),
+                                  int(tensor), out.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_track_step: n < 0, min_neighbours < 3, or an unknown mode or tensor")
+    return out[0], st
+
+
+def gauges_from_tracks(tracks, pairs):
+    """lk_gauges_from_tracks (host): tracks [F][Q] (TRACK_DTYPE) and pairs [G][2] of point indices -> float32 [F][G][4] =
+    length, engineering strain, logarithmic strain, rotation of the segment in radians."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    t = np.ascontiguousarray(tracks, TRACK_DTYPE)
+    if t.ndim != 2:
+        raise ValueError("lk_gauges_from_tracks: tracks must be [n_frames][n_points]")
+    ij = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    out = np.zeros((t.shape[0], len(ij), 4), np.float32)
+    if _compose_lib.lk_gauges_from_tracks(t.shape[0], t.shape[1], t.ctypes.data_as(_P), len(ij), ij.ctypes.data_as(_P),
+                                          fptr(out)) != 0:
+        raise ValueError("lk_gauges_from_tracks: no frames, points or gauges, or a pair index outside the points")
+    return out

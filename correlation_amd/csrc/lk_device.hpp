@@ -300,6 +300,17 @@ struct LkStrainArgs {
   double radius;
 };
 
+// Material-point tracks (lk_track.hip, include/lk_engine.h: lk_track_points): the windowed plane fit of lk_strain_field at the
+// points' own positions, frame after frame of one call, on the recovery pass's cell grid.
+struct LkTrackArgs {
+  LkReseedGrid grid;     // over the centres: the same in every frame of the call
+  const float4 *pack;    // [F][S] {cx, cy, u, v} of a good sector, cx = NaN for one that is not (lk_track_prep_kernel)
+  double *state;         // [Q][8] {X, Y, x, y, Fxx, Fxy, Fyx, Fyy}: read before frame 0, written after the last frame
+  lk_track *out;         // [F][Q]
+  int n_points, n_frames, n_sectors, min_neighbours, tensor, mode;
+  double radius;
+};
+
 // Outlier flags (lk_outlier.hip, include/lk_engine.h: lk_flag_outliers): one pass of the (detrended) normalised median test.
 struct LkOutlierArgs {
   LkReseedGrid grid;

@@ -296,10 +296,12 @@ struct lk_engine {
   bool stats_valid = false;
   lk_stats stats{};
   int records_S = 0;        // sectors the engine-held records of a batch solve cover (0: no solve since the commit)
+  int window_S = 0;         // sectors the device records of the last window cover (0: no window since the commit; lk_track_points)
   void *reseed = nullptr;   // lk_reseed.cpp's buffers (lk_reseed_failed / lk_reseed_plan), released by lk_destroy
   void *strain = nullptr;   // lk_strain.cpp's buffers (lk_strain_field), released by lk_destroy
   void *uncertainty = nullptr; // lk_uncertainty.cpp's buffers (lk_parameter_uncertainty), released by lk_destroy
   void *outlier = nullptr;  // lk_outlier.cpp's buffers (lk_flag_outliers), released by lk_destroy
+  void *track = nullptr;    // lk_track.cpp's buffers (lk_track_points), released by lk_destroy
 
   int fail(int code, const std::string &what) {
     err = what;
@@ -372,6 +374,8 @@ void lk_destroy(lk_engine *e) {
   e->uncertainty = nullptr;
   lk_internal_outlier_release(e->outlier);
   e->outlier = nullptr;
+  lk_internal_track_release(e->track);
+  e->track = nullptr;
   for (auto &im : e->img)
     for (auto &p : im.lvl)
       if (p)
@@ -1584,8 +1588,10 @@ static int commit_impl(lk_engine *e, bool keep_state) {
     e->eval_cap = std::atoi(f);
   HIPCHK(e->d_scratch.ensure(64));
   e->S = S;
-  if (!keep_state)
+  if (!keep_state) {
     e->records_S = 0;
+    e->window_S = 0;
+  }
   e->committed = true;
   e->lv_dirty = true;
   e->stats_valid = false;
@@ -2999,6 +3005,35 @@ int lk_internal_outlier_view(lk_engine *e, int need_records, LkOutlierView *v) {
 }
 void **lk_internal_outlier_slot(lk_engine *e) { return &e->outlier; }
 
+int lk_internal_track_view(lk_engine *e, int source, LkTrackView *v) {
+  if (!e->committed || e->S <= 0)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: no committed sectors (call lk_commit_sectors)");
+  if (source == LK_TRACK_RECORDS_ENGINE) {
+    if (e->results_pending)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: the outstanding solve has not been waited for (lk_wait_results)");
+    if (e->seq.outstanding)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: a sequence window is outstanding (lk_wait_sequence)");
+    if (e->records_S != e->S)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: no solve of the committed sectors yet (lk_correlate_all*); pass records");
+  } else if (source == LK_TRACK_RECORDS_WINDOW) {
+    if (e->seq.outstanding)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: the sequence window is outstanding (lk_wait_sequence)");
+    if (!e->d_seq_result.p || e->seq.n_frames < 1 || e->window_S != e->S || e->d_seq_result.n < (size_t)e->seq.n_frames * (size_t)e->S)
+      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: no window of the committed sectors was solved (lk_correlate_sequence_async)");
+  }
+  HIPCHK(hipSetDevice(e->cfg.device));
+  // (as lk_internal_strain_view: a pending rebuild of the lists stays pending)
+  v->stream = e->stream;
+  v->S = e->S;
+  v->model = e->cfg.fitting_model;
+  v->center = e->d_center.p;
+  v->result = e->d_result.p;
+  v->window = source == LK_TRACK_RECORDS_WINDOW ? e->d_seq_result.p : nullptr;
+  v->window_frames = source == LK_TRACK_RECORDS_WINDOW ? e->seq.n_frames : 0;
+  return LK_ERROR_NONE;
+}
+void **lk_internal_track_slot(lk_engine *e) { return &e->track; }
+
 extern "C" {
 
 int lk_get_results_device(lk_engine *e, const void **d_records) {
@@ -3526,6 +3561,7 @@ int lk_correlate_sequence_async(lk_engine *e, int und_slot, int first_slot, int 
   w.und_slot = und_slot;
   w.first_slot = first_slot;
   w.n_frames = n_frames;
+  e->window_S = e->S;
   w.reference_previous = reference_previous != 0;
   w.velocity = constant_velocity != 0;
   w.want_host = (flags & 1) != 0;

@@ -140,3 +140,23 @@ void lk_internal_outlier_release(void *state); // (lk_outlier.cpp; called by lk_
 // of its device part (bounding box with its round trip, grid kernels, prep, every pass, the mark), the lane group, the LDS
 // rows a lane may stash and the expected members of a sector's 3 x 3 cells.
 extern "C" int lk_internal_outlier_last(lk_engine *e, float *device_ms, int *group, int *lds_rows, double *members);
+
+// ---- material-point tracks (lk_track.cpp) ----------------------------------------------------------------------------------
+// What lk_track_points needs of the engine: read-only, lk_internal_strain_view's rules (a pending rebuild of the lists keeps
+// waiting).  source: LK_TRACK_RECORDS_CALLER needs committed sectors only; _ENGINE the records of a finished batch solve
+// (`result`); _WINDOW a window that has been waited for (`window`, [window_frames][S], read in place).
+struct LkTrackView {
+  hipStream_t stream;
+  int S, model;
+  const float2 *center;    // [S]
+  const lk_result *result; // [S] the engine-held records
+  const lk_result *window; // [window_frames][S] the device records of the last window (source WINDOW, else null)
+  int window_frames;
+};
+int lk_internal_track_view(lk_engine *e, int source, LkTrackView *v);
+void **lk_internal_track_slot(lk_engine *e);
+void lk_internal_track_release(void *state); // (lk_track.cpp; called by lk_destroy)
+// Bench hook (scripts/track_bench.py; exported, not part of include/*.h): of the last lk_track_points, the HIP-event time of
+// its device part (bounding box with its round trip, grid kernels, prep, the track kernel), the lane group that ran and the
+// expected members of a position's 3 x 3 cells.
+extern "C" int lk_internal_track_last(lk_engine *e, float *device_ms, int *group, double *members);

@@ -112,3 +112,11 @@ hipError_t lk_launch_outlier_exclude(const lk_outlier *flags, const float2 *cent
 hipError_t lk_launch_outlier(const LkOutlierArgs &a, int group, hipStream_t st);
 // errorCode = LK_ERROR_OUTLIER in the records of the flagged sectors
 hipError_t lk_launch_outlier_mark(const lk_outlier *flags, int n_sectors, lk_result *rec, hipStream_t st);
+
+// ---- lk_track.hip: material-point tracks (lk_track_points)
+// pack[f * S + s] = {cx, cy, u, v} of record f * S + s by the shared good rule (cx = NaN for a sector that is not good;
+// v = 0 without one), for the n_frames * n_sectors records of a call
+hipError_t lk_launch_track_prep(const lk_result *rec, const float2 *center, int n_sectors, int n_frames, int model, float chi_max,
+                                float4 *pack, hipStream_t st);
+// every point through every frame in one launch; group: 16 or 64 lanes per point
+hipError_t lk_launch_track(const LkTrackArgs &a, int group, hipStream_t st);

@@ -31,6 +31,7 @@ class HipCorrelationEngine:
         self.cfg = LkConfig(interpolation, fitting_model, precision, max_iters, py_start, py_step,
                             py_stop, device)
         self.n_params = _ffi.N_PARAMS[fitting_model]
+        self._seq_frames = 0   # frames of the last window this object launched (correlate_sequence_async)
         self._h = C.c_void_p()
         rc = self.lib.lk_create(C.byref(self.cfg), C.byref(self._h))
         if rc != 0:
@@ -425,6 +426,56 @@ class HipCorrelationEngine:
     def outlier_from_window(e_u, e_v, es_u, es_v, eps, threshold):
         """lk_outlier_from_window: the kernel's selection and ratio arithmetic on the host (no engine needed)."""
         return _ffi.outlier_from_window(e_u, e_v, es_u, es_v, eps, threshold)
+
+    # ---- material-point tracks: chosen points carried through a solved sequence --------------------------
+    def track_points(self, points, radius, n_frames=None, records=None, mode=_ffi.TRACK_TOTAL, source=None, state=None,
+                     chi_max=0.0, min_neighbours=3, tensor=_ffi.STRAIN_GREEN_LAGRANGE):
+        """lk_track_points: (TRACK_DTYPE array [F][Q], state float64 [Q][8]).  points [Q][2] start fresh; points None
+        continues from `state` (the second value of an earlier call).  source None: TRACK_RECORDS_CALLER when records
+        [F][S] are given, else TRACK_RECORDS_ENGINE (the last batch solve, one frame); TRACK_RECORDS_WINDOW reads the device
+        records of the last waited-for window in place.  No engine state changes."""
+        if source is None:
+            source = _ffi.TRACK_RECORDS_CALLER if records is not None else _ffi.TRACK_RECORDS_ENGINE
+        S = self.n_sectors
+        rec = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(-1, S)
+            if n_frames is None:
+                n_frames = rec.shape[0]
+            elif int(n_frames) > rec.shape[0]:
+                raise ValueError("track_points: fewer frames of records than n_frames")
+        elif source == _ffi.TRACK_RECORDS_WINDOW and not n_frames:
+            # (0 / None: the window's own frame count, which sizes the output; with no window launched by this object the
+            # library is asked for 0 frames, refuses for want of a window and writes nothing)
+            n_frames = self._seq_frames
+            if n_frames == 0 and self.lib.lk_get_sequence_results_device(self._h, None, None) == 0:
+                raise ValueError("track_points: a window this object did not launch is held; pass its n_frames")
+        elif n_frames is None:
+            n_frames = 1
+        pts = None
+        if points is not None:
+            pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+            st = np.zeros((len(pts), 8), np.float64)
+        elif state is None:
+            raise ValueError("track_points: neither points nor a state to continue from")
+        else:
+            st = np.array(state, np.float64).reshape(-1, 8)
+        cfg = _ffi.LkTrackConfig(float(radius), float(chi_max), int(min_neighbours), int(tensor), int(mode), int(source))
+        out = np.zeros((max(int(n_frames), 0), len(st)), _ffi.TRACK_DTYPE)
+        self._chk(self.lib.lk_track_points(self._h, C.byref(cfg), len(st), _ffi.fptr(pts) if pts is not None else None,
+                                           int(n_frames), rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
+                                           st.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out, st
+
+    @staticmethod
+    def track_step(mode, min_neighbours, n, sums11, state8, tensor=_ffi.STRAIN_GREEN_LAGRANGE):
+        """lk_track_step: the kernel's per-frame function on the host (no engine needed)."""
+        return _ffi.track_step(mode, min_neighbours, n, sums11, state8, tensor)
+
+    @staticmethod
+    def gauges_from_tracks(tracks, pairs):
+        """lk_gauges_from_tracks: virtual extensometers between tracked points (host, no engine needed)."""
+        return _ffi.gauges_from_tracks(tracks, pairs)
 
     # ---- stand-alone pieces -------------------------------------------------------------
     def evaluate(self, sector, level, p):

@@ -713,6 +713,117 @@ int lk_parameter_uncertainty(lk_engine *e, const lk_uncertainty_config *cfg, con
  * null pointer. */
 int lk_uncertainty_from_sums(int model, int n, const double *sums28, int level, lk_uncertainty *out);
 
+/* ---- material-point tracks: chosen points carried through a solved sequence ---------------- */
+/* lk_track_points answers what a sequence is usually recorded for: where a chosen material point is in every frame, how much
+ * it has strained since the reference configuration, and (lk_gauges_from_tracks) how far apart two such points are - the
+ * virtual extensometer.  Per frame and point it is lk_strain_field's windowed least-squares plane of the good sectors, taken
+ * around the point's own position instead of a sector centre, and composed from frame to frame (csrc/lk_track.hip,
+ * DESIGN.md section 18).
+ *   data      of a sector: position = the engine's committed centre c (lk_get_sector_info), the same in every frame of the
+ *             call; displacement u = p[0] and v = p[1], v = 0 for LK_FM_U.  The record's gradient parameters are not used.
+ *   good      the shared rule of the recovery pass and the strain field (one device function): LK_ERROR_NONE, finite
+ *             parameters (the model's P), finite chi and, if chi_max > 0, chi <= chi_max; evaluated once per (frame, sector).
+ *   records   source = LK_TRACK_RECORDS_CALLER: `records` is host [n_frames][S].  _ENGINE: records == NULL and n_frames == 1;
+ *             the engine-held records of the last finished batch solve are read.  _WINDOW: records == NULL; the device records
+ *             of the last window that was waited for (lk_wait_sequence) are read where lk_get_sequence_results_device shows
+ *             them, without a host copy; n_frames is 0 or that window's frame count.  A solve or window that is still in
+ *             flight, or that does not exist - a window solved before the last lk_commit_sectors does not - is refused.
+ *   window    of a point at position x in frame f: every good sector j of frame f with dx^2 + dy^2 <= r^2, where
+ *             (dx, dy) = c_j - x is formed in double from the float centre and the double position and r = (double)radius.
+ *             Each product and each sum is rounded to double (no fused multiply-add).  n = the number of such sectors; there
+ *             is no "sector itself".
+ *   fit       lk_strain_field's `fit` paragraph, all in double, in the window's coordinates x = dx, y = dy: the sums Sx, Sy,
+ *             Sxx, Sxy, Syy, Su, Sxu, Syu, Sv, Sxv, Syv; the centred moments Cxx = Sxx - Sx Sx / n, Cxy = Sxy - Sx Sy / n,
+ *             Cyy = Syy - Sy Sy / n, Cxu = Sxu - Sx Su / n, Cyu = Syu - Sy Su / n, Cxv, Cyv alike; D = Cxx Cyy - Cxy Cxy;
+ *               gux = (Cyy Cxu - Cxy Cyu) / D,  guy = (Cxx Cyu - Cxy Cxu) / D,  gvx, gvy by the same formulas from Cxv, Cyv;
+ *               du = Su / n - gux (Sx / n) - guy (Sy / n)  (the plane at the position),  dv alike.
+ *             There is no residual pass.
+ *   degenerate lk_strain_field's rule, Cxx Cyy == 0 or D <= 1e-6 Cxx Cyy, and in addition Cxx <= 2^-40 Sxx or
+ *             Cyy <= 2^-40 Syy.  At a sector centre a row or column of centres has dy or dx exactly 0 and the first rule
+ *             fires; seen from a position off the lattice (a point beyond the edge of the domain sees one row) the same
+ *             window has Cyy = Syy - Sy Sy / n of the order of 1e-16 Syy - the rounding of the sums, whose sign and size
+ *             depend on their order - and D and Cxx Cyy both scale with it.  A centred moment below 2^-40 of its raw sum is
+ *             that rounding, not a spread of the centres (a real spread of one pitch in a window of r pitches and n sectors
+ *             is about (1 / r)^2 / n of the raw sum).
+ *   step      LK_TRACK_TOTAL (every frame's records are displacements from the reference configuration): the fit is centred
+ *             at the reference position (X, Y) in every frame; x_f = X + du, y_f = Y + dv, F_f = I + g.  The frames are
+ *             independent of each other.
+ *             LK_TRACK_INCREMENTAL (frame f's records are displacements from frame f - 1, a reference_previous window, the
+ *             sectors staying where they are): the fit is centred at x_{f-1}, with x_{-1} = X; x_f = x_{f-1} + (du, dv);
+ *             F_f = (I + g) F_{f-1} with F_{-1} = I, each product and each sum rounded to double.
+ *             Position and F are carried in double from frame to frame; each output is rounded to float once per frame:
+ *             x, y; u = (float)(x - X), v alike; ux = (float)(Fxx - 1), uy = (float)Fxy, vx = (float)Fyx,
+ *             vy = (float)(Fyy - 1); the six tensor fields are lk_strain_from_gradient of those four floats, so `tensor`
+ *             is that of the TOTAL gradient in both modes.
+ *   status    checked in this order: BAD_POINT  X or Y is not finite (every frame of the point);  LOST  INCREMENTAL only: an
+ *             earlier frame of this point was not OK, or the state passed in is not finite;  TOO_FEW  n < min_neighbours;
+ *             DEGENERATE  the `degenerate` paragraph;  OK.  For every status but OK the float fields are 0 and
+ *             neighbours = n, with n = 0 for BAD_POINT and LOST (no window is formed).  In TOTAL mode a failed frame does not
+ *             affect the next one.
+ *   state     state_inout, if not NULL, is [n_points][8] doubles {X, Y, x, y, Fxx, Fxy, Fyx, Fyy}.  With points_xy
+ *             ([n_points][2] floats, the reference positions) the call starts fresh from {X, Y, X, Y, 1, 0, 0, 1} and the
+ *             state is output only; with points_xy == NULL it continues from the state; passing neither is an error.  On
+ *             return it holds the state after the last frame; a frame that is not OK leaves x, y and F as NaN (X, Y stay),
+ *             which is what makes the rest of an INCREMENTAL chain LOST.  Two calls on frames 0 .. k - 1 and k .. F - 1, the
+ *             second continuing from the first's state, give the same bytes as one call on 0 .. F - 1: this is how a
+ *             sequence longer than one window is tracked.
+ *   order     fixed, as for lk_strain_field: the candidates are the members of the 3 x 3 cells around the position's cell
+ *             of a grid of cell size `radius` over the centres (rows iy - 1, iy, iy + 1, each from ix - 1 to ix + 1), by
+ *             ascending sector index within a cell, dealt to the lanes of a group (16 or 64, chosen from the sector count and
+ *             the number of cells - not from the points) in turn and summed by a fixed butterfly.  The position's cell is
+ *             floor((x - x0) / cell) as for a centre, clamped to [-2, nx + 1] and [-2, ny + 1]: one cell beyond the grid
+ *             (-1, nx) the range still reaches the grid's edge cells; farther out (-2, nx + 1: more than `radius` from every
+ *             centre) there are no candidates and nothing is walked.  A point's records depend on that point, the centres, the records and the configuration only - not
+ *             on the other points of the call or on their count.  A float64 restatement reproduces them up to the order of
+ *             the double sums.
+ *   modes     allowed in every mode, reference-order mode included: the call writes nothing of the engine's - records,
+ *             guesses, last parameters, counters and lk_get_reseed_info stay byte for byte - and, as for lk_strain_field, a
+ *             rebuild of the sample lists that waits for the next solve keeps waiting.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message, `out` untouched: null configuration or output; no committed sectors;
+ *             n_points < 1; n_frames < 1 where a frame count is required (CALLER, ENGINE); radius not finite or <= 0; chi_max
+ *             not finite; min_neighbours < 3; unknown tensor, mode or source; neither points_xy nor state_inout; CALLER
+ *             without records; ENGINE or WINDOW with records; ENGINE with n_frames != 1, before any batch solve or with one
+ *             in flight; WINDOW with an n_frames that is neither 0 nor the window's, before any window or with one in flight.
+ *   scope     one engine.  lk_group, lk_tracker, the report CSV and the CudaClass adapter do not call it.  No weights inside
+ *             the window, no quadratic fit.  The cell grid assumes the centres of the call: a Lagrangian sequence whose
+ *             sectors move between frames is tracked with one call per frame, continuing from the state. */
+enum { LK_TRACK_OK = 0, LK_TRACK_TOO_FEW = 1, LK_TRACK_DEGENERATE = 2, LK_TRACK_LOST = 3, LK_TRACK_BAD_POINT = 4 };
+enum { LK_TRACK_TOTAL = 0, LK_TRACK_INCREMENTAL = 1 };
+enum { LK_TRACK_RECORDS_CALLER = 0, LK_TRACK_RECORDS_ENGINE = 1, LK_TRACK_RECORDS_WINDOW = 2 };
+typedef struct lk_track_config {
+  float radius;        /* window: good sectors whose centre lies within this many level-0 pixels of the point (<=, in double) */
+  float chi_max;       /* the shared good rule; <= 0: the error code alone decides */
+  int min_neighbours;  /* >= 3 */
+  int tensor;          /* LK_STRAIN_GREEN_LAGRANGE / LK_STRAIN_SMALL, of the TOTAL gradient */
+  int mode;            /* LK_TRACK_TOTAL: every frame's records are displacements from the reference configuration;
+                          LK_TRACK_INCREMENTAL: frame f's records are displacements from frame f - 1 (reference_previous) */
+  int source;          /* LK_TRACK_RECORDS_* */
+} lk_track_config;
+typedef struct lk_track {   /* 64 bytes, one per (frame, point), frame-major */
+  float x, y;               /* the point in frame f, level-0 pixels */
+  float u, v;               /* x - X, y - Y */
+  float ux, uy, vx, vy;     /* total displacement gradient F - I */
+  float exx, eyy, exy, e1, e2, theta;   /* lk_strain_from_gradient of the four floats above */
+  int32_t neighbours, status;
+} lk_track;
+/* points_xy: [n_points][2] or NULL; records: host [n_frames][S] or NULL (see `records`); state_inout: [n_points][8] doubles or
+ * NULL; out: [n_frames][n_points] (source WINDOW with n_frames = 0: the window's frame count).  Synchronous.  Changes no
+ * engine state. */
+int lk_track_points(lk_engine *e, const lk_track_config *cfg, int n_points, const float *points_xy,
+                    int n_frames, const lk_result *records, double *state_inout, lk_track *out);
+/* the kernel's own per-frame function compiled for the host (csrc/lk_track.hpp): n and the 11 sums of the `fit` paragraph, in
+ * its order, of the window around the position the mode centres the fit at, and the state {X, Y, x, y, Fxx, Fxy, Fyx, Fyy}
+ * -> the new state (in place) and the record.  LK_ERROR_BAD_DOMAIN for a null pointer, n < 0, min_neighbours < 3 or an
+ * unknown mode or tensor. */
+int lk_track_step(int mode, int min_neighbours, int n, const double *sums11, double *state8, int tensor, lk_track *out);
+/* virtual extensometers, host only, in double: per frame f and gauge g = (i, j) = pairs_ij[2 g], pairs_ij[2 g + 1] the four
+ * floats out4[(f * n_gauges + g) * 4 ..]: the length L of the segment between the float positions of points i and j; the
+ * engineering strain (L - L0) / L0, with L0 the length between the reference positions (x - u, y - v); the logarithmic strain
+ * ln(L / L0); the rotation of the segment against its reference direction in radians (atan2 of the cross and the dot
+ * product).  All four are 0 when either end is not LK_TRACK_OK in that frame or L0 = 0.  LK_ERROR_BAD_DOMAIN for a null
+ * pointer, n_frames, n_points or n_gauges < 1, or a pair index outside 0 .. n_points - 1 (out4 untouched). */
+int lk_gauges_from_tracks(int n_frames, int n_points, const lk_track *tracks, int n_gauges, const int32_t *pairs_ij, float *out4);
+
 /* ---- stand-alone pieces (known-answer tests, same kernels as the batch path) ------- */
 /* one evaluation of one sector at one level: raw sums A (6x6 row-major, upper valid),
  * b, chi (unscaled), error flag (apply_model_and_interpolate, correlation_class.cpp:131) */
