@@ -140,6 +140,28 @@ TRACK_DTYPE = np.dtype([(k, np.float32) for k in ("x", "y", "u", "v", "ux", "uy"
                        [("neighbours", np.int32), ("status", np.int32)])
 assert TRACK_DTYPE.itemsize == 64
 
+# photometry and the residual map (include/lk_engine.h: lk_photometry, lk_residual_map)
+PHOTO_OK, PHOTO_BAD_RECORD, PHOTO_OUT_OF_IMAGE, PHOTO_TOO_FEW, PHOTO_FLAT = range(5)
+PHOTO_SUMS = 8   # doubles per sector: sum f, sum g, sum f^2, sum g^2, sum f g, sum V^2, flagged samples, max |V|
+MAP_NO_OWNER = -1   # owner map: no good sector within the radius; -2 - s: sector s owns the pixel, the sampler flagged it
+
+
+class LkPhotometryConfig(C.Structure):
+    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("reserved", C.c_int * 2)]
+
+
+class LkResidualMapConfig(C.Structure):
+    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("radius", C.c_float), ("x0", C.c_int), ("y0", C.c_int),
+                ("w", C.c_int), ("h", C.c_int), ("reserved", C.c_int)]
+
+
+# struct lk_photometry as a numpy record
+PHOTOMETRY_DTYPE = np.dtype([("n_points", np.int32), ("status", np.int32)] +
+                            [(k, np.float32) for k in ("mean_f", "mean_g", "std_f", "std_g", "zncc", "gain", "offset", "rms",
+                                                       "rms_zn", "znssd", "max_abs")] +
+                            [("reserved", np.int32, (3,))])
+assert PHOTOMETRY_DTYPE.itemsize == 64 and C.sizeof(LkPhotometryConfig) == 16 and C.sizeof(LkResidualMapConfig) == 32
+
 # layout of lk_result == CorrelationResult (domains.hpp:110-118), 48 bytes
 RESULT_DTYPE = np.dtype([("p", np.float32, (6,)), ("chi", np.float32),
                          ("n_points", np.int32), ("iterations", np.int32),
@@ -225,6 +247,10 @@ SYMBOLS = {
     "lk_track_points": (C.c_int, [_P, C.POINTER(LkTrackConfig), C.c_int, _F, C.c_int, _P, _P, _P]),
     "lk_track_step": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
     "lk_gauges_from_tracks": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, _F]),
+    "lk_photometry": (C.c_int, [_P, C.POINTER(LkPhotometryConfig), _P, _P, _P]),
+    "lk_photometry_from_sums": (C.c_int, [C.c_int, _P, _P]),
+    "lk_residual_map": (C.c_int, [_P, C.POINTER(LkResidualMapConfig), _P, _P, _P, _P]),
+    "lk_map_owner": (C.c_int, [C.c_int, _F, _P, C.c_double, C.c_double, C.c_double]),
     "lk_evaluate": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_evaluate_backward": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_compose_inverse": (C.c_int, [C.c_int, _F, _F, _F]),
@@ -396,6 +422,39 @@ def outlier_from_window(e_u, e_v, es_u, es_v, eps, threshold):
                                            out.ctypes.data_as(_P)) != 0:
         raise ValueError("lk_outlier_from_window: an empty window, a value that is not finite, or eps / threshold <= 0")
     return out[0]
+
+
+def photometry_from_sums(n, sums8):
+    """lk_photometry_from_sums (host, the kernel's function): the PHOTOMETRY_DTYPE record of one sector of n samples whose
+    eight sums are sums8 (sum f, sum g, sum f^2, sum g^2, sum f g, sum V^2, flagged samples, max |V|)."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.ascontiguousarray(sums8, np.float64).reshape(PHOTO_SUMS)
+    out = np.zeros(1, PHOTOMETRY_DTYPE)
+    if _compose_lib.lk_photometry_from_sums(int(n), s.ctypes.data_as(_P), out.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_photometry_from_sums: n < 0")
+    return out[0]
+
+
+def map_owner(centers, X, Y, radius, good=None):
+    """lk_map_owner (host, the residual map's owner rule by brute force): the index of the good sector whose centre
+    (centers [n][2], level-0 pixels) is nearest to the level-0 position (X, Y) within `radius`, ties to the lowest index;
+    -1 without one."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    c = np.ascontiguousarray(centers, np.float32).reshape(-1, 2)
+    g = None
+    if good is not None:
+        g = np.ascontiguousarray(good, np.uint8).reshape(-1)
+        if len(g) != len(c):
+            raise ValueError("lk_map_owner: good and centers differ in length")
+    r = _compose_lib.lk_map_owner(len(c), fptr(c), g.ctypes.data_as(_P) if g is not None else None, float(X), float(Y),
+                                  float(radius))
+    if r < -1:
+        raise ValueError("lk_map_owner: the radius must be finite and positive")
+    return r
 
 
 def track_step(mode, min_neighbours, n, sums11, state8, tensor=STRAIN_GREEN_LAGRANGE):

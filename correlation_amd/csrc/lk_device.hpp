@@ -341,3 +341,42 @@ struct LkUncertaintyArgs {
   double *sums;             // [S][28] or null: A (upper triangle, row-major), b, chi in the layout of Sums<P>, then zeros
   int n_sectors, level;
 };
+
+// Photometry (lk_residual.hip, include/lk_engine.h: lk_photometry): one evaluation of every good sector at its record's
+// parameters, at pyramid level `level` - LkUncertaintyArgs's walk with the grey-value sums instead of the normal matrix.
+struct LkPhotometryArgs {
+  const uint8_t *und, *def; // level-L images, pitch == cols
+  int urows, ucols, drows, dcols;
+  const float2 *xy;         // level-L lists in the reference's order, [S+1] offsets, [S] implicit rectangles
+  const uint32_t *off;
+  const int4 *rect;
+  const float2 *center;     // [S] level-0 centres
+  const lk_result *rec;     // [S]
+  const uint32_t *order;    // [n_sectors] the sectors of this launch (one lane group's)
+  struct lk_photometry *out; // [S]
+  double *sums;             // [S][8] or null (lk_residual.hpp: kLkPhotoSums)
+  int n_sectors, level;
+  float chi_max;
+};
+
+// Residual map (lk_residual.hip, include/lk_engine.h: lk_residual_map): what a pixel needs of a sector, 48 bytes.
+struct LkMapSector {
+  float cx0, cy0; // level-0 centre; cx0 = NaN for a sector that is not good (it then fails the distance test by itself)
+  float cx, cy;   // level-L centre, as the solve scales it
+  float p[6];     // level-L parameters (translate<>), zeros behind the model's P
+  float pad[2];
+};
+struct LkResidualMapArgs {
+  LkReseedGrid grid;         // over the level-0 centres, cell = radius
+  const uint8_t *und, *def;  // level-L images, pitch == cols
+  int urows, ucols, drows, dcols;
+  const LkMapSector *pack;   // [S]
+  float *warped, *residual;  // [h][w] of the window, each may be null
+  int32_t *owner;
+  uint32_t *fallback;        // [1] tiles whose candidates did not fit into LDS (zeroed before the launch)
+  int n_sectors, level;
+  int x0, y0, w, h;          // the window in level-L pixels, inside the undeformed image
+  int tiles_x;
+  double r2;                 // (double)radius squared
+};
+constexpr int kLkMapTileW = 32, kLkMapTileH = 8; // pixels per workgroup: x fastest, a wavefront covers two rows of 32

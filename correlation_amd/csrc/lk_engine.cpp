@@ -302,6 +302,7 @@ struct lk_engine {
   void *uncertainty = nullptr; // lk_uncertainty.cpp's buffers (lk_parameter_uncertainty), released by lk_destroy
   void *outlier = nullptr;  // lk_outlier.cpp's buffers (lk_flag_outliers), released by lk_destroy
   void *track = nullptr;    // lk_track.cpp's buffers (lk_track_points), released by lk_destroy
+  void *residual = nullptr; // lk_residual.cpp's buffers (lk_photometry, lk_residual_map), released by lk_destroy
 
   int fail(int code, const std::string &what) {
     err = what;
@@ -376,6 +377,8 @@ void lk_destroy(lk_engine *e) {
   e->outlier = nullptr;
   lk_internal_track_release(e->track);
   e->track = nullptr;
+  lk_internal_residual_release(e->residual);
+  e->residual = nullptr;
   for (auto &im : e->img)
     for (auto &p : im.lvl)
       if (p)
@@ -3033,6 +3036,7 @@ int lk_internal_track_view(lk_engine *e, int source, LkTrackView *v) {
   return LK_ERROR_NONE;
 }
 void **lk_internal_track_slot(lk_engine *e) { return &e->track; }
+void **lk_internal_residual_slot(lk_engine *e) { return &e->residual; }
 
 extern "C" {
 

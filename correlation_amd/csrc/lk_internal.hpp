@@ -160,3 +160,14 @@ void lk_internal_track_release(void *state); // (lk_track.cpp; called by lk_dest
 // its device part (bounding box with its round trip, grid kernels, prep, the track kernel), the lane group that ran and the
 // expected members of a position's 3 x 3 cells.
 extern "C" int lk_internal_track_last(lk_engine *e, float *device_ms, int *group, double *members);
+
+// ---- photometry and the residual map (lk_residual.cpp) ------------------------------------------------------------------------
+// Both passes read the engine through lk_internal_uncertainty_view (the same level-L images, lists, rectangles, centres,
+// records and ring slot); their buffers hang on a slot of their own.
+void **lk_internal_residual_slot(lk_engine *e);
+void lk_internal_residual_release(void *state); // (lk_residual.cpp; called by lk_destroy)
+// Bench hook (scripts/residual_bench.py; exported, not part of include/*.h): of the last lk_photometry or lk_residual_map, the
+// HIP-event time of its device part (the map: bounding box with its round trip, grid kernels, prep, the map kernel), the
+// pixel tiles of a map (0 after lk_photometry) and how many of them walked global memory because their candidates did not fit
+// into LDS.
+extern "C" int lk_internal_residual_last(lk_engine *e, float *device_ms, int *tiles, int *fallback_tiles);

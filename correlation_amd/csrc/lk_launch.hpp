@@ -120,3 +120,12 @@ hipError_t lk_launch_track_prep(const lk_result *rec, const float2 *center, int 
                                 float4 *pack, hipStream_t st);
 // every point through every frame in one launch; group: 16 or 64 lanes per point
 hipError_t lk_launch_track(const LkTrackArgs &a, int group, hipStream_t st);
+
+// ---- lk_residual.hip: photometry and the residual map (lk_photometry, lk_residual_map)
+// group: 16, 64 or 512 lanes per sector (lk_bw_group of the level-0 sample count); a.order lists that group's sectors
+hipError_t lk_launch_photometry(const LkPhotometryArgs &a, int model, int interp, int group, hipStream_t st);
+// pack[s] of every sector by the shared good rule: centres of both levels, parameters at `level`
+hipError_t lk_launch_map_prep(const lk_result *rec, const float2 *center, int n_sectors, int model, int level, float chi_max,
+                              LkMapSector *pack, hipStream_t st);
+// one workgroup per tile of kLkMapTileW x kLkMapTileH pixels of the window; *n_tiles = the tiles launched
+hipError_t lk_launch_residual_map(const LkResidualMapArgs &a, int model, int interp, int *n_tiles, hipStream_t st);

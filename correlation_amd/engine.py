@@ -427,6 +427,65 @@ class HipCorrelationEngine:
         """lk_outlier_from_window: the kernel's selection and ratio arithmetic on the host (no engine needed)."""
         return _ffi.outlier_from_window(e_u, e_v, es_u, es_v, eps, threshold)
 
+    # ---- photometry and the back-warped residual map ----------------------------------------------------
+    def photometry(self, records=None, def_slot=-1, chi_max=0.0, return_sums=False):
+        """lk_photometry: a PHOTOMETRY_DTYPE array [S] (ZNCC, gain, offset, residuals of every good sector at its record's
+        parameters) from the engine-held records of the last batch solve or, records given, from those [S]; with
+        return_sums also the eight double sums of every sector [S][8].  No engine state changes."""
+        cfg = _ffi.LkPhotometryConfig(int(def_slot), float(chi_max))
+        rec = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        out = np.zeros(self.n_sectors, _ffi.PHOTOMETRY_DTYPE)
+        sums = np.zeros((self.n_sectors, _ffi.PHOTO_SUMS), np.float64) if return_sums else None
+        self._chk(self.lib.lk_photometry(self._h, C.byref(cfg), rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
+                                         out.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p) if return_sums else None))
+        return (out, sums) if return_sums else out
+
+    def residual_map(self, radius, window=None, records=None, def_slot=-1, chi_max=0.0, want=("warped", "residual", "owner")):
+        """lk_residual_map: the deformed frame pulled back into the reference configuration by the solved field, at pyramid
+        level py_start.  window = (x0, y0, w, h) in that level's pixels, None: the whole image.  Returns (warped float32 [h][w],
+        residual float32 [h][w], owner int32 [h][w]); an output not named in `want` is None.  owner: the sector, -1 without a
+        good sector within `radius` (level-0 pixels), -2 - s where sector s owns the pixel but the position left the deformed
+        image; the float maps are NaN in both cases.  No engine state changes."""
+        x0, y0, w, h = (0, 0, 0, 0) if window is None else (int(t) for t in window)
+        cfg = _ffi.LkResidualMapConfig(int(def_slot), float(chi_max), float(radius), x0, y0, w, h, 0)
+        if window is None:
+            r, c = C.c_int(), C.c_int()
+            self._chk(self.lib.lk_get_pyramid_level(self._h, _ffi.IMG_UND, self.cfg.py_start, None, C.byref(r), C.byref(c)))
+            h, w = r.value, c.value
+        rec = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        shape = (max(h, 0), max(w, 0))
+        warped = np.zeros(shape, np.float32) if "warped" in want else None
+        residual = np.zeros(shape, np.float32) if "residual" in want else None
+        owner = np.zeros(shape, np.int32) if "owner" in want else None
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self.lib.lk_residual_map(self._h, C.byref(cfg), ptr(rec), ptr(warped), ptr(residual), ptr(owner)))
+        return warped, residual, owner
+
+    def residual_last(self):
+        """Bench hook: (device ms, pixel tiles, tiles that took the global-memory fall-back) of the last photometry or
+        residual_map call."""
+        ms, tiles, fb = C.c_float(), C.c_int(), C.c_int()
+        fn = self.lib.lk_internal_residual_last
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self._chk(fn(self._h, C.byref(ms), C.byref(tiles), C.byref(fb)))
+        return ms.value, tiles.value, fb.value
+
+    @staticmethod
+    def photometry_from_sums(n, sums8):
+        """lk_photometry_from_sums: the kernel's record arithmetic on the host (no engine needed)."""
+        return _ffi.photometry_from_sums(n, sums8)
+
+    @staticmethod
+    def map_owner(centers, X, Y, radius, good=None):
+        """lk_map_owner: the residual map's owner rule on the host (no engine needed)."""
+        return _ffi.map_owner(centers, X, Y, radius, good)
+
     # ---- material-point tracks: chosen points carried through a solved sequence --------------------------
     def track_points(self, points, radius, n_frames=None, records=None, mode=_ffi.TRACK_TOTAL, source=None, state=None,
                      chi_max=0.0, min_neighbours=3, tensor=_ffi.STRAIN_GREEN_LAGRANGE):

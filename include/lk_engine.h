@@ -824,6 +824,111 @@ int lk_track_step(int mode, int min_neighbours, int n, const double *sums11, dou
  * pointer, n_frames, n_points or n_gauges < 1, or a pair index outside 0 .. n_points - 1 (out4 untouched). */
 int lk_gauges_from_tracks(int n_frames, int n_points, const lk_track *tracks, int n_gauges, const int32_t *pairs_ij, float *out4);
 
+/* ---- photometry and the back-warped residual map: the grey values once more ---------------- */
+/* chi is a plain sum of squared grey-level differences: a frame that is 20 % darker gives every sector a large chi although
+ * the match is perfect.  lk_photometry evaluates every good sector once at its record's parameters and reports the
+ * zero-mean normalised cross-correlation (ZNCC) of the two patches, the gain and offset between them and the residual that
+ * is left with and without them.  lk_residual_map pulls the deformed frame back into the reference configuration with the
+ * solved field, pixel by pixel, and subtracts the undeformed image (csrc/lk_residual.hip).
+ *   level     both passes work at L = py_start with the record's parameters brought to that level and the committed centre
+ *             times 2^-L, exactly as lk_parameter_uncertainty (`level` there).
+ *   good      the shared rule (csrc/lk_good.hpp): LK_ERROR_NONE, finite parameters (the model's P), finite chi and, if
+ *             chi_max > 0, chi <= chi_max.
+ *
+ * lk_photometry
+ *   sample    lk_parameter_uncertainty's walk and lane groups (16 / 64 / 512 lanes from the level-0 sample count; lane j
+ *             takes the samples j, j + G, ...).  Per sample, in float: f = the undeformed node, g = the deformed image at
+ *             W(x; p) by the engine's interpolation (the solve's device functions), V = f - g.
+ *   sums      eight doubles per sector: sum f, sum g, sum f^2, sum g^2, sum f g, sum V^2 - each product formed in double
+ *             from the floats (exact or rounded once, no fused multiply-add) - then the number of samples the sampler
+ *             flagged, and max |V| (a float maximum carried in a double; order-independent).  The sums are added by the
+ *             uncertainty pass's fixed butterfly, so a sector's eight numbers and its record are the same bytes in any
+ *             batch, shard or mode.  A float64 restatement reproduces the six sums up to the order of the double additions.
+ *   record    lk_photometry_from_sums (one function for the kernel and the host, csrc/lk_residual.hpp), in double without
+ *             fused multiply-add, each output rounded to float once; with N = (double)n:
+ *               mean_f = Sf / N, mean_g = Sg / N;  vf = N Sff - Sf Sf, vg = N Sgg - Sg Sg, c = N Sfg - Sf Sg;
+ *               std_f = sqrt(vf) / N, std_g = sqrt(vg) / N (population);  zncc = c / sqrt(vf vg);
+ *               gain = c / vf, offset = mean_g - gain mean_f (least squares g ~ gain f + offset);
+ *               rms = sqrt(SVV / N);  rms_zn = std_g sqrt(max(0, 1 - zncc^2)), what is left of g after gain and offset
+ *               are removed;  znssd = 2 (1 - zncc);  max_abs = max |V|.
+ *   status    checked in this order: BAD_RECORD  the record is not good (not evaluated; sums and floats 0);  OUT_OF_IMAGE
+ *             the sampler flagged a sample (sums and floats 0);  TOO_FEW  n < 2 (floats 0);  FLAT  vx <= 1e-12 N Sxx for
+ *             x = f or x = g, i.e. N sum x^2 - (sum x)^2 <= 1e-12 N sum x^2 - a scale-free rule like the uncertainty
+ *             pass's pivot rule: a patch whose variance is below 1e-12 of its mean square has no contrast to normalise
+ *             by.  mean_f, mean_g, std_f, std_g (a negative vx counts as 0), rms and max_abs are still filled; zncc, gain,
+ *             offset, rms_zn and znssd are 0.  OK otherwise.  n_points = n in every case; reserved words are 0.
+ *
+ * lk_residual_map
+ *   window    x0, y0, w, h in pixels of the level-L undeformed image; all four 0: the whole level-L image.  The three
+ *             outputs are [h][w] row-major; each may be NULL, not all three.
+ *   owner     pixel (x, y) of the level-L undeformed image has the level-0 position (X, Y) = (x 2^L, y 2^L).  Its owner is
+ *             the good sector with the smallest d2 = (X - cx)^2 + (Y - cy)^2 among those with d2 <= radius^2: the
+ *             differences are doubles formed from the float centre and the double position, each square rounded, one
+ *             rounded sum, no fused multiply-add; radius^2 is the double square of the float radius.  Equal d2 goes to the
+ *             lowest sector index.  A sector that is not good never owns a pixel.  No candidate: owner = -1.
+ *             lk_map_owner is the same rule on the host, by brute force.
+ *   values    with owner s: (xd, yd) = W((float)x, (float)y; p_s) about s's level-L centre, then the engine's
+ *             interpolation of the deformed image there - the solve's device functions, in float.  If the sampler flags
+ *             the position: owner = -2 - s, warped = residual = NaN.  Otherwise warped = that value, residual = f - warped
+ *             with f the level-L undeformed pixel, owner = s.  Pixels without an owner have NaN in both float maps.
+ *   order     nothing is summed: a pixel's three values depend on that pixel, the centres, the records and the
+ *             configuration only.  The sectors are found on the recovery pass's cell grid with cell size = radius; a tile
+ *             of pixels searches the members of the cells it can reach from LDS, or - when they do not fit - every pixel
+ *             walks its own 3 x 3 cells in global memory.  Both give the same owner: the pair (d2, index) is compared.
+ *
+ *   modes     both calls are allowed in every mode, reference-order mode included, write nothing of the engine's - records,
+ *             guesses, last parameters, counters, the strain field and the uncertainty records stay byte for byte - carry
+ *             out a rebuild of the sample lists that waits for the next solve first, as lk_parameter_uncertainty does, and
+ *             synchronise the engine's stream before they return.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message, outputs untouched: null configuration; no output; non-zero reserved
+ *             words; chi_max not finite; radius not finite or <= 0; a window that is not inside the level-L image; and
+ *             what lk_parameter_uncertainty refuses (its accessor is used, its messages carry its name): no committed
+ *             sectors; records == NULL before any batch solve of the committed sectors, or with one in flight; images not
+ *             set; a bad def_slot.
+ *   scope     one engine, the undeformed image is LK_IMG_UND.  lk_group, lk_tracker, the report CSV and the CudaClass
+ *             adapter do not call them; windows with reference_previous are not covered; the maps are host arrays; zncc
+ *             does not enter the good rule; the solve's criterion stays the plain sum of squares; no colour frames. */
+enum { LK_PHOTO_OK = 0, LK_PHOTO_BAD_RECORD = 1, LK_PHOTO_OUT_OF_IMAGE = 2, LK_PHOTO_TOO_FEW = 3, LK_PHOTO_FLAT = 4 };
+typedef struct lk_photometry_config {
+  int def_slot;      /* -1: LK_IMG_DEF; k >= 0: ring slot k, as for lk_parameter_uncertainty */
+  float chi_max;     /* the shared good rule; <= 0: the error code alone decides */
+  int reserved[2];   /* must be 0 */
+} lk_photometry_config;
+/* (the record shares its name with the function: it is a struct tag without a typedef, written `struct lk_photometry`) */
+struct lk_photometry {                    /* 64 bytes, one per sector */
+  int32_t n_points, status;
+  float mean_f, mean_g, std_f, std_g;     /* undeformed (f) and back-warped deformed (g) patch, grey levels */
+  float zncc;
+  float gain, offset;                     /* g ~ gain f + offset */
+  float rms, rms_zn;                      /* sqrt(sum V^2 / n); the same after gain and offset are removed */
+  float znssd;                            /* 2 (1 - zncc) */
+  float max_abs;                          /* max |V| */
+  int32_t reserved[3];
+};
+/* records: host [S], or NULL = the engine-held records of the last finished batch solve.  out: [S].  sums_out: [S][8]
+ * doubles or NULL.  Synchronous.  Changes no engine state. */
+int lk_photometry(lk_engine *e, const lk_photometry_config *cfg, const lk_result *records, struct lk_photometry *out,
+                  double *sums_out);
+/* the kernel's own function compiled for the host: the record of one sector of n samples with the eight sums `sums8`
+ * (status OK, TOO_FEW or FLAT; OUT_OF_IMAGE if the flagged count sums8[6] is not 0).  LK_ERROR_BAD_DOMAIN for a null
+ * pointer or n < 0. */
+int lk_photometry_from_sums(int n, const double *sums8, struct lk_photometry *out);
+typedef struct lk_residual_map_config {
+  int def_slot;      /* as lk_photometry_config */
+  float chi_max;
+  float radius;      /* level-0 pixels, finite and > 0 */
+  int x0, y0, w, h;  /* window in level-L pixels of the undeformed image; all 0: the whole level-L image */
+  int reserved;      /* must be 0 */
+} lk_residual_map_config;
+/* records: host [S] or NULL (as lk_photometry).  warped, residual, owner: host [h][w], each may be NULL (not all three).
+ * Synchronous.  Changes no engine state. */
+int lk_residual_map(lk_engine *e, const lk_residual_map_config *cfg, const lk_result *records, float *warped, float *residual,
+                    int32_t *owner);
+/* the owner rule on the host, by brute force over n centres {cx, cy} (good: [n] bytes, 0 = not good, or NULL = all good):
+ * the owner of the level-0 position (X, Y), or -1.  INT32_MIN for a null centres pointer with n > 0, n < 0 or a radius
+ * that is not finite and positive. */
+int lk_map_owner(int n, const float *centers_xy, const uint8_t *good, double X, double Y, double radius);
+
 /* ---- stand-alone pieces (known-answer tests, same kernels as the batch path) ------- */
 /* one evaluation of one sector at one level: raw sums A (6x6 row-major, upper valid),
  * b, chi (unscaled), error flag (apply_model_and_interpolate, correlation_class.cpp:131) */
