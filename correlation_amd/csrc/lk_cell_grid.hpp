@@ -1,6 +1,6 @@
 // lk_cell_grid.hpp - host side of the uniform cell grid over the sector centres (kernels: lk_reseed.hip, through
-// lk_launch_reseed_grid), shared by the recovery pass (lk_reseed.cpp) and the strain field (lk_strain.cpp): the device
-// buffers a grid needs and the rule that sizes it.
+// lk_launch_reseed_grid), shared by every pass that looks for a sector's neighbours: the device buffers a grid needs and the
+// rule that sizes it.  A part of lk_pass.hpp, which defines LkDevBytes and then includes this file: include that header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,31 +10,7 @@
 #include "lk_device.hpp"
 #include "lk_launch.hpp"
 
-struct LkDevBytes { // device memory grown on demand, never shrunk
-  void *p = nullptr;
-  size_t bytes = 0;
-  hipError_t ensure(size_t want) {
-    if (p && want <= bytes)
-      return hipSuccess;
-    if (p)
-      (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    const hipError_t err = hipMalloc(&p, std::max<size_t>(want, 16));
-    if (err == hipSuccess)
-      bytes = want;
-    return err;
-  }
-  void release() {
-    if (p)
-      (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <class T> T *as() const { return (T *)p; }
-};
-
-struct LkCellGridBufs {
+struct LkCellGridBufs { // (freed with their owner: LkDevBytes)
   LkDevBytes cell_of, start, cursor, unordered, members;
 };
 

@@ -297,12 +297,7 @@ struct lk_engine {
   lk_stats stats{};
   int records_S = 0;        // sectors the engine-held records of a batch solve cover (0: no solve since the commit)
   int window_S = 0;         // sectors the device records of the last window cover (0: no window since the commit; lk_track_points)
-  void *reseed = nullptr;   // lk_reseed.cpp's buffers (lk_reseed_failed / lk_reseed_plan), released by lk_destroy
-  void *strain = nullptr;   // lk_strain.cpp's buffers (lk_strain_field), released by lk_destroy
-  void *uncertainty = nullptr; // lk_uncertainty.cpp's buffers (lk_parameter_uncertainty), released by lk_destroy
-  void *outlier = nullptr;  // lk_outlier.cpp's buffers (lk_flag_outliers), released by lk_destroy
-  void *track = nullptr;    // lk_track.cpp's buffers (lk_track_points), released by lk_destroy
-  void *residual = nullptr; // lk_residual.cpp's buffers (lk_photometry, lk_residual_map), released by lk_destroy
+  LkPassSlot *pass[LK_PASS_COUNT] = {}; // what the add-on passes keep between their calls (lk_pass.hpp), deleted by lk_destroy
 
   int fail(int code, const std::string &what) {
     err = what;
@@ -367,18 +362,10 @@ void lk_destroy(lk_engine *e) {
     return;
   (void)hipSetDevice(e->cfg.device);
   (void)hipDeviceSynchronize();
-  lk_internal_reseed_release(e->reseed);
-  e->reseed = nullptr;
-  lk_internal_strain_release(e->strain);
-  e->strain = nullptr;
-  lk_internal_uncertainty_release(e->uncertainty);
-  e->uncertainty = nullptr;
-  lk_internal_outlier_release(e->outlier);
-  e->outlier = nullptr;
-  lk_internal_track_release(e->track);
-  e->track = nullptr;
-  lk_internal_residual_release(e->residual);
-  e->residual = nullptr;
+  for (LkPassSlot *&p : e->pass) {
+    delete p;
+    p = nullptr;
+  }
   for (auto &im : e->img)
     for (auto &p : im.lvl)
       if (p)
@@ -2789,6 +2776,26 @@ int lk_internal_guess_search_matches(lk_engine *e, lk_guess_match **d_match, hip
   return LK_ERROR_NONE;
 }
 
+// The images of a pass that reads level `level`: the undeformed one and LK_IMG_DEF (def_slot < 0) or a ring slot, whose
+// pyramid the engine's stream then waits for.
+static int level_images(lk_engine *e, const char *who, int level, int def_slot, const DevImage **und, const DevImage **def) {
+  const std::string w(who);
+  const DevImage &u = e->img[LK_IMG_UND];
+  const DevImage *d = &e->img[LK_IMG_DEF];
+  if (def_slot >= 0) {
+    if (def_slot >= (int)e->ring.size())
+      return e->fail(LK_ERROR_BAD_DOMAIN, w + ": unknown ring slot (lk_sequence_reserve)");
+    d = &e->ring[(size_t)def_slot];
+    if (d->valid)
+      HIPCHK(hipStreamWaitEvent(e->stream, e->ring_ready[(size_t)def_slot], 0));
+  }
+  if (!u.valid || !d->valid || !u.lvl[level] || !d->lvl[level])
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": the undeformed and the deformed image must be set");
+  *und = &u;
+  *def = d;
+  return LK_ERROR_NONE;
+}
+
 int lk_internal_guess_search_view(lk_engine *e, int level, int def_slot, LkGuessSearchView *v) {
   if (level < 0)
     level = e->cfg.py_stop;
@@ -2803,26 +2810,18 @@ int lk_internal_guess_search_view(lk_engine *e, int level, int def_slot, LkGuess
     if (int rc = commit_impl(e, true))
       return rc;
   }
-  const DevImage &u = e->img[LK_IMG_UND];
-  const DevImage *d = &e->img[LK_IMG_DEF];
-  if (def_slot >= 0) {
-    if (def_slot >= (int)e->ring.size())
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_search_guesses: unknown ring slot (lk_sequence_reserve)");
-    d = &e->ring[(size_t)def_slot];
-    if (d->valid)
-      HIPCHK(hipStreamWaitEvent(e->stream, e->ring_ready[(size_t)def_slot], 0));
-  }
-  if (!u.valid || !d->valid || !u.lvl[level] || !d->lvl[level])
-    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_search_guesses: the undeformed and the deformed image must be set");
+  const DevImage *u = nullptr, *d = nullptr;
+  if (int rc = level_images(e, "lk_search_guesses", level, def_slot, &u, &d)) // (any negative def_slot: LK_IMG_DEF)
+    return rc;
   HIPCHK(e->d_gs_match.ensure((size_t)std::max(e->S, 1)));
   v->stream = e->stream;
   v->S = e->S;
   v->model = e->cfg.fitting_model;
   v->level = level;
-  v->und = u.lvl[level];
+  v->und = u->lvl[level];
   v->def = d->lvl[level];
-  v->urows = u.rows >> level;
-  v->ucols = u.cols >> level;
+  v->urows = u->rows >> level;
+  v->ucols = u->cols >> level;
   v->drows = d->rows >> level;
   v->dcols = d->cols >> level;
   v->xy = e->d_xy[level].p;
@@ -2908,135 +2907,66 @@ int lk_internal_reseed_stats(lk_engine *e, const unsigned long long totals[5]) {
   e->stats_frames = 1;
   return LK_ERROR_NONE;
 }
-void **lk_internal_reseed_slot(lk_engine *e) { return &e->reseed; }
 
-int lk_internal_strain_view(lk_engine *e, int need_records, LkStrainView *v) {
+LkPassSlot **lk_internal_pass_slot(lk_engine *e, int which) { return &e->pass[which]; }
+
+int lk_internal_pass_view(lk_engine *e, const char *who, unsigned need, int def_slot, LkPassView *v) {
+  const std::string w(who);
   if (!e->committed || e->S <= 0)
-    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_strain_field: no committed sectors (call lk_commit_sectors)");
-  if (need_records) {
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": no committed sectors (call lk_commit_sectors)");
+  if (need & LK_VIEW_RECORDS) {
     if (e->results_pending)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_strain_field: the outstanding solve has not been waited for (lk_wait_results)");
+      return e->fail(LK_ERROR_BAD_DOMAIN, w + ": the outstanding solve has not been waited for (lk_wait_results)");
     if (e->seq.outstanding)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_strain_field: a sequence window is outstanding (lk_wait_sequence)");
+      return e->fail(LK_ERROR_BAD_DOMAIN, w + ": a sequence window is outstanding (lk_wait_sequence)");
     if (e->records_S != e->S)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_strain_field: no solve of the committed sectors yet (lk_correlate_all*); pass records");
+      return e->fail(LK_ERROR_BAD_DOMAIN, w + ": no solve of the committed sectors yet (lk_correlate_all*); pass records");
+  }
+  if (need & LK_VIEW_WINDOW) {
+    if (e->seq.outstanding)
+      return e->fail(LK_ERROR_BAD_DOMAIN, w + ": the sequence window is outstanding (lk_wait_sequence)");
+    if (!e->d_seq_result.p || e->seq.n_frames < 1 || e->window_S != e->S || e->d_seq_result.n < (size_t)e->seq.n_frames * (size_t)e->S)
+      return e->fail(LK_ERROR_BAD_DOMAIN, w + ": no window of the committed sectors was solved (lk_correlate_sequence_async)");
   }
   HIPCHK(hipSetDevice(e->cfg.device));
-  // (a rebuild of the lists that is pending - lk_update_sector, a change of mode - stays pending: the call is read-only, and
-  // the centres held until then are the ones the engine-held records were solved at)
-  v->stream = e->stream;
-  v->S = e->S;
-  v->model = e->cfg.fitting_model;
-  v->center = e->d_center.p;
-  v->result = e->d_result.p;
-  return LK_ERROR_NONE;
-}
-void **lk_internal_strain_slot(lk_engine *e) { return &e->strain; }
-
-int lk_internal_uncertainty_view(lk_engine *e, int need_records, int def_slot, LkUncertaintyView *v) {
-  if (!e->committed || e->S <= 0)
-    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: no committed sectors (call lk_commit_sectors)");
-  if (need_records) {
-    if (e->results_pending)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: the outstanding solve has not been waited for (lk_wait_results)");
-    if (e->seq.outstanding)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: a sequence window is outstanding (lk_wait_sequence)");
-    if (e->records_S != e->S)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: no solve of the committed sectors yet (lk_correlate_all*); pass records");
-  }
-  HIPCHK(hipSetDevice(e->cfg.device));
-  if (e->recommit_pending) { // lk_update_sector moved lists: rebuild them as the next solve would (the pass walks them)
-    e->recommit_pending = false;
-    if (int rc = commit_impl(e, true))
+  *v = LkPassView{};
+  if (need & LK_VIEW_IMAGES) {
+    if (e->recommit_pending) { // lk_update_sector moved lists: rebuild them as the next solve would (the pass walks them)
+      e->recommit_pending = false;
+      if (int rc = commit_impl(e, true))
+        return rc;
+    }
+    if (def_slot < -1)
+      return e->fail(LK_ERROR_BAD_DOMAIN, w + ": def_slot must be -1 (LK_IMG_DEF) or a ring slot");
+    const int level = e->cfg.py_start; // a level the commit builds lists for (commit_impl: level 0 and py_start, ...)
+    const DevImage *u = nullptr, *d = nullptr;
+    if (int rc = level_images(e, who, level, def_slot, &u, &d))
       return rc;
+    v->level = level;
+    v->und = u->lvl[level];
+    v->def = d->lvl[level];
+    v->urows = u->rows >> level;
+    v->ucols = u->cols >> level;
+    v->drows = d->rows >> level;
+    v->dcols = d->cols >> level;
+    v->xy = e->d_xy[level].p;
+    v->off = e->d_off[level].p;
+    v->rect = e->d_rect[level].p;
   }
-  const int level = e->cfg.py_start; // a level the commit builds lists for (commit_impl: level 0 and py_start, ...)
-  const DevImage &u = e->img[LK_IMG_UND];
-  const DevImage *d = &e->img[LK_IMG_DEF];
-  if (def_slot >= 0) {
-    if (def_slot >= (int)e->ring.size())
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: unknown ring slot (lk_sequence_reserve)");
-    d = &e->ring[(size_t)def_slot];
-    if (d->valid)
-      HIPCHK(hipStreamWaitEvent(e->stream, e->ring_ready[(size_t)def_slot], 0));
-  } else if (def_slot != -1) {
-    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: def_slot must be -1 (LK_IMG_DEF) or a ring slot");
-  }
-  if (!u.valid || !d->valid || !u.lvl[level] || !d->lvl[level])
-    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: the undeformed and the deformed image must be set");
   v->stream = e->stream;
   v->S = e->S;
   v->model = e->cfg.fitting_model;
   v->interp = e->cfg.interpolation;
-  v->level = level;
-  v->und = u.lvl[level];
-  v->def = d->lvl[level];
-  v->urows = u.rows >> level;
-  v->ucols = u.cols >> level;
-  v->drows = d->rows >> level;
-  v->dcols = d->cols >> level;
-  v->xy = e->d_xy[level].p;
-  v->off = e->d_off[level].p;
-  v->rect = e->d_rect[level].p;
   v->h_rect0 = e->h_rect[0].data();
   v->h_off0 = e->h_off[0].data();
   v->center = e->d_center.p;
   v->result = e->d_result.p;
-  return LK_ERROR_NONE;
-}
-void **lk_internal_uncertainty_slot(lk_engine *e) { return &e->uncertainty; }
-
-int lk_internal_outlier_view(lk_engine *e, int need_records, LkOutlierView *v) {
-  if (!e->committed || e->S <= 0)
-    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_flag_outliers: no committed sectors (call lk_commit_sectors)");
-  if (need_records) {
-    if (e->results_pending)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_flag_outliers: the outstanding solve has not been waited for (lk_wait_results)");
-    if (e->seq.outstanding)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_flag_outliers: a sequence window is outstanding (lk_wait_sequence)");
-    if (e->records_S != e->S)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_flag_outliers: no solve of the committed sectors yet (lk_correlate_all*); pass records");
+  if (need & LK_VIEW_WINDOW) {
+    v->window = e->d_seq_result.p;
+    v->window_frames = e->seq.n_frames;
   }
-  HIPCHK(hipSetDevice(e->cfg.device));
-  // (as lk_internal_strain_view: a pending rebuild of the lists stays pending)
-  v->stream = e->stream;
-  v->S = e->S;
-  v->model = e->cfg.fitting_model;
-  v->center = e->d_center.p;
-  v->result = e->d_result.p;
   return LK_ERROR_NONE;
 }
-void **lk_internal_outlier_slot(lk_engine *e) { return &e->outlier; }
-
-int lk_internal_track_view(lk_engine *e, int source, LkTrackView *v) {
-  if (!e->committed || e->S <= 0)
-    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: no committed sectors (call lk_commit_sectors)");
-  if (source == LK_TRACK_RECORDS_ENGINE) {
-    if (e->results_pending)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: the outstanding solve has not been waited for (lk_wait_results)");
-    if (e->seq.outstanding)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: a sequence window is outstanding (lk_wait_sequence)");
-    if (e->records_S != e->S)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: no solve of the committed sectors yet (lk_correlate_all*); pass records");
-  } else if (source == LK_TRACK_RECORDS_WINDOW) {
-    if (e->seq.outstanding)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: the sequence window is outstanding (lk_wait_sequence)");
-    if (!e->d_seq_result.p || e->seq.n_frames < 1 || e->window_S != e->S || e->d_seq_result.n < (size_t)e->seq.n_frames * (size_t)e->S)
-      return e->fail(LK_ERROR_BAD_DOMAIN, "lk_track_points: no window of the committed sectors was solved (lk_correlate_sequence_async)");
-  }
-  HIPCHK(hipSetDevice(e->cfg.device));
-  // (as lk_internal_strain_view: a pending rebuild of the lists stays pending)
-  v->stream = e->stream;
-  v->S = e->S;
-  v->model = e->cfg.fitting_model;
-  v->center = e->d_center.p;
-  v->result = e->d_result.p;
-  v->window = source == LK_TRACK_RECORDS_WINDOW ? e->d_seq_result.p : nullptr;
-  v->window_frames = source == LK_TRACK_RECORDS_WINDOW ? e->seq.n_frames : 0;
-  return LK_ERROR_NONE;
-}
-void **lk_internal_track_slot(lk_engine *e) { return &e->track; }
-void **lk_internal_residual_slot(lk_engine *e) { return &e->residual; }
 
 extern "C" {
 

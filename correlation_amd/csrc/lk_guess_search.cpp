@@ -6,20 +6,12 @@
 
 #include "../../include/lk_engine.h"
 #include "../../include/lk_tracker.h"
-#include "lk_device.hpp"
-#include "lk_internal.hpp"
 #include "lk_launch.hpp"
+#include "lk_pass.hpp"
 
 // lk_tracker.cpp: the search the sequence functions run on frame 0 (nullptr: none)
 extern "C" int lk_tracker_internal_set_search(lk_tracker *t, const lk_guess_search *cfg,
                                    int (*search)(lk_engine *, const lk_guess_search *, float *));
-
-#define GSCHK(call)                                                                                   \
-  do {                                                                                                \
-    hipError_t _e = (call);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return lk_internal_hipfail(e, _e, #call);                                                       \
-  } while (0)
 
 extern "C" {
 
@@ -70,12 +62,12 @@ int lk_search_guesses(lk_engine *e, const lk_guess_search *cfg, float *guesses_i
   }
   a.win_bytes = (int)std::min<long long>(budget, (need + 3) / 4 * 4);
   if (guesses_inout)
-    GSCHK(hipMemcpyAsync(v.d_guess, guesses_inout, 6 * sizeof(float) * (size_t)v.S, hipMemcpyHostToDevice, v.stream));
-  GSCHK(lk_launch_guess_search(a, v.stream));
+    LK_HIPCHK(hipMemcpyAsync(v.d_guess, guesses_inout, 6 * sizeof(float) * (size_t)v.S, hipMemcpyHostToDevice, v.stream));
+  LK_HIPCHK(lk_launch_guess_search(a, v.stream));
   *lk_internal_guess_search_count(e) = v.S;
   if (guesses_inout) {
-    GSCHK(hipMemcpyAsync(guesses_inout, v.d_guess, 6 * sizeof(float) * (size_t)v.S, hipMemcpyDeviceToHost, v.stream));
-    GSCHK(hipStreamSynchronize(v.stream));
+    LK_HIPCHK(hipMemcpyAsync(guesses_inout, v.d_guess, 6 * sizeof(float) * (size_t)v.S, hipMemcpyDeviceToHost, v.stream));
+    LK_HIPCHK(hipStreamSynchronize(v.stream));
   }
   return LK_ERROR_NONE;
 }
@@ -90,8 +82,8 @@ int lk_get_guess_search_info(lk_engine *e, lk_guess_match *out) {
   hipStream_t st = nullptr;
   if (int rc = lk_internal_guess_search_matches(e, &d_match, &st))
     return rc;
-  GSCHK(hipMemcpyAsync(out, d_match, sizeof(lk_guess_match) * (size_t)n, hipMemcpyDeviceToHost, st));
-  GSCHK(hipStreamSynchronize(st));
+  LK_HIPCHK(hipMemcpyAsync(out, d_match, sizeof(lk_guess_match) * (size_t)n, hipMemcpyDeviceToHost, st));
+  LK_HIPCHK(hipStreamSynchronize(st));
   return LK_ERROR_NONE;
 }
 

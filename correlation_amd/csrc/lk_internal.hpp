@@ -79,35 +79,32 @@ int lk_internal_solve_set(lk_engine *e, const LkSectorSet *set, const float *d_g
 // lk_get_stats after the pass: the counters of the retry solves {sectors, evaluations, sample evaluations, point
 // iterations, ill-conditioned solves}
 int lk_internal_reseed_stats(lk_engine *e, const unsigned long long totals[5]);
-void **lk_internal_reseed_slot(lk_engine *e);
-void lk_internal_reseed_release(void *state); // (lk_reseed.cpp; called by lk_destroy)
 
-// ---- strain field (lk_strain.cpp) ------------------------------------------------------------------------------------
-// What lk_strain_field needs of the engine: read-only.  need_records: the engine must hold the records of a finished
-// batch solve of the committed sectors (allowed in every mode, reference-order included).
-struct LkStrainView {
-  hipStream_t stream;
-  int S, model;
-  const float2 *center;    // [S]
-  const lk_result *result; // [S] the engine-held records
+// ---- the add-on passes (lk_pass.hpp has the host plumbing they share) -----------------------------------------------------
+// What a pass keeps between its calls hangs on its entry of one table of the engine: made by the pass on first use
+// (lk_pass_state), deleted by lk_destroy through the virtual destructor.
+struct LkPassSlot {
+  virtual ~LkPassSlot() = default;
 };
-int lk_internal_strain_view(lk_engine *e, int need_records, LkStrainView *v);
-void **lk_internal_strain_slot(lk_engine *e);
-void lk_internal_strain_release(void *state); // (lk_strain.cpp; called by lk_destroy)
-// Bench hook (scripts/strain_bench.py; exported, not part of include/*.h): of the last lk_strain_field, the HIP-event time
-// of its device part (bounding box with its round trip, grid kernels, prep, fit), the lane group and variant that ran and
-// the expected members of a sector's 3 x 3 cells.  The two events are recorded by every call; the time is read here.
-extern "C" int lk_internal_strain_last(lk_engine *e, float *device_ms, int *group, int *packed, double *members);
+enum LkPass { LK_PASS_RESEED, LK_PASS_STRAIN, LK_PASS_UNCERTAINTY, LK_PASS_OUTLIER, LK_PASS_TRACK, LK_PASS_RESIDUAL, LK_PASS_COUNT };
+LkPassSlot **lk_internal_pass_slot(lk_engine *e, int which);
 
-// ---- per-sector uncertainty (lk_uncertainty.cpp) -----------------------------------------------------------------------
-// What lk_parameter_uncertainty needs of the engine: read-only, at level L = py_start (the finest level the solve reaches).
-// The accessor finishes a pending rebuild of the lists as lk_internal_guess_search_view does (the pass walks them), and makes
-// the engine's stream wait for a ring slot's pyramid.  need_records: the engine must hold the records of a finished batch
-// solve of the committed sectors.  Allowed in every mode, reference-order included.
-struct LkUncertaintyView {
+// What a post-processing pass reads of the engine (lk_strain_field, lk_parameter_uncertainty, lk_flag_outliers,
+// lk_track_points, lk_photometry, lk_residual_map).  Allowed in every mode, reference-order included.  `need` says what the
+// call depends on; every refusal is prefixed with `who`, the function the caller called.
+enum : unsigned {
+  LK_VIEW_RECORDS = 1u, // the engine-held records of a finished batch solve of the committed sectors (`result`)
+  LK_VIEW_WINDOW = 2u,  // a window of the committed sectors that has been waited for (`window`, read in place)
+  // The level-L images and lists, L = py_start, the finest level the solve reaches; def_slot: -1 (LK_IMG_DEF) or a ring
+  // slot, whose pyramid the engine's stream then waits for.  The pass walks the lists, so a pending rebuild of them
+  // (lk_update_sector) is finished as the next solve would.  Without this flag it stays pending: the call reads the centres
+  // alone, and the ones held until then are the ones the engine-held records were solved at.
+  LK_VIEW_IMAGES = 4u,
+};
+struct LkPassView {
   hipStream_t stream;
   int S, model, interp, level;
-  const uint8_t *und, *def; // level-L images (def: LK_IMG_DEF or the ring slot)
+  const uint8_t *und, *def; // level-L images (LK_VIEW_IMAGES, else null, as the lists)
   int urows, ucols, drows, dcols;
   const float2 *xy;         // level-L lists in the reference's order, [S+1] offsets, [S] implicit rectangles (device)
   const uint32_t *off;
@@ -115,59 +112,26 @@ struct LkUncertaintyView {
   const int4 *h_rect0;      // [S] the level-0 rectangles on the host (width 0: explicit list)
   const uint32_t *h_off0;   // [S+1] the level-0 offsets on the host
   const float2 *center;     // [S]
-  const lk_result *result;  // [S] the engine-held records
-};
-int lk_internal_uncertainty_view(lk_engine *e, int need_records, int def_slot, LkUncertaintyView *v);
-void **lk_internal_uncertainty_slot(lk_engine *e);
-void lk_internal_uncertainty_release(void *state); // (lk_uncertainty.cpp; called by lk_destroy)
-// Bench hook (scripts/uncertainty_bench.py; exported, not part of include/*.h): of the last lk_parameter_uncertainty, the
-// HIP-event time of its kernels and the sectors each lane group (16, 64, 512 lanes) took.
-extern "C" int lk_internal_uncertainty_last(lk_engine *e, float *device_ms, int *count3);
-
-// ---- outlier flags (lk_outlier.cpp) --------------------------------------------------------------------------------------
-// What lk_flag_outliers needs of the engine: lk_internal_strain_view's rules (a pending rebuild of the lists keeps waiting),
-// but `result` may be written - the errorCode words of the flagged sectors, and only with mark = 1 on engine-held records.
-struct LkOutlierView {
-  hipStream_t stream;
-  int S, model;
-  const float2 *center; // [S]
-  lk_result *result;    // [S] the engine-held records
-};
-int lk_internal_outlier_view(lk_engine *e, int need_records, LkOutlierView *v);
-void **lk_internal_outlier_slot(lk_engine *e);
-void lk_internal_outlier_release(void *state); // (lk_outlier.cpp; called by lk_destroy)
-// Bench hook (scripts/outlier_bench.py; exported, not part of include/*.h): of the last lk_flag_outliers, the HIP-event time
-// of its device part (bounding box with its round trip, grid kernels, prep, every pass, the mark), the lane group, the LDS
-// rows a lane may stash and the expected members of a sector's 3 x 3 cells.
-extern "C" int lk_internal_outlier_last(lk_engine *e, float *device_ms, int *group, int *lds_rows, double *members);
-
-// ---- material-point tracks (lk_track.cpp) ----------------------------------------------------------------------------------
-// What lk_track_points needs of the engine: read-only, lk_internal_strain_view's rules (a pending rebuild of the lists keeps
-// waiting).  source: LK_TRACK_RECORDS_CALLER needs committed sectors only; _ENGINE the records of a finished batch solve
-// (`result`); _WINDOW a window that has been waited for (`window`, [window_frames][S], read in place).
-struct LkTrackView {
-  hipStream_t stream;
-  int S, model;
-  const float2 *center;    // [S]
-  const lk_result *result; // [S] the engine-held records
-  const lk_result *window; // [window_frames][S] the device records of the last window (source WINDOW, else null)
+  lk_result *result;        // [S] the engine-held records; lk_flag_outliers with mark = 1 writes their errorCode words, every
+                            // other pass only reads
+  const lk_result *window;  // [window_frames][S] the device records of the last window (LK_VIEW_WINDOW, else null)
   int window_frames;
 };
-int lk_internal_track_view(lk_engine *e, int source, LkTrackView *v);
-void **lk_internal_track_slot(lk_engine *e);
-void lk_internal_track_release(void *state); // (lk_track.cpp; called by lk_destroy)
-// Bench hook (scripts/track_bench.py; exported, not part of include/*.h): of the last lk_track_points, the HIP-event time of
-// its device part (bounding box with its round trip, grid kernels, prep, the track kernel), the lane group that ran and the
-// expected members of a position's 3 x 3 cells.
-extern "C" int lk_internal_track_last(lk_engine *e, float *device_ms, int *group, double *members);
+int lk_internal_pass_view(lk_engine *e, const char *who, unsigned need, int def_slot, LkPassView *v);
 
-// ---- photometry and the residual map (lk_residual.cpp) ------------------------------------------------------------------------
-// Both passes read the engine through lk_internal_uncertainty_view (the same level-L images, lists, rectangles, centres,
-// records and ring slot); their buffers hang on a slot of their own.
-void **lk_internal_residual_slot(lk_engine *e);
-void lk_internal_residual_release(void *state); // (lk_residual.cpp; called by lk_destroy)
-// Bench hook (scripts/residual_bench.py; exported, not part of include/*.h): of the last lk_photometry or lk_residual_map, the
-// HIP-event time of its device part (the map: bounding box with its round trip, grid kernels, prep, the map kernel), the
-// pixel tiles of a map (0 after lk_photometry) and how many of them walked global memory because their candidates did not fit
-// into LDS.
-extern "C" int lk_internal_residual_last(lk_engine *e, float *device_ms, int *tiles, int *fallback_tiles);
+// Bench hooks (scripts/*_bench.py; exported, not part of include/*.h): of the last call of a pass, the HIP-event time of its
+// device part - for the passes with a cell grid the bounding box with its round trip, the grid kernels, the prep and the
+// pass's own kernels - and what the call chose.  The two events are recorded by every call; the time is read here.
+extern "C" {
+// the lane group and variant that ran, the expected members of a sector's 3 x 3 cells
+int lk_internal_strain_last(lk_engine *e, float *device_ms, int *group, int *packed, double *members);
+// the sectors each lane group (16, 64, 512 lanes) took
+int lk_internal_uncertainty_last(lk_engine *e, float *device_ms, int *count3);
+// the lane group, the LDS rows a lane may stash, the expected members of a sector's 3 x 3 cells
+int lk_internal_outlier_last(lk_engine *e, float *device_ms, int *group, int *lds_rows, double *members);
+// the lane group, the expected members of a position's 3 x 3 cells
+int lk_internal_track_last(lk_engine *e, float *device_ms, int *group, double *members);
+// lk_photometry or lk_residual_map: the pixel tiles of a map (0 after lk_photometry) and how many of them walked global
+// memory because their candidates did not fit into LDS
+int lk_internal_residual_last(lk_engine *e, float *device_ms, int *tiles, int *fallback_tiles);
+}

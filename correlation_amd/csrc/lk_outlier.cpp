@@ -5,21 +5,11 @@
 
 #include <cmath>
 #include <cstdlib>
-#include <initializer_list>
 
 #include "../../include/lk_engine.h"
-#include "lk_cell_grid.hpp"
-#include "lk_device.hpp"
-#include "lk_internal.hpp"
 #include "lk_launch.hpp"
 #include "lk_outlier.hpp"
-
-#define OLCHK(call)                                                                                   \
-  do {                                                                                                \
-    hipError_t _e = (call);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return lk_internal_hipfail(e, _e, #call);                                                       \
-  } while (0)
+#include "lk_pass.hpp"
 
 namespace {
 
@@ -30,45 +20,16 @@ namespace {
 // (DESIGN.md section 17).
 constexpr double kWideGroupFrom = 640.0;
 
-struct OutlierState {
+struct OutlierState : LkPassState {
   LkDevBytes rec, good, pack, out, bbox;
   LkCellGridBufs grid;
-  float *h_bbox = nullptr; // pinned [4]
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;      // ev0 / ev1 bracket the device part of a finished call (read by lk_internal_outlier_last)
   int group = 0, lds_rows = 0;
-  double members = 0;      // expected members of the 3 x 3 cells of the last call
+  double members = 0; // expected members of the 3 x 3 cells of the last call
 };
-
-int get_state(lk_engine *e, OutlierState **out) {
-  void **slot = lk_internal_outlier_slot(e);
-  if (!*slot) {
-    OutlierState *st = new OutlierState();
-    hipError_t err = hipHostMalloc((void **)&st->h_bbox, 4 * sizeof(float), hipHostMallocDefault);
-    if (err == hipSuccess)
-      err = hipEventCreate(&st->ev0);
-    if (err == hipSuccess)
-      err = hipEventCreate(&st->ev1);
-    if (err != hipSuccess) {
-      lk_internal_outlier_release(st);
-      return lk_internal_hipfail(e, err, "hipHostMalloc / hipEventCreate (lk_flag_outliers)");
-    }
-    *slot = st;
-  }
-  *out = (OutlierState *)*slot;
-  return LK_ERROR_NONE;
-}
 
 // test hooks: LK_OUTLIER_GROUP = 16 / 64 overrides the choice of the lane group; LK_OUTLIER_LDS_CAP =
 // the members of a window a group may keep in LDS (rounded down to whole rows of `group` lanes, at most kLkOutlierRows rows;
 // 0 re-walks every window)
-int env_group(int otherwise) {
-  const char *s = std::getenv("LK_OUTLIER_GROUP");
-  if (!s || !*s)
-    return otherwise;
-  const int v = std::atoi(s);
-  return v == 16 || v == 64 ? v : otherwise;
-}
 int env_rows(int group) {
   const char *s = std::getenv("LK_OUTLIER_LDS_CAP");
   if (!s || !*s)
@@ -83,22 +44,6 @@ int env_rows(int group) {
 bool positive(float v) { return std::isfinite(v) && v > 0.f; }
 
 } // namespace
-
-void lk_internal_outlier_release(void *state) {
-  OutlierState *st = (OutlierState *)state;
-  if (!st)
-    return;
-  for (LkDevBytes *b : {&st->rec, &st->good, &st->pack, &st->out, &st->bbox, &st->grid.cell_of, &st->grid.start, &st->grid.cursor,
-                        &st->grid.unordered, &st->grid.members})
-    b->release();
-  if (st->h_bbox)
-    (void)hipHostFree(st->h_bbox);
-  if (st->ev0)
-    (void)hipEventDestroy(st->ev0);
-  if (st->ev1)
-    (void)hipEventDestroy(st->ev1);
-  delete st;
-}
 
 extern "C" {
 
@@ -128,38 +73,29 @@ int lk_flag_outliers(lk_engine *e, const lk_outlier_config *cfg, const lk_result
                             "the sector itself is not counted), at least 3 without");
   if (cfg->passes < 1 || cfg->passes > 4)
     return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_flag_outliers: passes must be 1..4");
-  LkOutlierView v{};
-  if (int rc = lk_internal_outlier_view(e, records ? 0 : 1, &v))
+  LkPassView v{};
+  if (int rc = lk_internal_pass_view(e, "lk_flag_outliers", records ? 0 : LK_VIEW_RECORDS, -1, &v))
     return rc;
   if (cfg->mark && !records && lk_internal_reference_order(e))
     return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN,
                             "lk_flag_outliers: mark = 1 on the engine-held records is refused in reference-order mode (its records "
                             "are the CPU engine's); pass records, or mark = 0");
   OutlierState *st = nullptr;
-  if (int rc = get_state(e, &st))
+  if (int rc = lk_pass_state(e, LK_PASS_OUTLIER, "hipHostMalloc / hipEventCreate (lk_flag_outliers)", &st))
     return rc;
   const size_t n = (size_t)v.S;
-  OLCHK(st->good.ensure(n));
-  OLCHK(st->pack.ensure(n * sizeof(float4)));
-  OLCHK(st->out.ensure(n * sizeof(lk_outlier)));
-  OLCHK(st->bbox.ensure(4 * sizeof(float)));
+  LK_HIPCHK(st->good.ensure(n));
+  LK_HIPCHK(st->pack.ensure(n * sizeof(float4)));
+  LK_HIPCHK(st->out.ensure(n * sizeof(lk_outlier)));
+  LK_HIPCHK(st->bbox.ensure(4 * sizeof(float)));
   lk_result *d_rec = v.result;
-  if (records) {
-    OLCHK(st->rec.ensure(n * sizeof(lk_result)));
-    OLCHK(hipMemcpyAsync(st->rec.p, records, n * sizeof(lk_result), hipMemcpyHostToDevice, v.stream));
-    d_rec = st->rec.as<lk_result>(); // (the call's own copy: marking it touches nothing of the engine's)
-  }
-  st->timed = false;
-  OLCHK(hipEventRecord(st->ev0, v.stream));
-  // the centres' bounding box sizes the grid: the call's one round trip before the kernels
-  OLCHK(lk_launch_reseed_bbox(v.center, v.S, st->bbox.as<float>(), v.stream));
-  OLCHK(hipMemcpyAsync(st->h_bbox, st->bbox.p, 4 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
-  OLCHK(hipStreamSynchronize(v.stream));
-  if (!lk_cell_grid_bbox_finite(st->h_bbox))
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_flag_outliers: a sector centre is not finite");
+  if (int rc = lk_pass_records(e, st->rec, records, n, v.stream, &d_rec)) // (the call's own copy: marking it touches nothing of the engine's)
+    return rc;
+  LK_HIPCHK(st->begin(v.stream));
   LkOutlierArgs a{};
-  OLCHK(lk_cell_grid_build(st->grid, v.center, v.S, cfg->radius, st->h_bbox, v.stream, &a.grid));
-  OLCHK(lk_launch_outlier_prep(d_rec, v.center, v.S, v.model, cfg->chi_max, st->good.as<uint8_t>(), st->pack.as<float4>(), v.stream));
+  if (int rc = lk_pass_grid(e, "lk_flag_outliers", st, st->bbox, st->grid, v.center, v.S, cfg->radius, v.stream, &a.grid))
+    return rc;
+  LK_HIPCHK(lk_launch_outlier_prep(d_rec, v.center, v.S, v.model, cfg->chi_max, st->good.as<uint8_t>(), st->pack.as<float4>(), v.stream));
   a.center = v.center;
   a.good = st->good.as<uint8_t>();
   a.pack = st->pack.as<float4>();
@@ -171,22 +107,22 @@ int lk_flag_outliers(lk_engine *e, const lk_outlier_config *cfg, const lk_result
   a.threshold = cfg->threshold;
   a.radius = (double)cfg->radius;
   st->members = 9.0 * (double)v.S / ((double)a.grid.nx * (double)a.grid.ny);
-  st->group = env_group(st->members > kWideGroupFrom ? 64 : 16);
+  st->group = lk_pass_env_choice("LK_OUTLIER_GROUP", 16, 64, st->members > kWideGroupFrom ? 64 : 16);
   st->lds_rows = a.lds_rows = env_rows(st->group);
   for (int pass = 0; pass < cfg->passes; ++pass) {
     if (pass > 0) // (the pass before has written every record of a.out; this one writes them again after reading the marks)
-      OLCHK(lk_launch_outlier_exclude(a.out, v.center, a.good, v.S, st->pack.as<float4>(), v.stream));
-    OLCHK(lk_launch_outlier(a, st->group, v.stream));
+      LK_HIPCHK(lk_launch_outlier_exclude(a.out, v.center, a.good, v.S, st->pack.as<float4>(), v.stream));
+    LK_HIPCHK(lk_launch_outlier(a, st->group, v.stream));
   }
   const bool marks = cfg->mark && (records_out || !records);
   if (marks)
-    OLCHK(lk_launch_outlier_mark(a.out, v.S, d_rec, v.stream));
-  OLCHK(hipEventRecord(st->ev1, v.stream));
-  OLCHK(hipMemcpyAsync(out, st->out.p, n * sizeof(lk_outlier), hipMemcpyDeviceToHost, v.stream));
+    LK_HIPCHK(lk_launch_outlier_mark(a.out, v.S, d_rec, v.stream));
+  LK_HIPCHK(st->end(v.stream));
+  LK_HIPCHK(hipMemcpyAsync(out, st->out.p, n * sizeof(lk_outlier), hipMemcpyDeviceToHost, v.stream));
   if (records_out)
-    OLCHK(hipMemcpyAsync(records_out, d_rec, n * sizeof(lk_result), hipMemcpyDeviceToHost, v.stream));
-  OLCHK(hipStreamSynchronize(v.stream));
-  st->timed = true;
+    LK_HIPCHK(hipMemcpyAsync(records_out, d_rec, n * sizeof(lk_result), hipMemcpyDeviceToHost, v.stream));
+  LK_HIPCHK(hipStreamSynchronize(v.stream));
+  st->finished();
   if (n_flagged) {
     int c = 0;
     for (size_t s = 0; s < n; ++s)
@@ -210,11 +146,9 @@ int lk_outlier_from_window(int n, const float *e_u, const float *e_v, float es_u
 int lk_internal_outlier_last(lk_engine *e, float *device_ms, int *group, int *lds_rows, double *members) {
   if (!e)
     return LK_ERROR_BAD_DOMAIN;
-  OutlierState *st = (OutlierState *)*lk_internal_outlier_slot(e);
-  if (!st || !st->timed)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_internal_outlier_last: no lk_flag_outliers yet");
-  if (device_ms)
-    OLCHK(hipEventElapsedTime(device_ms, st->ev0, st->ev1));
+  OutlierState *st = nullptr;
+  if (int rc = lk_pass_last(e, LK_PASS_OUTLIER, "lk_internal_outlier_last: no lk_flag_outliers yet", device_ms, &st))
+    return rc;
   if (group)
     *group = st->group;
   if (lds_rows)

@@ -9,17 +9,8 @@
 #include <string>
 
 #include "../../include/lk_engine.h"
-#include "lk_cell_grid.hpp"
-#include "lk_device.hpp"
-#include "lk_internal.hpp"
 #include "lk_launch.hpp"
-
-#define RSCHK(call)                                                                                   \
-  do {                                                                                                \
-    hipError_t _e = (call);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return lk_internal_hipfail(e, _e, #call);                                                       \
-  } while (0)
+#include "lk_pass.hpp"
 
 namespace {
 
@@ -34,14 +25,17 @@ struct Words {
   float bbox[4];
 };
 
-struct ReseedState {
+struct ReseedState : LkPassSlot {
   Buf good, tried, nbrs, retry, guess, info, plan_info, fresh, keep_last_p, keep_last_eval_p, keep_stats, retry_order,
       bw_retry_order, words;
   LkCellGridBufs grid;
   Words *h_words = nullptr; // pinned
   int info_S = 0;           // sectors `info` describes (0: no lk_reseed_failed yet)
-  Buf *all[19] = {&good, &tried, &nbrs, &retry, &guess, &info, &plan_info, &fresh, &keep_last_p, &keep_last_eval_p,
-                  &keep_stats, &retry_order, &bw_retry_order, &grid.cell_of, &grid.start, &grid.cursor, &grid.unordered, &grid.members, &words};
+  hipError_t init() { return hipHostMalloc((void **)&h_words, sizeof(Words), hipHostMallocDefault); }
+  ~ReseedState() override {
+    if (h_words)
+      (void)hipHostFree(h_words);
+  }
 };
 
 int n_params_of(int model) { return model == LK_FM_U ? 1 : model == LK_FM_UV ? 2 : model == LK_FM_UVQ ? 3 : 6; }
@@ -61,30 +55,15 @@ int check_config(lk_engine *e, const lk_reseed_config *cfg, const char *who, boo
   return LK_ERROR_NONE;
 }
 
-int get_state(lk_engine *e, ReseedState **out) {
-  void **slot = lk_internal_reseed_slot(e);
-  if (!*slot) {
-    ReseedState *st = new ReseedState();
-    const hipError_t err = hipHostMalloc((void **)&st->h_words, sizeof(Words), hipHostMallocDefault);
-    if (err != hipSuccess) {
-      delete st;
-      return lk_internal_hipfail(e, err, "hipHostMalloc (lk_reseed)");
-    }
-    *slot = st;
-  }
-  *out = (ReseedState *)*slot;
-  return LK_ERROR_NONE;
-}
-
 int ensure_common(lk_engine *e, ReseedState *st, int S) {
   const size_t n = (size_t)S;
-  RSCHK(st->good.ensure(n));
-  RSCHK(st->tried.ensure(n * sizeof(int32_t)));
-  RSCHK(st->nbrs.ensure(n * sizeof(int32_t)));
-  RSCHK(st->retry.ensure(n));
-  RSCHK(st->guess.ensure(n * 6 * sizeof(float)));
-  RSCHK(st->fresh.ensure(n * sizeof(lk_result)));
-  RSCHK(st->words.ensure(sizeof(Words)));
+  LK_HIPCHK(st->good.ensure(n));
+  LK_HIPCHK(st->tried.ensure(n * sizeof(int32_t)));
+  LK_HIPCHK(st->nbrs.ensure(n * sizeof(int32_t)));
+  LK_HIPCHK(st->retry.ensure(n));
+  LK_HIPCHK(st->guess.ensure(n * 6 * sizeof(float)));
+  LK_HIPCHK(st->fresh.ensure(n * sizeof(lk_result)));
+  LK_HIPCHK(st->words.ensure(sizeof(Words)));
   return LK_ERROR_NONE;
 }
 
@@ -92,13 +71,13 @@ int ensure_common(lk_engine *e, ReseedState *st, int S) {
 int build_grid(lk_engine *e, ReseedState *st, const LkReseedView &v, float radius, const float bbox[4], LkReseedGrid *g) {
   if (!lk_cell_grid_bbox_finite(bbox))
     return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_reseed: a sector centre is not finite");
-  RSCHK(lk_cell_grid_build(st->grid, v.center, v.S, radius, bbox, v.stream, g));
+  LK_HIPCHK(lk_cell_grid_build(st->grid, v.center, v.S, radius, bbox, v.stream, g));
   return LK_ERROR_NONE;
 }
 
 int fetch_words(lk_engine *e, ReseedState *st, hipStream_t stream) {
-  RSCHK(hipMemcpyAsync(st->h_words, st->words.p, sizeof(Words), hipMemcpyDeviceToHost, stream));
-  RSCHK(hipStreamSynchronize(stream));
+  LK_HIPCHK(hipMemcpyAsync(st->h_words, st->words.p, sizeof(Words), hipMemcpyDeviceToHost, stream));
+  LK_HIPCHK(hipStreamSynchronize(stream));
   return LK_ERROR_NONE;
 }
 
@@ -123,17 +102,6 @@ LkReseedPlanArgs plan_args(ReseedState *st, const LkReseedView &v, const LkResee
 
 } // namespace
 
-void lk_internal_reseed_release(void *state) {
-  ReseedState *st = (ReseedState *)state;
-  if (!st)
-    return;
-  for (Buf *b : st->all)
-    b->release();
-  if (st->h_words)
-    (void)hipHostFree(st->h_words);
-  delete st;
-}
-
 extern "C" {
 
 int lk_reseed_failed(lk_engine *e, const lk_reseed_config *cfg, lk_result *out, int *n_recovered) {
@@ -147,26 +115,26 @@ int lk_reseed_failed(lk_engine *e, const lk_reseed_config *cfg, lk_result *out, 
   if (int rc = lk_internal_reseed_view(e, 1, "lk_reseed_failed", &v))
     return rc;
   ReseedState *st = nullptr;
-  if (int rc = get_state(e, &st))
+  if (int rc = lk_pass_state(e, LK_PASS_RESEED, "hipHostMalloc (lk_reseed)", &st))
     return rc;
   st->info_S = 0;
   const int S = v.S, P = n_params_of(v.model);
   const size_t n = (size_t)S;
   if (int rc = ensure_common(e, st, S))
     return rc;
-  RSCHK(st->info.ensure(n * sizeof(lk_reseed_info)));
-  RSCHK(st->keep_last_p.ensure(n * 6 * sizeof(float)));
-  RSCHK(st->keep_last_eval_p.ensure(n * 6 * sizeof(float)));
-  RSCHK(st->keep_stats.ensure(n * 4 * sizeof(uint32_t)));
-  RSCHK(st->retry_order.ensure(n * sizeof(uint32_t)));
-  RSCHK(st->bw_retry_order.ensure(n * sizeof(uint32_t)));
+  LK_HIPCHK(st->info.ensure(n * sizeof(lk_reseed_info)));
+  LK_HIPCHK(st->keep_last_p.ensure(n * 6 * sizeof(float)));
+  LK_HIPCHK(st->keep_last_eval_p.ensure(n * 6 * sizeof(float)));
+  LK_HIPCHK(st->keep_stats.ensure(n * 4 * sizeof(uint32_t)));
+  LK_HIPCHK(st->retry_order.ensure(n * sizeof(uint32_t)));
+  LK_HIPCHK(st->bw_retry_order.ensure(n * sizeof(uint32_t)));
   Words *d_words = st->words.as<Words>();
 
   // classify, and the centres' bounding box: the one round trip before the rounds
-  RSCHK(hipMemsetAsync(d_words, 0, sizeof(Words), v.stream));
-  RSCHK(lk_launch_reseed_classify(v.result, S, P, cfg->chi_max, st->good.as<uint8_t>(), st->tried.as<int32_t>(),
+  LK_HIPCHK(hipMemsetAsync(d_words, 0, sizeof(Words), v.stream));
+  LK_HIPCHK(lk_launch_reseed_classify(v.result, S, P, cfg->chi_max, st->good.as<uint8_t>(), st->tried.as<int32_t>(),
                                   st->info.as<lk_reseed_info>(), &d_words->n_failed, v.stream));
-  RSCHK(lk_launch_reseed_bbox(v.center, S, d_words->bbox, v.stream));
+  LK_HIPCHK(lk_launch_reseed_bbox(v.center, S, d_words->bbox, v.stream));
   if (int rc = fetch_words(e, st, v.stream))
     return rc;
   st->info_S = S;
@@ -175,9 +143,9 @@ int lk_reseed_failed(lk_engine *e, const lk_reseed_config *cfg, lk_result *out, 
     if (int rc = build_grid(e, st, v, cfg->radius, st->h_words->bbox, &grid))
       return rc;
     // everything a solve writes per sector besides its record: kept, and put back for a retry that is rejected
-    RSCHK(hipMemcpyAsync(st->keep_last_p.p, v.last_p, n * 6 * sizeof(float), hipMemcpyDeviceToDevice, v.stream));
-    RSCHK(hipMemcpyAsync(st->keep_last_eval_p.p, v.last_eval_p, n * 6 * sizeof(float), hipMemcpyDeviceToDevice, v.stream));
-    RSCHK(hipMemcpyAsync(st->keep_stats.p, v.stats, n * 4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, v.stream));
+    LK_HIPCHK(hipMemcpyAsync(st->keep_last_p.p, v.last_p, n * 6 * sizeof(float), hipMemcpyDeviceToDevice, v.stream));
+    LK_HIPCHK(hipMemcpyAsync(st->keep_last_eval_p.p, v.last_eval_p, n * 6 * sizeof(float), hipMemcpyDeviceToDevice, v.stream));
+    LK_HIPCHK(hipMemcpyAsync(st->keep_stats.p, v.stats, n * 4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, v.stream));
 
     LkReseedCompactArgs ca{};
     ca.retry = st->retry.as<uint8_t>();
@@ -210,8 +178,8 @@ int lk_reseed_failed(lk_engine *e, const lk_reseed_config *cfg, lk_result *out, 
     const LkReseedPlanArgs pa = plan_args(st, v, grid, cfg, v.result);
 
     for (int round = 0; round < cfg->max_rounds; ++round) {
-      RSCHK(lk_launch_reseed_plan(pa, v.stream));
-      RSCHK(lk_launch_reseed_compact(ca, v.stream));
+      LK_HIPCHK(lk_launch_reseed_plan(pa, v.stream));
+      LK_HIPCHK(lk_launch_reseed_compact(ca, v.stream));
       if (int rc = fetch_words(e, st, v.stream)) // the round's one trip to the host: the counts that size the launches
         return rc;
       LkSectorSet set{};
@@ -227,7 +195,7 @@ int lk_reseed_failed(lk_engine *e, const lk_reseed_config *cfg, lk_result *out, 
       if (int rc = lk_internal_solve_set(e, &set, st->guess.as<float>(), st->fresh.as<lk_result>()))
         return rc;
       ma.round = round;
-      RSCHK(lk_launch_reseed_merge(ma, v.stream));
+      LK_HIPCHK(lk_launch_reseed_merge(ma, v.stream));
     }
     if (int rc = fetch_words(e, st, v.stream))
       return rc;
@@ -239,8 +207,8 @@ int lk_reseed_failed(lk_engine *e, const lk_reseed_config *cfg, lk_result *out, 
   if (n_recovered)
     *n_recovered = (int)st->h_words->totals[5];
   if (out) {
-    RSCHK(hipMemcpyAsync(out, v.result, n * sizeof(lk_result), hipMemcpyDeviceToHost, v.stream));
-    RSCHK(hipStreamSynchronize(v.stream));
+    LK_HIPCHK(hipMemcpyAsync(out, v.result, n * sizeof(lk_result), hipMemcpyDeviceToHost, v.stream));
+    LK_HIPCHK(hipStreamSynchronize(v.stream));
   }
   return LK_ERROR_NONE;
 }
@@ -248,10 +216,10 @@ int lk_reseed_failed(lk_engine *e, const lk_reseed_config *cfg, lk_result *out, 
 int lk_get_reseed_info(lk_engine *e, lk_reseed_info *out) {
   if (!e)
     return LK_ERROR_BAD_DOMAIN;
-  ReseedState *st = (ReseedState *)*lk_internal_reseed_slot(e);
+  ReseedState *st = static_cast<ReseedState *>(*lk_internal_pass_slot(e, LK_PASS_RESEED));
   if (!out || !st || st->info_S <= 0 || st->info_S != lk_internal_sector_count(e))
     return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_get_reseed_info: no lk_reseed_failed of the committed sectors");
-  RSCHK(hipMemcpy(out, st->info.p, (size_t)st->info_S * sizeof(lk_reseed_info), hipMemcpyDeviceToHost));
+  LK_HIPCHK(hipMemcpy(out, st->info.p, (size_t)st->info_S * sizeof(lk_reseed_info), hipMemcpyDeviceToHost));
   return LK_ERROR_NONE;
 }
 
@@ -267,20 +235,20 @@ int lk_reseed_plan(lk_engine *e, const lk_reseed_config *cfg, const lk_result *r
   if (int rc = lk_internal_reseed_view(e, 0, "lk_reseed_plan", &v))
     return rc;
   ReseedState *st = nullptr;
-  if (int rc = get_state(e, &st))
+  if (int rc = lk_pass_state(e, LK_PASS_RESEED, "hipHostMalloc (lk_reseed)", &st))
     return rc;
   const int S = v.S, P = n_params_of(v.model);
   const size_t n = (size_t)S;
   if (int rc = ensure_common(e, st, S))
     return rc;
-  RSCHK(st->plan_info.ensure(n * sizeof(lk_reseed_info)));
+  LK_HIPCHK(st->plan_info.ensure(n * sizeof(lk_reseed_info)));
   Words *d_words = st->words.as<Words>();
-  RSCHK(hipMemsetAsync(d_words, 0, sizeof(Words), v.stream));
-  RSCHK(hipMemcpyAsync(st->fresh.p, records, n * sizeof(lk_result), hipMemcpyHostToDevice, v.stream));
-  RSCHK(hipMemsetAsync(st->guess.p, 0, n * 6 * sizeof(float), v.stream));
-  RSCHK(lk_launch_reseed_classify(st->fresh.as<lk_result>(), S, P, cfg->chi_max, st->good.as<uint8_t>(),
+  LK_HIPCHK(hipMemsetAsync(d_words, 0, sizeof(Words), v.stream));
+  LK_HIPCHK(hipMemcpyAsync(st->fresh.p, records, n * sizeof(lk_result), hipMemcpyHostToDevice, v.stream));
+  LK_HIPCHK(hipMemsetAsync(st->guess.p, 0, n * 6 * sizeof(float), v.stream));
+  LK_HIPCHK(lk_launch_reseed_classify(st->fresh.as<lk_result>(), S, P, cfg->chi_max, st->good.as<uint8_t>(),
                                   st->tried.as<int32_t>(), st->plan_info.as<lk_reseed_info>(), &d_words->n_failed, v.stream));
-  RSCHK(lk_launch_reseed_bbox(v.center, S, d_words->bbox, v.stream));
+  LK_HIPCHK(lk_launch_reseed_bbox(v.center, S, d_words->bbox, v.stream));
   if (int rc = fetch_words(e, st, v.stream))
     return rc;
   LkReseedGrid grid{};
@@ -288,10 +256,10 @@ int lk_reseed_plan(lk_engine *e, const lk_reseed_config *cfg, const lk_result *r
     return rc;
   LkReseedPlanArgs pa = plan_args(st, v, grid, cfg, st->fresh.as<lk_result>());
   pa.plan_info = st->plan_info.as<lk_reseed_info>();
-  RSCHK(lk_launch_reseed_plan(pa, v.stream));
-  RSCHK(hipMemcpyAsync(guesses_out, st->guess.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
-  RSCHK(hipMemcpyAsync(info_out, st->plan_info.p, n * sizeof(lk_reseed_info), hipMemcpyDeviceToHost, v.stream));
-  RSCHK(hipStreamSynchronize(v.stream));
+  LK_HIPCHK(lk_launch_reseed_plan(pa, v.stream));
+  LK_HIPCHK(hipMemcpyAsync(guesses_out, st->guess.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
+  LK_HIPCHK(hipMemcpyAsync(info_out, st->plan_info.p, n * sizeof(lk_reseed_info), hipMemcpyDeviceToHost, v.stream));
+  LK_HIPCHK(hipStreamSynchronize(v.stream));
   return LK_ERROR_NONE;
 }
 

@@ -3,21 +3,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
-#include <initializer_list>
 
 #include "../../include/lk_engine.h"
-#include "lk_cell_grid.hpp"
-#include "lk_device.hpp"
-#include "lk_internal.hpp"
 #include "lk_launch.hpp"
-
-#define STCHK(call)                                                                                   \
-  do {                                                                                                \
-    hipError_t _e = (call);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return lk_internal_hipfail(e, _e, #call);                                                       \
-  } while (0)
+#include "lk_pass.hpp"
 
 namespace {
 
@@ -28,61 +17,14 @@ namespace {
 // largest window measured; nothing above it has been timed.
 constexpr double kWideGroupFrom = 1024.0;
 
-struct StrainState {
+struct StrainState : LkPassState {
   LkDevBytes rec, good, pack, out, bbox;
   LkCellGridBufs grid;
-  float *h_bbox = nullptr; // pinned [4]
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;      // ev0 / ev1 bracket the device part of a finished call (read by lk_internal_strain_last)
   int group = 0, packed = 0;
-  double members = 0;      // expected members of the 3 x 3 cells of the last call
+  double members = 0; // expected members of the 3 x 3 cells of the last call
 };
 
-int get_state(lk_engine *e, StrainState **out) {
-  void **slot = lk_internal_strain_slot(e);
-  if (!*slot) {
-    StrainState *st = new StrainState();
-    hipError_t err = hipHostMalloc((void **)&st->h_bbox, 4 * sizeof(float), hipHostMallocDefault);
-    if (err == hipSuccess)
-      err = hipEventCreate(&st->ev0);
-    if (err == hipSuccess)
-      err = hipEventCreate(&st->ev1);
-    if (err != hipSuccess) {
-      lk_internal_strain_release(st);
-      return lk_internal_hipfail(e, err, "hipHostMalloc / hipEventCreate (lk_strain_field)");
-    }
-    *slot = st;
-  }
-  *out = (StrainState *)*slot;
-  return LK_ERROR_NONE;
-}
-
-// tuning experiments (scripts/strain_bench.py): LK_STRAIN_GROUP = 16 / 64 and LK_STRAIN_PACKED = 0 / 1 override the choice
-int env_choice(const char *name, int a, int b, int otherwise) {
-  const char *s = std::getenv(name);
-  if (!s || !*s)
-    return otherwise;
-  const int v = std::atoi(s);
-  return v == a || v == b ? v : otherwise;
-}
-
 } // namespace
-
-void lk_internal_strain_release(void *state) {
-  StrainState *st = (StrainState *)state;
-  if (!st)
-    return;
-  for (LkDevBytes *b : {&st->rec, &st->good, &st->pack, &st->out, &st->bbox, &st->grid.cell_of, &st->grid.start, &st->grid.cursor,
-                        &st->grid.unordered, &st->grid.members})
-    b->release();
-  if (st->h_bbox)
-    (void)hipHostFree(st->h_bbox);
-  if (st->ev0)
-    (void)hipEventDestroy(st->ev0);
-  if (st->ev1)
-    (void)hipEventDestroy(st->ev1);
-  delete st;
-}
 
 extern "C" {
 
@@ -101,34 +43,25 @@ int lk_strain_field(lk_engine *e, const lk_strain_config *cfg, const lk_result *
     return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_strain_field: min_neighbours must be at least 3 (a plane has three unknowns)");
   if (cfg->tensor != LK_STRAIN_GREEN_LAGRANGE && cfg->tensor != LK_STRAIN_SMALL)
     return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_strain_field: unknown tensor");
-  LkStrainView v{};
-  if (int rc = lk_internal_strain_view(e, records ? 0 : 1, &v))
+  LkPassView v{};
+  if (int rc = lk_internal_pass_view(e, "lk_strain_field", records ? 0 : LK_VIEW_RECORDS, -1, &v))
     return rc;
   StrainState *st = nullptr;
-  if (int rc = get_state(e, &st))
+  if (int rc = lk_pass_state(e, LK_PASS_STRAIN, "hipHostMalloc / hipEventCreate (lk_strain_field)", &st))
     return rc;
   const size_t n = (size_t)v.S;
-  STCHK(st->good.ensure(n));
-  STCHK(st->pack.ensure(n * sizeof(float4)));
-  STCHK(st->out.ensure(n * sizeof(lk_strain)));
-  STCHK(st->bbox.ensure(4 * sizeof(float)));
+  LK_HIPCHK(st->good.ensure(n));
+  LK_HIPCHK(st->pack.ensure(n * sizeof(float4)));
+  LK_HIPCHK(st->out.ensure(n * sizeof(lk_strain)));
+  LK_HIPCHK(st->bbox.ensure(4 * sizeof(float)));
   const lk_result *d_rec = v.result;
-  if (records) {
-    STCHK(st->rec.ensure(n * sizeof(lk_result)));
-    STCHK(hipMemcpyAsync(st->rec.p, records, n * sizeof(lk_result), hipMemcpyHostToDevice, v.stream));
-    d_rec = st->rec.as<lk_result>();
-  }
-  st->timed = false;
-  STCHK(hipEventRecord(st->ev0, v.stream));
-  // the centres' bounding box sizes the grid: the call's one round trip before the kernels
-  STCHK(lk_launch_reseed_bbox(v.center, v.S, st->bbox.as<float>(), v.stream));
-  STCHK(hipMemcpyAsync(st->h_bbox, st->bbox.p, 4 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
-  STCHK(hipStreamSynchronize(v.stream));
-  if (!lk_cell_grid_bbox_finite(st->h_bbox))
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_strain_field: a sector centre is not finite");
+  if (int rc = lk_pass_records(e, st->rec, records, n, v.stream, &d_rec))
+    return rc;
+  LK_HIPCHK(st->begin(v.stream));
   LkStrainArgs a{};
-  STCHK(lk_cell_grid_build(st->grid, v.center, v.S, cfg->radius, st->h_bbox, v.stream, &a.grid));
-  STCHK(lk_launch_strain_prep(d_rec, v.center, v.S, v.model, cfg->chi_max, st->good.as<uint8_t>(), st->pack.as<float4>(), v.stream));
+  if (int rc = lk_pass_grid(e, "lk_strain_field", st, st->bbox, st->grid, v.center, v.S, cfg->radius, v.stream, &a.grid))
+    return rc;
+  LK_HIPCHK(lk_launch_strain_prep(d_rec, v.center, v.S, v.model, cfg->chi_max, st->good.as<uint8_t>(), st->pack.as<float4>(), v.stream));
   a.center = v.center;
   a.rec = d_rec;
   a.good = st->good.as<uint8_t>();
@@ -140,13 +73,14 @@ int lk_strain_field(lk_engine *e, const lk_strain_config *cfg, const lk_result *
   a.tensor = cfg->tensor;
   a.radius = (double)cfg->radius;
   st->members = 9.0 * (double)v.S / ((double)a.grid.nx * (double)a.grid.ny);
-  st->group = env_choice("LK_STRAIN_GROUP", 16, 64, st->members > kWideGroupFrom ? 64 : 16);
-  st->packed = env_choice("LK_STRAIN_PACKED", 0, 1, 1);
-  STCHK(lk_launch_strain(a, st->group, st->packed, v.stream));
-  STCHK(hipEventRecord(st->ev1, v.stream));
-  STCHK(hipMemcpyAsync(out, st->out.p, n * sizeof(lk_strain), hipMemcpyDeviceToHost, v.stream));
-  STCHK(hipStreamSynchronize(v.stream));
-  st->timed = true;
+  // tuning experiments (scripts/strain_bench.py): LK_STRAIN_GROUP = 16 / 64 and LK_STRAIN_PACKED = 0 / 1 override the choice
+  st->group = lk_pass_env_choice("LK_STRAIN_GROUP", 16, 64, st->members > kWideGroupFrom ? 64 : 16);
+  st->packed = lk_pass_env_choice("LK_STRAIN_PACKED", 0, 1, 1);
+  LK_HIPCHK(lk_launch_strain(a, st->group, st->packed, v.stream));
+  LK_HIPCHK(st->end(v.stream));
+  LK_HIPCHK(hipMemcpyAsync(out, st->out.p, n * sizeof(lk_strain), hipMemcpyDeviceToHost, v.stream));
+  LK_HIPCHK(hipStreamSynchronize(v.stream));
+  st->finished();
   return LK_ERROR_NONE;
 }
 
@@ -154,11 +88,9 @@ int lk_strain_field(lk_engine *e, const lk_strain_config *cfg, const lk_result *
 int lk_internal_strain_last(lk_engine *e, float *device_ms, int *group, int *packed, double *members) {
   if (!e)
     return LK_ERROR_BAD_DOMAIN;
-  StrainState *st = (StrainState *)*lk_internal_strain_slot(e);
-  if (!st || !st->timed)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_internal_strain_last: no lk_strain_field yet");
-  if (device_ms)
-    STCHK(hipEventElapsedTime(device_ms, st->ev0, st->ev1));
+  StrainState *st = nullptr;
+  if (int rc = lk_pass_last(e, LK_PASS_STRAIN, "lk_internal_strain_last: no lk_strain_field yet", device_ms, &st))
+    return rc;
   if (group)
     *group = st->group;
   if (packed)

@@ -4,23 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
-#include <initializer_list>
 #include <vector>
 
 #include "../../include/lk_engine.h"
-#include "lk_cell_grid.hpp"
-#include "lk_device.hpp"
-#include "lk_internal.hpp"
 #include "lk_launch.hpp"
+#include "lk_pass.hpp"
 #include "lk_track.hpp"
-
-#define TRCHK(call)                                                                                   \
-  do {                                                                                                \
-    hipError_t _e = (call);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return lk_internal_hipfail(e, _e, #call);                                                       \
-  } while (0)
 
 namespace {
 
@@ -30,61 +19,14 @@ namespace {
 // members (7.5 pitches).  The switch lies at twice the largest window measured; nothing above it has been timed.
 constexpr double kWideGroupFrom = 1024.0;
 
-struct TrackState {
+struct TrackState : LkPassState {
   LkDevBytes rec, pack, state, out, bbox;
   LkCellGridBufs grid;
-  float *h_bbox = nullptr; // pinned [4]
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;      // ev0 / ev1 bracket the device part of a finished call (read by lk_internal_track_last)
   int group = 0;
-  double members = 0;      // expected members of the 3 x 3 cells of the last call
+  double members = 0; // expected members of the 3 x 3 cells of the last call
 };
 
-int get_state(lk_engine *e, TrackState **out) {
-  void **slot = lk_internal_track_slot(e);
-  if (!*slot) {
-    TrackState *st = new TrackState();
-    hipError_t err = hipHostMalloc((void **)&st->h_bbox, 4 * sizeof(float), hipHostMallocDefault);
-    if (err == hipSuccess)
-      err = hipEventCreate(&st->ev0);
-    if (err == hipSuccess)
-      err = hipEventCreate(&st->ev1);
-    if (err != hipSuccess) {
-      lk_internal_track_release(st);
-      return lk_internal_hipfail(e, err, "hipHostMalloc / hipEventCreate (lk_track_points)");
-    }
-    *slot = st;
-  }
-  *out = (TrackState *)*slot;
-  return LK_ERROR_NONE;
-}
-
-// tuning experiments (scripts/track_bench.py): LK_TRACK_GROUP = 16 / 64 overrides the choice
-int env_group(int otherwise) {
-  const char *s = std::getenv("LK_TRACK_GROUP");
-  if (!s || !*s)
-    return otherwise;
-  const int v = std::atoi(s);
-  return v == 16 || v == 64 ? v : otherwise;
-}
-
 } // namespace
-
-void lk_internal_track_release(void *state) {
-  TrackState *st = (TrackState *)state;
-  if (!st)
-    return;
-  for (LkDevBytes *b : {&st->rec, &st->pack, &st->state, &st->out, &st->bbox, &st->grid.cell_of, &st->grid.start, &st->grid.cursor,
-                        &st->grid.unordered, &st->grid.members})
-    b->release();
-  if (st->h_bbox)
-    (void)hipHostFree(st->h_bbox);
-  if (st->ev0)
-    (void)hipEventDestroy(st->ev0);
-  if (st->ev1)
-    (void)hipEventDestroy(st->ev1);
-  delete st;
-}
 
 extern "C" {
 
@@ -124,8 +66,9 @@ int lk_track_points(lk_engine *e, const lk_track_config *cfg, int n_points, cons
   } else if (cfg->source == LK_TRACK_RECORDS_WINDOW && n_frames < 0) {
     return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_track_points: n_frames must be 0 or the window's frame count");
   }
-  LkTrackView v{};
-  if (int rc = lk_internal_track_view(e, cfg->source, &v))
+  LkPassView v{};
+  const unsigned need = cfg->source == LK_TRACK_RECORDS_ENGINE ? LK_VIEW_RECORDS : cfg->source == LK_TRACK_RECORDS_WINDOW ? LK_VIEW_WINDOW : 0u;
+  if (int rc = lk_internal_pass_view(e, "lk_track_points", need, -1, &v))
     return rc;
   if (cfg->source == LK_TRACK_RECORDS_WINDOW) {
     if (n_frames != 0 && n_frames != v.window_frames)
@@ -133,7 +76,7 @@ int lk_track_points(lk_engine *e, const lk_track_config *cfg, int n_points, cons
     n_frames = v.window_frames;
   }
   TrackState *st = nullptr;
-  if (int rc = get_state(e, &st))
+  if (int rc = lk_pass_state(e, LK_PASS_TRACK, "hipHostMalloc / hipEventCreate (lk_track_points)", &st))
     return rc;
   const size_t S = (size_t)v.S, F = (size_t)n_frames, Q = (size_t)n_points;
   std::vector<double> h_state(Q * 8);
@@ -147,28 +90,19 @@ int lk_track_points(lk_engine *e, const lk_track_config *cfg, int n_points, cons
         s[i] = state_inout[q * 8 + i];
     }
   }
-  TRCHK(st->pack.ensure(F * S * sizeof(float4)));
-  TRCHK(st->state.ensure(Q * 8 * sizeof(double)));
-  TRCHK(st->out.ensure(F * Q * sizeof(lk_track)));
-  TRCHK(st->bbox.ensure(4 * sizeof(float)));
+  LK_HIPCHK(st->pack.ensure(F * S * sizeof(float4)));
+  LK_HIPCHK(st->state.ensure(Q * 8 * sizeof(double)));
+  LK_HIPCHK(st->out.ensure(F * Q * sizeof(lk_track)));
+  LK_HIPCHK(st->bbox.ensure(4 * sizeof(float)));
   const lk_result *d_rec = cfg->source == LK_TRACK_RECORDS_WINDOW ? v.window : v.result;
-  if (records) {
-    TRCHK(st->rec.ensure(F * S * sizeof(lk_result)));
-    TRCHK(hipMemcpyAsync(st->rec.p, records, F * S * sizeof(lk_result), hipMemcpyHostToDevice, v.stream));
-    d_rec = st->rec.as<lk_result>();
-  }
-  TRCHK(hipMemcpyAsync(st->state.p, h_state.data(), Q * 8 * sizeof(double), hipMemcpyHostToDevice, v.stream)); // (pageable: staged before it returns)
-  st->timed = false;
-  TRCHK(hipEventRecord(st->ev0, v.stream));
-  // the centres' bounding box sizes the grid: the call's one round trip before the kernels
-  TRCHK(lk_launch_reseed_bbox(v.center, v.S, st->bbox.as<float>(), v.stream));
-  TRCHK(hipMemcpyAsync(st->h_bbox, st->bbox.p, 4 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
-  TRCHK(hipStreamSynchronize(v.stream));
-  if (!lk_cell_grid_bbox_finite(st->h_bbox))
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_track_points: a sector centre is not finite");
+  if (int rc = lk_pass_records(e, st->rec, records, F * S, v.stream, &d_rec))
+    return rc;
+  LK_HIPCHK(hipMemcpyAsync(st->state.p, h_state.data(), Q * 8 * sizeof(double), hipMemcpyHostToDevice, v.stream)); // (pageable: staged before it returns)
+  LK_HIPCHK(st->begin(v.stream));
   LkTrackArgs a{};
-  TRCHK(lk_cell_grid_build(st->grid, v.center, v.S, cfg->radius, st->h_bbox, v.stream, &a.grid));
-  TRCHK(lk_launch_track_prep(d_rec, v.center, v.S, n_frames, v.model, cfg->chi_max, st->pack.as<float4>(), v.stream));
+  if (int rc = lk_pass_grid(e, "lk_track_points", st, st->bbox, st->grid, v.center, v.S, cfg->radius, v.stream, &a.grid))
+    return rc;
+  LK_HIPCHK(lk_launch_track_prep(d_rec, v.center, v.S, n_frames, v.model, cfg->chi_max, st->pack.as<float4>(), v.stream));
   a.pack = st->pack.as<float4>();
   a.state = st->state.as<double>();
   a.out = st->out.as<lk_track>();
@@ -180,16 +114,17 @@ int lk_track_points(lk_engine *e, const lk_track_config *cfg, int n_points, cons
   a.mode = cfg->mode;
   a.radius = (double)cfg->radius;
   st->members = 9.0 * (double)v.S / ((double)a.grid.nx * (double)a.grid.ny);
-  st->group = env_group(st->members > kWideGroupFrom ? 64 : 16);
-  TRCHK(lk_launch_track(a, st->group, v.stream));
-  TRCHK(hipEventRecord(st->ev1, v.stream));
-  TRCHK(hipMemcpyAsync(h_state.data(), st->state.p, Q * 8 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-  TRCHK(hipMemcpyAsync(out, st->out.p, F * Q * sizeof(lk_track), hipMemcpyDeviceToHost, v.stream));
-  TRCHK(hipStreamSynchronize(v.stream));
+  // tuning experiments (scripts/track_bench.py): LK_TRACK_GROUP = 16 / 64 overrides the choice
+  st->group = lk_pass_env_choice("LK_TRACK_GROUP", 16, 64, st->members > kWideGroupFrom ? 64 : 16);
+  LK_HIPCHK(lk_launch_track(a, st->group, v.stream));
+  LK_HIPCHK(st->end(v.stream));
+  LK_HIPCHK(hipMemcpyAsync(h_state.data(), st->state.p, Q * 8 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+  LK_HIPCHK(hipMemcpyAsync(out, st->out.p, F * Q * sizeof(lk_track), hipMemcpyDeviceToHost, v.stream));
+  LK_HIPCHK(hipStreamSynchronize(v.stream));
   if (state_inout)
     for (size_t i = 0; i < Q * 8; ++i)
       state_inout[i] = h_state[i];
-  st->timed = true;
+  st->finished();
   return LK_ERROR_NONE;
 }
 
@@ -233,11 +168,9 @@ int lk_gauges_from_tracks(int n_frames, int n_points, const lk_track *tracks, in
 int lk_internal_track_last(lk_engine *e, float *device_ms, int *group, double *members) {
   if (!e)
     return LK_ERROR_BAD_DOMAIN;
-  TrackState *st = (TrackState *)*lk_internal_track_slot(e);
-  if (!st || !st->timed)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_internal_track_last: no lk_track_points yet");
-  if (device_ms)
-    TRCHK(hipEventElapsedTime(device_ms, st->ev0, st->ev1));
+  TrackState *st = nullptr;
+  if (int rc = lk_pass_last(e, LK_PASS_TRACK, "lk_internal_track_last: no lk_track_points yet", device_ms, &st))
+    return rc;
   if (group)
     *group = st->group;
   if (members)

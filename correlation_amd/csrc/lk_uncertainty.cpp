@@ -2,66 +2,23 @@
 // lk_uncertainty_from_sums).  The kernel is lk_uncertainty.hip; the record's arithmetic is lk_uncertainty.hpp.
 #include <hip/hip_runtime.h>
 
-#include <initializer_list>
 #include <vector>
 
 #include "../../include/lk_engine.h"
-#include "lk_cell_grid.hpp"
-#include "lk_device.hpp"
-#include "lk_internal.hpp"
 #include "lk_launch.hpp"
+#include "lk_pass.hpp"
 #include "lk_uncertainty.hpp"
-
-#define UNCHK(call)                                                                                   \
-  do {                                                                                                \
-    hipError_t _e = (call);                                                                           \
-    if (_e != hipSuccess)                                                                             \
-      return lk_internal_hipfail(e, _e, #call);                                                       \
-  } while (0)
 
 namespace {
 
-constexpr int kGroups[3] = {16, 64, 512};
-
-struct UncertaintyState {
+struct UncertaintyState : LkPassState {
   LkDevBytes rec, order, out, sums;
   std::vector<uint32_t> h_order;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false; // ev0 / ev1 bracket the kernels of a finished call (read by lk_internal_uncertainty_last)
   int count[3] = {0, 0, 0};
+  hipError_t init() { return LkPassState::init(false); } // (no cell grid: no bounding box to land)
 };
 
-int get_state(lk_engine *e, UncertaintyState **out) {
-  void **slot = lk_internal_uncertainty_slot(e);
-  if (!*slot) {
-    UncertaintyState *st = new UncertaintyState();
-    hipError_t err = hipEventCreate(&st->ev0);
-    if (err == hipSuccess)
-      err = hipEventCreate(&st->ev1);
-    if (err != hipSuccess) {
-      lk_internal_uncertainty_release(st);
-      return lk_internal_hipfail(e, err, "hipEventCreate (lk_parameter_uncertainty)");
-    }
-    *slot = st;
-  }
-  *out = (UncertaintyState *)*slot;
-  return LK_ERROR_NONE;
-}
-
 } // namespace
-
-void lk_internal_uncertainty_release(void *state) {
-  UncertaintyState *st = (UncertaintyState *)state;
-  if (!st)
-    return;
-  for (LkDevBytes *b : {&st->rec, &st->order, &st->out, &st->sums})
-    b->release();
-  if (st->ev0)
-    (void)hipEventDestroy(st->ev0);
-  if (st->ev1)
-    (void)hipEventDestroy(st->ev1);
-  delete st;
-}
 
 extern "C" {
 
@@ -79,37 +36,22 @@ int lk_parameter_uncertainty(lk_engine *e, const lk_uncertainty_config *cfg, con
     return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: no configuration");
   if (!out)
     return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_parameter_uncertainty: no output");
-  LkUncertaintyView v{};
-  if (int rc = lk_internal_uncertainty_view(e, records ? 0 : 1, cfg->def_slot, &v))
+  LkPassView v{};
+  if (int rc = lk_internal_pass_view(e, "lk_parameter_uncertainty", LK_VIEW_IMAGES | (records ? 0 : LK_VIEW_RECORDS), cfg->def_slot, &v))
     return rc;
   UncertaintyState *st = nullptr;
-  if (int rc = get_state(e, &st))
+  if (int rc = lk_pass_state(e, LK_PASS_UNCERTAINTY, "hipEventCreate (lk_parameter_uncertainty)", &st))
     return rc;
   const size_t n = (size_t)v.S;
-  // the sectors by lane group: from the level-0 sample count alone, as the backward solve's tables
-  st->h_order.resize(n);
-  size_t at = 0;
-  for (int g = 0; g < 3; ++g) {
-    const size_t begin = at;
-    for (int s = 0; s < v.S; ++s) {
-      const int4 r = v.h_rect0[s];
-      const int n0 = r.z > 0 ? r.w : (int)(v.h_off0[s + 1] - v.h_off0[s]);
-      if (lk_bw_group(n0) == kGroups[g])
-        st->h_order[at++] = (uint32_t)s;
-    }
-    st->count[g] = (int)(at - begin);
-  }
-  UNCHK(st->order.ensure(n * sizeof(uint32_t)));
-  UNCHK(st->out.ensure(n * sizeof(lk_uncertainty)));
+  lk_pass_order_by_group(v.h_rect0, v.h_off0, v.S, st->h_order, st->count);
+  LK_HIPCHK(st->order.ensure(n * sizeof(uint32_t)));
+  LK_HIPCHK(st->out.ensure(n * sizeof(lk_uncertainty)));
   if (sums_out)
-    UNCHK(st->sums.ensure(n * kLkUncSums * sizeof(double)));
-  UNCHK(hipMemcpyAsync(st->order.p, st->h_order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
+    LK_HIPCHK(st->sums.ensure(n * kLkUncSums * sizeof(double)));
+  LK_HIPCHK(hipMemcpyAsync(st->order.p, st->h_order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
   const lk_result *d_rec = v.result;
-  if (records) {
-    UNCHK(st->rec.ensure(n * sizeof(lk_result)));
-    UNCHK(hipMemcpyAsync(st->rec.p, records, n * sizeof(lk_result), hipMemcpyHostToDevice, v.stream));
-    d_rec = st->rec.as<lk_result>();
-  }
+  if (int rc = lk_pass_records(e, st->rec, records, n, v.stream, &d_rec))
+    return rc;
   LkUncertaintyArgs a{};
   a.und = v.und;
   a.def = v.def;
@@ -125,22 +67,21 @@ int lk_parameter_uncertainty(lk_engine *e, const lk_uncertainty_config *cfg, con
   a.out = st->out.as<lk_uncertainty>();
   a.sums = sums_out ? st->sums.as<double>() : nullptr;
   a.level = v.level;
-  st->timed = false;
-  UNCHK(hipEventRecord(st->ev0, v.stream));
+  LK_HIPCHK(st->begin(v.stream));
   const uint32_t *order = st->order.as<uint32_t>();
   for (int g = 0; g < 3; ++g) {
     a.order = order;
     a.n_sectors = st->count[g];
     if (a.n_sectors > 0)
-      UNCHK(lk_launch_uncertainty(a, v.model, v.interp, kGroups[g], v.stream));
+      LK_HIPCHK(lk_launch_uncertainty(a, v.model, v.interp, kLkPassGroups[g], v.stream));
     order += st->count[g];
   }
-  UNCHK(hipEventRecord(st->ev1, v.stream));
-  UNCHK(hipMemcpyAsync(out, st->out.p, n * sizeof(lk_uncertainty), hipMemcpyDeviceToHost, v.stream));
+  LK_HIPCHK(st->end(v.stream));
+  LK_HIPCHK(hipMemcpyAsync(out, st->out.p, n * sizeof(lk_uncertainty), hipMemcpyDeviceToHost, v.stream));
   if (sums_out)
-    UNCHK(hipMemcpyAsync(sums_out, st->sums.p, n * kLkUncSums * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-  UNCHK(hipStreamSynchronize(v.stream));
-  st->timed = true;
+    LK_HIPCHK(hipMemcpyAsync(sums_out, st->sums.p, n * kLkUncSums * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+  LK_HIPCHK(hipStreamSynchronize(v.stream));
+  st->finished();
   return LK_ERROR_NONE;
 }
 
@@ -148,11 +89,9 @@ int lk_parameter_uncertainty(lk_engine *e, const lk_uncertainty_config *cfg, con
 int lk_internal_uncertainty_last(lk_engine *e, float *device_ms, int *count3) {
   if (!e)
     return LK_ERROR_BAD_DOMAIN;
-  UncertaintyState *st = (UncertaintyState *)*lk_internal_uncertainty_slot(e);
-  if (!st || !st->timed)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_internal_uncertainty_last: no lk_parameter_uncertainty yet");
-  if (device_ms)
-    UNCHK(hipEventElapsedTime(device_ms, st->ev0, st->ev1));
+  UncertaintyState *st = nullptr;
+  if (int rc = lk_pass_last(e, LK_PASS_UNCERTAINTY, "lk_internal_uncertainty_last: no lk_parameter_uncertainty yet", device_ms, &st))
+    return rc;
   if (count3)
     for (int g = 0; g < 3; ++g)
       count3[g] = st->count[g];

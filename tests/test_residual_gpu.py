@@ -443,7 +443,7 @@ def test_arguments_and_refusals(pair):
             cfg.reserved[word] = 1
         rc = lib.lk_photometry(h, C.byref(cfg) if cfg is not None else None, ptr(records), ptr(output), None)
         msg = lib.lk_last_error_string(h).decode()
-        assert rc == ca.ERROR_BAD_DOMAIN, (rc, msg)
+        assert rc == ca.ERROR_BAD_DOMAIN and msg.startswith("lk_photometry: "), (rc, msg)   # names the function called
         return msg
 
     def mapped(cfg=None, records=None, outputs=maps, **kw):
@@ -453,7 +453,7 @@ def test_arguments_and_refusals(pair):
             cfg = _ffi.LkResidualMapConfig(**fields)
         rc = lib.lk_residual_map(h, C.byref(cfg) if cfg != "none" else None, ptr(records), *[ptr(o) for o in outputs])
         msg = lib.lk_last_error_string(h).decode()
-        assert rc == ca.ERROR_BAD_DOMAIN, (rc, msg)
+        assert rc == ca.ERROR_BAD_DOMAIN and msg.startswith("lk_residual_map: "), (rc, msg)   # names the function called
         return msg
 
     assert "no committed sectors" in photo(records=rec) and "no committed sectors" in mapped(records=rec)
@@ -487,5 +487,6 @@ def test_arguments_and_refusals(pair):
     e.close()
     bare = make_engine(None, None, rects)
     rc = bare.lib.lk_photometry(bare._h, C.byref(_ffi.LkPhotometryConfig(-1, 0.0)), ptr(rec), ptr(out), None)
-    assert rc == ca.ERROR_BAD_DOMAIN and "image" in bare.lib.lk_last_error_string(bare._h).decode()
+    msg = bare.lib.lk_last_error_string(bare._h).decode()
+    assert rc == ca.ERROR_BAD_DOMAIN and "image" in msg and msg.startswith("lk_photometry: "), (rc, msg)
     bare.close()
