@@ -14,67 +14,15 @@
 #include "lk_device.hpp"
 #include "lk_compose.hpp"
 #include "lk_launch.hpp"
-#include "lk_solver_common.hpp"
-
-#include <type_traits>
+#include "lk_sector_eval.hpp"
 
 namespace {
 
 constexpr int kBwLdsStride = 32; // floats per wavefront in the cross-wavefront reduction (22 used at most)
 
-struct BwLevel { // what a lane needs to know about its sector at the current level
-  gptr<uint8_t> und, def;
-  gptr<f32x2> xy; // explicit list (the reference's order), already offset to the sector's first sample
-  float4 *tpl;    // the sector's template slots
-  int rx, ry, rw; // implicit rectangle: first x, first y, width (rw == 0: explicit list)
-  int n;
-  int urows, ucols, drows, dcols;
-  float cx, cy, inv_w;
+struct BwLevel : SectorLevel {
+  float4 *tpl; // the sector's template slots
 };
-
-__device__ __forceinline__ BwLevel bw_level(const LkLevelView *lvs, float4 *tpl, int s, int level, float2 c0) {
-  const LkLevelView &lv = lvs[level];
-  BwLevel c;
-  const int4 rc = lv.rect[s];
-  const uint32_t off = lv.off[s];
-  c.und = (gptr<uint8_t>)lv.und;
-  c.def = (gptr<uint8_t>)lv.def;
-  c.xy = (gptr<f32x2>)(lv.xy + off);
-  c.tpl = tpl;
-  c.rx = rc.x;
-  c.ry = rc.y;
-  c.rw = rc.z;
-  c.n = rc.z > 0 ? rc.w : (int)(lv.off[s + 1] - off);
-  c.urows = lv.urows;
-  c.ucols = lv.ucols;
-  c.drows = lv.drows;
-  c.dcols = lv.dcols;
-  const float inv = 1.f / (float)(1 << level); // pyramid_class.cpp:357-361, as the forward kernels
-  c.cx = level == 0 ? c0.x : c0.x * inv;
-  c.cy = level == 0 ? c0.y : c0.y * inv;
-  c.inv_w = c.rw > 0 ? 1.f / (float)c.rw : 0.f;
-  return c;
-}
-
-// sample k of the sector: implicit rectangles row by row (neighbouring lanes read neighbouring pixels), lists in their order
-__device__ __forceinline__ f32x2 bw_coords(const BwLevel &c, int k) {
-  if (c.rw > 0) {
-    int row = (int)((float)k * c.inv_w);
-    int col = k - row * c.rw;
-    if (col < 0) {
-      col += c.rw;
-      --row;
-    } else if (col >= c.rw) {
-      col -= c.rw;
-      ++row;
-    }
-    f32x2 q;
-    q.x = (float)(c.rx + col);
-    q.y = (float)(c.ry + row);
-    return q;
-  }
-  return c.xy[k];
-}
 
 // Sum of N values over the group; every lane of the group ends with the same bits.  GROUP <= 64 uses no barrier (the rows
 // of a wavefront may be at different points of their sectors' solves); GROUP == 512 is the whole (uniform) workgroup.
@@ -134,7 +82,7 @@ __device__ __forceinline__ bool bw_template(const BwLevel &c, int lane, float (&
     v[i] = 0.f;
   const int umaxr = c.urows - 1, umaxc = c.ucols - 1;
   for (int k = lane; k < c.n; k += GROUP) {
-    const f32x2 q = bw_coords(c, k);
+    const f32x2 q = sector_sample(c, k);
     int uix = (int)(q.x + 0.5f), uiy = (int)(q.y + 0.5f); // the node the forward residual reads
     uix = min(max(uix, 0), umaxc);                          // (memory safety only; valid lists never clamp)
     uiy = min(max(uiy, 0), umaxr);
@@ -173,7 +121,7 @@ __device__ __forceinline__ bool bw_evaluate(const BwLevel &c, int lane, const fl
   for (int i = 0; i < P + 2; ++i)
     v[i] = 0.f;
   for (int k = lane; k < c.n; k += GROUP) {
-    const f32x2 q = bw_coords(c, k);
+    const f32x2 q = sector_sample(c, k);
     float xd, yd, dx = 0.f, dy = 0.f;
     Warp<MODEL>::apply(q.x, q.y, c.cx, c.cy, p, xd, yd, dx, dy);
     const float4 t = c.tpl[k];
@@ -254,7 +202,8 @@ __global__ void __launch_bounds__(GROUP <= 64 ? 256 : GROUP) lk_backward_kernel(
     error = LK_ERROR_NONE;
     lambda = 0.0001f;
     lg_chi = FLT_MAX;
-    const BwLevel c = bw_level(a.lv, tpl, s, level, c0);
+    BwLevel c = sector_level<BwLevel>(a.lv[level], s, level, c0);
+    c.tpl = tpl;
     const float scaling = 1.f / ((float)c.n);
     const bool starved = c.n <= a.starved_max;
     if (bw_template<MODEL, INTERP, GROUP>(c, lane, H, lds)) {
@@ -399,7 +348,8 @@ __global__ void __launch_bounds__(GROUP) lk_backward_eval_kernel(LkBackwardEvalA
   constexpr int P = n_params(MODEL), NA = P * (P + 1) / 2;
   __shared__ float lds[(GROUP > 64 ? GROUP / kWave : 1) * kBwLdsStride];
   const int lane = (int)threadIdx.x;
-  const BwLevel c = bw_level(a.lv, a.tpl, a.sector, a.level, a.center[a.sector]);
+  BwLevel c = sector_level<BwLevel>(a.lv[a.level], a.sector, a.level, a.center[a.sector]);
+  c.tpl = a.tpl;
   float H[NA], b[P], chi;
   const bool tbad = bw_template<MODEL, INTERP, GROUP>(c, lane, H, lds);
   float p[6];
@@ -424,66 +374,19 @@ __global__ void __launch_bounds__(GROUP) lk_backward_eval_kernel(LkBackwardEvalA
   }
 }
 
-template <int MODEL, int INTERP>
-hipError_t launch_bw_mi(const LkBackwardArgs &a, int group, hipStream_t st) {
-  const int per_block = group <= 64 ? 256 / group : 1;
-  const int blocks = (a.n_sectors + per_block - 1) / per_block;
-  if (blocks <= 0)
-    return hipSuccess;
-  if (group == 16)
-    hipLaunchKernelGGL((lk_backward_kernel<MODEL, INTERP, 16>), dim3(blocks), dim3(256), 0, st, a);
-  else if (group == 64)
-    hipLaunchKernelGGL((lk_backward_kernel<MODEL, INTERP, 64>), dim3(blocks), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((lk_backward_kernel<MODEL, INTERP, 512>), dim3(blocks), dim3(512), 0, st, a);
-  return hipGetLastError();
-}
-
-template <int MODEL, int INTERP>
-hipError_t launch_bw_eval_mi(const LkBackwardEvalArgs &a, int group, hipStream_t st) {
-  if (group == 16)
-    hipLaunchKernelGGL((lk_backward_eval_kernel<MODEL, INTERP, 16>), dim3(1), dim3(16), 0, st, a);
-  else if (group == 64)
-    hipLaunchKernelGGL((lk_backward_eval_kernel<MODEL, INTERP, 64>), dim3(1), dim3(64), 0, st, a);
-  else
-    hipLaunchKernelGGL((lk_backward_eval_kernel<MODEL, INTERP, 512>), dim3(1), dim3(512), 0, st, a);
-  return hipGetLastError();
-}
-
-template <class F> hipError_t bw_dispatch_interp(int interp, F &&f) {
-  switch (interp) {
-  case LK_IM_NEAREST: return f(std::integral_constant<int, LK_IM_NEAREST>{});
-  case LK_IM_BILINEAR: return f(std::integral_constant<int, LK_IM_BILINEAR>{});
-  case LK_IM_BICUBIC: return f(std::integral_constant<int, LK_IM_BICUBIC>{});
-  default: return f(std::integral_constant<int, LK_IM_BICUBIC_SEPARABLE>{});
-  }
-}
-
 } // namespace
 
 hipError_t lk_launch_backward(const LkBackwardArgs &a, int model, int interp, int group, hipStream_t st) {
-  auto go = [&](auto m) {
-    constexpr int M = decltype(m)::value;
-    return bw_dispatch_interp(interp, [&](auto i) { return launch_bw_mi<M, decltype(i)::value>(a, group, st); });
-  };
-  switch (model) {
-  case LK_FM_U: return go(std::integral_constant<int, LK_FM_U>{});
-  case LK_FM_UV: return go(std::integral_constant<int, LK_FM_UV>{});
-  case LK_FM_UVQ: return go(std::integral_constant<int, LK_FM_UVQ>{});
-  default: return go(std::integral_constant<int, LK_FM_UVUXUYVXVY>{});
-  }
+  return dispatch_sector_kernel(model, interp, group, [&](auto m, auto i, auto g) {
+    constexpr int M = decltype(m)::value, I = decltype(i)::value, G = decltype(g)::value;
+    return launch_sector_groups<G>(lk_backward_kernel<M, I, G>, a, a.n_sectors, st);
+  });
 }
 
 hipError_t lk_launch_backward_eval(const LkBackwardEvalArgs &a, int model, int interp, int group, hipStream_t st) {
-  auto go = [&](auto m) {
-    constexpr int M = decltype(m)::value;
-    return bw_dispatch_interp(interp,
-                                                      [&](auto i) { return launch_bw_eval_mi<M, decltype(i)::value>(a, group, st); });
-  };
-  switch (model) {
-  case LK_FM_U: return go(std::integral_constant<int, LK_FM_U>{});
-  case LK_FM_UV: return go(std::integral_constant<int, LK_FM_UV>{});
-  case LK_FM_UVQ: return go(std::integral_constant<int, LK_FM_UVQ>{});
-  default: return go(std::integral_constant<int, LK_FM_UVUXUYVXVY>{});
-  }
+  return dispatch_sector_kernel(model, interp, group, [&](auto m, auto i, auto g) {
+    constexpr int M = decltype(m)::value, I = decltype(i)::value, G = decltype(g)::value;
+    hipLaunchKernelGGL((lk_backward_eval_kernel<M, I, G>), dim3(1), dim3(G), 0, st, a);
+    return hipGetLastError();
+  });
 }

@@ -293,7 +293,7 @@ struct LkStrainArgs {
   LkReseedGrid grid;
   const float2 *center;  // [S]
   const lk_result *rec;  // [S]
-  const uint8_t *good;   // [S] the good rule, evaluated once per call (lk_strain_prep_kernel)
+  const uint8_t *good;   // [S] the good rule, evaluated once per call (lk_pack_prep_kernel)
   const float4 *pack;    // [S] {cx, cy, u, v} of a good sector, cx = NaN for a failed one (the packed variants)
   lk_strain *out;        // [S]
   int n_sectors, has_v, min_neighbours, tensor;
@@ -304,7 +304,7 @@ struct LkStrainArgs {
 // points' own positions, frame after frame of one call, on the recovery pass's cell grid.
 struct LkTrackArgs {
   LkReseedGrid grid;     // over the centres: the same in every frame of the call
-  const float4 *pack;    // [F][S] {cx, cy, u, v} of a good sector, cx = NaN for one that is not (lk_track_prep_kernel)
+  const float4 *pack;    // [F][S] {cx, cy, u, v} of a good sector, cx = NaN for one that is not (lk_pack_prep_kernel)
   double *state;         // [Q][8] {X, Y, x, y, Fxx, Fxy, Fyx, Fyy}: read before frame 0, written after the last frame
   lk_track *out;         // [F][Q]
   int n_points, n_frames, n_sectors, min_neighbours, tensor, mode;
@@ -315,7 +315,7 @@ struct LkTrackArgs {
 struct LkOutlierArgs {
   LkReseedGrid grid;
   const float2 *center;  // [S]
-  const uint8_t *good;   // [S] the good rule, evaluated once per call (lk_outlier_prep_kernel)
+  const uint8_t *good;   // [S] the good rule, evaluated once per call (lk_pack_prep_kernel)
   const float4 *pack;    // [S] {cx, cy, u, v}; cx = NaN for a sector that is not good or was flagged in the pass before
   lk_outlier *out;       // [S]
   int n_sectors, min_neighbours, detrend;
@@ -325,10 +325,11 @@ struct LkOutlierArgs {
 };
 constexpr int kLkOutlierRows = 16;
 
-// Per-sector uncertainty (lk_uncertainty.hip, include/lk_engine.h: lk_parameter_uncertainty): one evaluation of every
-// sector at its record's parameters, at pyramid level `level` (the finest level the solve reaches).  The images, lists and
-// rectangles are that level's (LkLevelView's fields; `def` may be a ring slot's pyramid).
-struct LkUncertaintyArgs {
+// What a pass that evaluates every sector once at its record's parameters reads (lk_sector_eval.hpp; filled from the
+// engine's view by lk_pass_sector_eval, lk_pass.hpp): the images, lists and rectangles of one pyramid level - the finest
+// level the solve reaches - under LkLevelView's names (`def` may be a ring slot's pyramid), the centres, the records, and
+// the sectors of one launch.
+struct LkSectorEvalArgs {
   const uint8_t *und, *def; // level-L images, pitch == cols
   int urows, ucols, drows, dcols;
   const float2 *xy;         // level-L lists in the reference's order, [S+1] offsets, [S] implicit rectangles
@@ -337,22 +338,20 @@ struct LkUncertaintyArgs {
   const float2 *center;     // [S] level-0 centres
   const lk_result *rec;     // [S]
   const uint32_t *order;    // [n_sectors] the sectors of this launch (one lane group's)
+};
+
+// Per-sector uncertainty (lk_uncertainty.hip, include/lk_engine.h: lk_parameter_uncertainty).
+struct LkUncertaintyArgs {
+  LkSectorEvalArgs ev;
   lk_uncertainty *out;      // [S]
   double *sums;             // [S][28] or null: A (upper triangle, row-major), b, chi in the layout of Sums<P>, then zeros
   int n_sectors, level;
 };
 
-// Photometry (lk_residual.hip, include/lk_engine.h: lk_photometry): one evaluation of every good sector at its record's
-// parameters, at pyramid level `level` - LkUncertaintyArgs's walk with the grey-value sums instead of the normal matrix.
+// Photometry (lk_residual.hip, include/lk_engine.h: lk_photometry): the same walk with the grey-value sums instead of the
+// normal matrix, over the good sectors.
 struct LkPhotometryArgs {
-  const uint8_t *und, *def; // level-L images, pitch == cols
-  int urows, ucols, drows, dcols;
-  const float2 *xy;         // level-L lists in the reference's order, [S+1] offsets, [S] implicit rectangles
-  const uint32_t *off;
-  const int4 *rect;
-  const float2 *center;     // [S] level-0 centres
-  const lk_result *rec;     // [S]
-  const uint32_t *order;    // [n_sectors] the sectors of this launch (one lane group's)
+  LkSectorEvalArgs ev;
   struct lk_photometry *out; // [S]
   double *sums;             // [S][8] or null (lk_residual.hpp: kLkPhotoSums)
   int n_sectors, level;

@@ -90,10 +90,12 @@ hipError_t lk_launch_reseed_plan(const LkReseedPlanArgs &a, hipStream_t st);
 hipError_t lk_launch_reseed_compact(const LkReseedCompactArgs &a, hipStream_t st);
 hipError_t lk_launch_reseed_merge(const LkReseedMergeArgs &a, hipStream_t st);
 
-// ---- lk_strain.hip: the strain field (lk_strain_field)
-// good[s] by the recovery pass's rule and pack[s] = {cx, cy, u, v} (cx = NaN for a failed sector; v = 0 without one)
-hipError_t lk_launch_strain_prep(const lk_result *rec, const float2 *center, int n_sectors, int model, float chi_max,
-                                 uint8_t *good, float4 *pack, hipStream_t st);
+// ---- lk_strain.hip: the strain field (lk_strain_field), and the pack of every pass that fits its plane
+// for the n_frames * n_sectors records of a call: good[f * S + s] (where good is not null) by the shared good rule and
+// pack[f * S + s] = {cx, cy, u, v} (cx = NaN for a sector that is not good; v = 0 without one); canonical_zero != 0: u + 0
+// and v + 0, so that a -0 is packed as +0
+hipError_t lk_launch_pack_prep(const lk_result *rec, const float2 *center, int n_sectors, int n_frames, int model, float chi_max,
+                               int canonical_zero, uint8_t *good, float4 *pack, hipStream_t st);
 // group: 16 or 64 lanes per sector; packed != 0: the neighbours' data come from a.pack, else from a.center / a.good / a.rec
 hipError_t lk_launch_strain(const LkStrainArgs &a, int group, int packed, hipStream_t st);
 
@@ -102,9 +104,6 @@ hipError_t lk_launch_strain(const LkStrainArgs &a, int group, int packed, hipStr
 hipError_t lk_launch_uncertainty(const LkUncertaintyArgs &a, int model, int interp, int group, hipStream_t st);
 
 // ---- lk_outlier.hip: the outlier flags (lk_flag_outliers)
-// good[s] by the shared rule and pack[s] = {cx, cy, u + 0, v + 0} (cx = NaN for a sector that is not good; v = 0 without one)
-hipError_t lk_launch_outlier_prep(const lk_result *rec, const float2 *center, int n_sectors, int model, float chi_max,
-                                  uint8_t *good, float4 *pack, hipStream_t st);
 // between two passes: pack[s].x = NaN for a sector that is not good or that `flags` (the pass before) has flagged, else cx
 hipError_t lk_launch_outlier_exclude(const lk_outlier *flags, const float2 *center, const uint8_t *good, int n_sectors,
                                      float4 *pack, hipStream_t st);
@@ -114,10 +113,6 @@ hipError_t lk_launch_outlier(const LkOutlierArgs &a, int group, hipStream_t st);
 hipError_t lk_launch_outlier_mark(const lk_outlier *flags, int n_sectors, lk_result *rec, hipStream_t st);
 
 // ---- lk_track.hip: material-point tracks (lk_track_points)
-// pack[f * S + s] = {cx, cy, u, v} of record f * S + s by the shared good rule (cx = NaN for a sector that is not good;
-// v = 0 without one), for the n_frames * n_sectors records of a call
-hipError_t lk_launch_track_prep(const lk_result *rec, const float2 *center, int n_sectors, int n_frames, int model, float chi_max,
-                                float4 *pack, hipStream_t st);
 // every point through every frame in one launch; group: 16 or 64 lanes per point
 hipError_t lk_launch_track(const LkTrackArgs &a, int group, hipStream_t st);
 

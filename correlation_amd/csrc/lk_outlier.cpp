@@ -95,7 +95,7 @@ int lk_flag_outliers(lk_engine *e, const lk_outlier_config *cfg, const lk_result
   LkOutlierArgs a{};
   if (int rc = lk_pass_grid(e, "lk_flag_outliers", st, st->bbox, st->grid, v.center, v.S, cfg->radius, v.stream, &a.grid))
     return rc;
-  LK_HIPCHK(lk_launch_outlier_prep(d_rec, v.center, v.S, v.model, cfg->chi_max, st->good.as<uint8_t>(), st->pack.as<float4>(), v.stream));
+  LK_HIPCHK(lk_launch_pack_prep(d_rec, v.center, v.S, 1, v.model, cfg->chi_max, 1, st->good.as<uint8_t>(), st->pack.as<float4>(), v.stream));
   a.center = v.center;
   a.good = st->good.as<uint8_t>();
   a.pack = st->pack.as<float4>();

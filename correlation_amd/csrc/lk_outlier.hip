@@ -3,10 +3,10 @@
 // Per sector s: the (detrended) normalised median test of its displacement against the good sectors within `radius` of
 // c_s, s itself left out.  The neighbours are found as lk_strain.hip finds them: the recovery pass's cell grid (cell size =
 // radius), a lane group per sector, three cell rows, GROUP candidates at a time.
-//   prep     a thread per sector: the good rule once per record, {cx, cy, u + 0, v + 0} packed into 16 bytes (cx = NaN marks
-//            a sector that is not in anybody's window - it fails the distance test by itself)
+//   prep     lk_strain.hip's pack with the canonical zero: the good rule once per record, {cx, cy, u + 0, v + 0} packed
+//            into 16 bytes (cx = NaN marks a sector that is not in anybody's window - it fails the distance test by itself)
 //   exclude  between two passes: the NaN marks rewritten from the good flags and the flags of the pass before
-//   outlier  walk 1: the count and (detrend) the 11 plane sums, joined by the strain kernel's butterfly; status and plane
+//   outlier  walk 1: the count and (detrend) the 11 plane sums, joined by their butterfly (lk_neighbours.hpp); status and plane
 //            alike in every lane.  Walk 2: the floats e_j of both components.  Then the selections of lk_outlier.hpp - four
 //            medians (med and mad of u and v) in 2 x 33 counting rounds, u and v sharing a round - and the ratios.
 //   mark     errorCode = LK_ERROR_OUTLIER in the records of the flagged sectors
@@ -22,26 +22,12 @@
 #include <stdint.h>
 
 #include "lk_device.hpp"
-#include "lk_good.hpp"
 #include "lk_launch.hpp"
+#include "lk_neighbours.hpp"
 #include "lk_outlier.hpp"
+#include "lk_strain.hpp"
 
 namespace {
-
-constexpr int kBlock = 256;
-
-__global__ __launch_bounds__(kBlock) void lk_outlier_prep_kernel(const lk_result *rec, const float2 *center, int n, int model,
-                                                                 float chi_max, uint8_t *good, float4 *pack) {
-  const int s = (int)(blockIdx.x * kBlock + threadIdx.x);
-  if (s >= n)
-    return;
-  const lk_result r = rec[s];
-  const bool g = reseed_good(r, n_params_of(model), chi_max);
-  const float2 c = center[s];
-  good[s] = g ? 1 : 0;
-  pack[s] = make_float4(g ? c.x : __uint_as_float(0x7fc00000u), c.y, r.resultingParameters[0] + 0.0f,
-                        model == LK_FM_U ? 0.f : r.resultingParameters[1] + 0.0f);
-}
 
 __global__ __launch_bounds__(kBlock) void lk_outlier_exclude_kernel(const lk_outlier *flags, const float2 *center,
                                                                     const uint8_t *good, int n, float4 *pack) {
@@ -68,7 +54,8 @@ struct Plane {
 // The window of one sector as its lane group sees it (lk_outlier.hpp: Src).
 template <int GROUP> struct GroupWindow {
   const LkOutlierArgs &a;
-  int s = 0, lane = 0, x_lo = 0, x_hi = 0, y_lo = 0, y_hi = 0;
+  int s = 0, lane = 0;
+  CellRange cells = {0, 0, 0, -1};
   float2 cs = {0.f, 0.f};
   double r2 = 0;
   bool detrend = false, stashed = false;
@@ -80,22 +67,14 @@ template <int GROUP> struct GroupWindow {
 
   // every member of the window this lane is dealt: f(dx, dy, u, v)
   template <class F> __device__ inline void walk(F f) const {
-    const LkReseedGrid &g = a.grid;
-    const uint32_t S = (uint32_t)a.n_sectors;
-    for (int yy = y_lo; yy <= y_hi; ++yy) {
-      const uint32_t b = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_lo];
-      uint32_t e = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_hi + 1];
-      e = e < S ? e : S;
-      for (uint32_t k = b + (uint32_t)lane; k < e; k += GROUP) {
-        const uint32_t m = g.members[k];
-        if (m >= S || m == (uint32_t)s)
-          continue;
-        const float4 q = a.pack[m];
-        const double dx = (double)q.x - (double)cs.x, dy = (double)q.y - (double)cs.y;
-        if (dx * dx + dy * dy <= r2) // (a NaN centre - not good, or excluded - is outside)
-          f(dx, dy, (double)q.z, (double)q.w);
-      }
-    }
+    walk_members<GROUP>(a.grid, cells, (uint32_t)a.n_sectors, lane, [&](uint32_t m) {
+      if (m == (uint32_t)s)
+        return;
+      const float4 q = a.pack[m];
+      const double dx = (double)q.x - (double)cs.x, dy = (double)q.y - (double)cs.y;
+      if (dx * dx + dy * dy <= r2) // (a NaN centre - not good, or excluded - is outside)
+        f(dx, dy, (double)q.z, (double)q.w);
+    });
   }
   __device__ inline float e_u(double dx, double dy, double u) const {
     return detrend ? (float)(u - (pl.u0 + pl.ux * dx + pl.uy * dy)) + 0.0f : (float)u;
@@ -154,50 +133,22 @@ template <int GROUP> __global__ __launch_bounds__(kBlock) void lk_outlier_kernel
   if (row >= (unsigned long long)a.n_sectors)
     return; // (the whole group leaves together; no barrier follows)
   const int s = (int)row;
-  const LkReseedGrid &g = a.grid;
-  const int cell = (int)g.cell_of[s], ix = cell % g.nx, iy = cell / g.nx;
   GroupWindow<GROUP> w{a};
   w.s = s, w.lane = lane;
-  w.x_lo = ix > 0 ? ix - 1 : 0, w.x_hi = ix + 1 < g.nx ? ix + 1 : g.nx - 1;
-  w.y_lo = iy > 0 ? iy - 1 : 0, w.y_hi = iy + 1 < g.ny ? iy + 1 : g.ny - 1;
+  w.cells = cell_range_of(a.grid, s);
   w.cs = a.center[s];
   w.r2 = a.radius * a.radius;
   w.detrend = a.detrend != 0;
 
   // walk 1: the count, this lane's share of it, and the plane's sums
-  double Sx = 0, Sy = 0, Sxx = 0, Sxy = 0, Syy = 0, Su = 0, Sxu = 0, Syu = 0, Sv = 0, Sxv = 0, Syv = 0;
-  int mine = 0;
-  if (w.detrend) {
-    w.walk([&](double x, double y, double u, double v) {
-      Sx += x;
-      Sy += y;
-      Sxx += x * x;
-      Sxy += x * y;
-      Syy += y * y;
-      Su += u;
-      Sxu += x * u;
-      Syu += y * u;
-      Sv += v;
-      Sxv += x * v;
-      Syv += y * v;
-      ++mine;
-    });
-    for (int m = GROUP / 2; m >= 1; m >>= 1) {
-      Sx += __shfl_xor(Sx, m, GROUP);
-      Sy += __shfl_xor(Sy, m, GROUP);
-      Sxx += __shfl_xor(Sxx, m, GROUP);
-      Sxy += __shfl_xor(Sxy, m, GROUP);
-      Syy += __shfl_xor(Syy, m, GROUP);
-      Su += __shfl_xor(Su, m, GROUP);
-      Sxu += __shfl_xor(Sxu, m, GROUP);
-      Syu += __shfl_xor(Syu, m, GROUP);
-      Sv += __shfl_xor(Sv, m, GROUP);
-      Sxv += __shfl_xor(Sxv, m, GROUP);
-      Syv += __shfl_xor(Syv, m, GROUP);
-    }
-  } else {
-    w.walk([&](double, double, double, double) { ++mine; });
-  }
+  PlaneSums sums;
+  if (w.detrend)
+    w.walk([&](double x, double y, double u, double v) { sums.add(x, y, u, v); });
+  else
+    w.walk([&](double, double, double, double) { ++sums.n; });
+  const int mine = sums.n;
+  if (w.detrend)
+    sums.template join<GROUP>();
   int cnt = mine, most = mine;
   for (int m = GROUP / 2; m >= 1; m >>= 1) {
     cnt += __shfl_xor(cnt, m, GROUP);
@@ -210,19 +161,12 @@ template <int GROUP> __global__ __launch_bounds__(kBlock) void lk_outlier_kernel
   if (cnt < a.min_neighbours) {
     status = LK_OUTLIER_TOO_FEW;
   } else if (w.detrend) {
-    // moments, status, plane: the same bits in every lane of the group (lk_strain.hip)
-    const double n = (double)cnt;
-    const double Cxx = Sxx - Sx * Sx / n, Cxy = Sxy - Sx * Sy / n, Cyy = Syy - Sy * Sy / n;
-    const double Cxu = Sxu - Sx * Su / n, Cyu = Syu - Sy * Su / n, Cxv = Sxv - Sx * Sv / n, Cyv = Syv - Sy * Sv / n;
-    const double CC = Cxx * Cyy, D = CC - Cxy * Cxy;
-    if (CC == 0.0 || !(D > 1e-6 * CC)) {
+    // moments, status, plane: the same bits in every lane of the group
+    const LkPlaneFit pf = lk_plane_fit(cnt, sums.s);
+    if (pf.CC == 0.0 || !(pf.D > 1e-6 * pf.CC))
       status = LK_OUTLIER_DEGENERATE;
-    } else {
-      w.pl.ux = (Cyy * Cxu - Cxy * Cyu) / D, w.pl.uy = (Cxx * Cyu - Cxy * Cxu) / D;
-      w.pl.vx = (Cyy * Cxv - Cxy * Cyv) / D, w.pl.vy = (Cxx * Cyv - Cxy * Cxv) / D;
-      w.pl.u0 = Su / n - w.pl.ux * (Sx / n) - w.pl.uy * (Sy / n);
-      w.pl.v0 = Sv / n - w.pl.vx * (Sx / n) - w.pl.vy * (Sy / n);
-    }
+    else
+      w.pl = Plane{pf.u0, pf.ux, pf.uy, pf.v0, pf.vx, pf.vy};
   }
   lk_outlier rec{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, cnt, status};
   if (status == LK_OUTLIER_OK) { // (uniform over the group)
@@ -263,18 +207,7 @@ template <int GROUP> __global__ __launch_bounds__(kBlock) void lk_outlier_kernel
   o[1] = make_float4(rec.ratio_u, rec.ratio_v, __int_as_float(rec.neighbours), __int_as_float(rec.status));
 }
 
-inline unsigned blocks_for(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
 } // namespace
-
-hipError_t lk_launch_outlier_prep(const lk_result *rec, const float2 *center, int n_sectors, int model, float chi_max,
-                                  uint8_t *good, float4 *pack, hipStream_t st) {
-  if (n_sectors <= 0)
-    return hipSuccess;
-  hipLaunchKernelGGL(lk_outlier_prep_kernel, dim3(blocks_for(n_sectors, kBlock)), dim3(kBlock), 0, st, rec, center, n_sectors,
-                     model, chi_max, good, pack);
-  return hipGetLastError();
-}
 
 hipError_t lk_launch_outlier_exclude(const lk_outlier *flags, const float2 *center, const uint8_t *good, int n_sectors,
                                      float4 *pack, hipStream_t st) {

@@ -1,8 +1,8 @@
 // lk_pass.hpp - the host plumbing the add-on passes share (lk_reseed.cpp, lk_strain.cpp, lk_uncertainty.cpp, lk_outlier.cpp,
 // lk_track.cpp, lk_residual.cpp; the error macro also lk_guess_search.cpp): device buffers that free themselves, the state a
 // pass keeps on its slot of the engine, the upload of caller records, the bounding box and cell grid over the centres, the
-// order of the sectors by lane group.  Host only: no .hip file includes it.  A new pass starts here ("adding a
-// pass").
+// order of the sectors by lane group.  Host only: no .hip file includes it; the device half is lk_neighbours.hpp and
+// lk_sector_eval.hpp.  A new pass starts here ("adding a pass").
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -151,6 +151,24 @@ inline void lk_pass_order_by_group(const int4 *h_rect0, const uint32_t *h_off0, 
     }
     count[g] = (int)(at - begin);
   }
+}
+
+// What the kernels of lk_sector_eval.hpp read of the view (LK_VIEW_IMAGES), for the records d_rec; the caller sets `order`
+// per launch.
+inline LkSectorEvalArgs lk_pass_sector_eval(const LkPassView &v, const lk_result *d_rec) {
+  LkSectorEvalArgs a{};
+  a.und = v.und;
+  a.def = v.def;
+  a.urows = v.urows;
+  a.ucols = v.ucols;
+  a.drows = v.drows;
+  a.dcols = v.dcols;
+  a.xy = v.xy;
+  a.off = v.off;
+  a.rect = v.rect;
+  a.center = v.center;
+  a.rec = d_rec;
+  return a;
 }
 
 // an environment variable that chooses between a and b (tuning experiments and test hooks); anything else: `otherwise`

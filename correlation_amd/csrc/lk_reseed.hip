@@ -17,13 +17,12 @@
 #include <stdint.h>
 
 #include "lk_device.hpp"
-#include "lk_good.hpp"
 #include "lk_launch.hpp"
+#include "lk_neighbours.hpp"
 
 namespace {
 
 constexpr int kWave = 64;
-constexpr int kBlock = 256;
 constexpr int kWide = 1024; // the one-workgroup kernels (bounding box, scan, compaction)
 
 // ---- bounding box of the centres: one workgroup, {min x, min y, max x, max y} ---------------------------------------
@@ -87,11 +86,6 @@ __global__ __launch_bounds__(kBlock) void lk_reseed_classify_kernel(const lk_res
 }
 
 // ---- cell grid ---------------------------------------------------------------------------------------------------------
-__device__ inline int cell_coord(double v, double origin, double cell, int n) {
-  const double q = floor((v - origin) / cell);
-  return q >= (double)(n - 1) ? n - 1 : (q > 0.0 ? (int)q : 0); // (a NaN lands in cell 0)
-}
-
 __global__ __launch_bounds__(kBlock) void lk_reseed_cell_count_kernel(const float2 *center, int n, double x0, double y0,
                                                                       double cell, int nx, int ny, uint32_t *cell_of,
                                                                       uint32_t *count) {
@@ -187,38 +181,31 @@ __global__ __launch_bounds__(kBlock) void lk_reseed_plan_kernel(LkReseedPlanArgs
   }
   const LkReseedGrid &g = a.grid;
   const float2 cs = a.center[s];
-  const int cell = (int)g.cell_of[s], ix = cell % g.nx, iy = cell / g.nx;
-  const int x_lo = ix > 0 ? ix - 1 : 0, x_hi = ix + 1 < g.nx ? ix + 1 : g.nx - 1;
-  const int y_lo = iy > 0 ? iy - 1 : 0, y_hi = iy + 1 < g.ny ? iy + 1 : g.ny - 1;
   const double r2 = a.radius * a.radius;
   double acc[6] = {0, 0, 0, 0, 0, 0};
   int cnt = 0;
-  for (int yy = y_lo; yy <= y_hi; ++yy) {
-    const uint32_t b = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_lo], e = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_hi + 1];
-    for (uint32_t k = b + (uint32_t)lane; k < e; k += kLkReseedGroup) {
-      const uint32_t m = g.members[k];
-      if (m >= (uint32_t)a.n_sectors || !a.good[m])
-        continue;
-      const float2 cn = a.center[m];
-      const double dx = (double)cs.x - (double)cn.x, dy = (double)cs.y - (double)cn.y;
-      if (!(dx * dx + dy * dy <= r2))
-        continue;
-      const float *p = a.rec[m].resultingParameters;
-      double q[6] = {0, 0, 0, 0, 0, 0};
-      for (int i = 0; i < P; ++i)
-        q[i] = (double)p[i];
-      if (a.model == LK_FM_UVUXUYVXVY) { // (lk_guess_kernel's rule, manager_class.cpp:2602-2707)
-        q[0] = q[0] + (dx * q[2] + dy * q[3]);
-        q[1] = q[1] + (dx * q[4] + dy * q[5]);
-      } else if (a.model == LK_FM_UVQ) {
-        q[0] = q[0] + (-dy * q[2]);
-        q[1] = q[1] + dx * q[2];
-      }
-      for (int i = 0; i < 6; ++i)
-        acc[i] += q[i];
-      ++cnt;
+  walk_members<kLkReseedGroup>(g, cell_range_of(g, s), (uint32_t)a.n_sectors, lane, [&](uint32_t m) {
+    if (!a.good[m])
+      return;
+    const float2 cn = a.center[m];
+    const double dx = (double)cs.x - (double)cn.x, dy = (double)cs.y - (double)cn.y;
+    if (!(dx * dx + dy * dy <= r2))
+      return;
+    const float *p = a.rec[m].resultingParameters;
+    double q[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < P; ++i)
+      q[i] = (double)p[i];
+    if (a.model == LK_FM_UVUXUYVXVY) { // (lk_guess_kernel's rule, manager_class.cpp:2602-2707)
+      q[0] = q[0] + (dx * q[2] + dy * q[3]);
+      q[1] = q[1] + (dx * q[4] + dy * q[5]);
+    } else if (a.model == LK_FM_UVQ) {
+      q[0] = q[0] + (-dy * q[2]);
+      q[1] = q[1] + dx * q[2];
     }
-  }
+    for (int i = 0; i < 6; ++i)
+      acc[i] += q[i];
+    ++cnt;
+  });
   for (int m = kLkReseedGroup / 2; m >= 1; m >>= 1) {
     for (int i = 0; i < 6; ++i)
       acc[i] += __shfl_xor(acc[i], m, kLkReseedGroup);
@@ -302,8 +289,6 @@ __global__ __launch_bounds__(kBlock) void lk_reseed_merge_kernel(LkReseedMergeAr
   }
   a.info[s] = o;
 }
-
-inline unsigned blocks_for(int n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 } // namespace
 

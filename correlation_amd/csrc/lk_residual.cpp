@@ -79,25 +79,15 @@ int lk_photometry(lk_engine *e, const lk_photometry_config *cfg, const lk_result
   if (int rc = lk_pass_records(e, st->rec, records, n, v.stream, &d_rec))
     return rc;
   LkPhotometryArgs a{};
-  a.und = v.und;
-  a.def = v.def;
-  a.urows = v.urows;
-  a.ucols = v.ucols;
-  a.drows = v.drows;
-  a.dcols = v.dcols;
-  a.xy = v.xy;
-  a.off = v.off;
-  a.rect = v.rect;
-  a.center = v.center;
-  a.rec = d_rec;
+  a.ev = lk_pass_sector_eval(v, d_rec);
+  a.level = v.level;
   a.out = st->out.as<struct lk_photometry>();
   a.sums = sums_out ? st->sums.as<double>() : nullptr;
-  a.level = v.level;
   a.chi_max = cfg->chi_max;
   LK_HIPCHK(st->begin(v.stream));
   const uint32_t *order = st->order.as<uint32_t>();
   for (int g = 0; g < 3; ++g) {
-    a.order = order;
+    a.ev.order = order;
     a.n_sectors = count[g];
     if (a.n_sectors > 0)
       LK_HIPCHK(lk_launch_photometry(a, v.model, v.interp, kLkPassGroups[g], v.stream));

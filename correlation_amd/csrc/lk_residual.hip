@@ -6,7 +6,7 @@
 //             workgroup, chosen from the sector's level-0 sample count alone (lk_bw_group).  A sample is f = the undeformed
 //             node, g = sample_def<> at Warp<>::apply, V = f - g, in float; f, g, f^2, g^2, f g, V^2 are formed and summed in
 //             double, the flagged samples are counted and max |V| is kept.  Lane j takes the samples j, j + G, ...; the
-//             reduction (DPP inside rows, readlane across rows, LDS across wavefronts) has the uncertainty kernel's fixed
+//             reduction (lk_sector_eval.hpp: DPP inside rows, readlane across rows, LDS across wavefronts) has one fixed
 //             order, so a sector's eight numbers and its record are the same bytes in any launch.  Lane 0 turns them into
 //             the record with the function the host exports (lk_residual.hpp).
 // map prep    a thread per sector: the good rule once per record; the level-0 centre (cx = NaN marks a sector that owns
@@ -22,66 +22,15 @@
 //             its own 3 x 3 cells in global memory - the same rule, the same bits.  Then the owner's 48 bytes, the solve's
 //             warp and sampler, three stores.
 #include "lk_device.hpp"
-#include "lk_good.hpp"
 #include "lk_launch.hpp"
+#include "lk_neighbours.hpp"
 #include "lk_residual.hpp"
-#include "lk_solver_common.hpp"
+#include "lk_sector_eval.hpp"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kPhotoLdsStride = 8; // doubles per wavefront in the cross-wavefront reduction
 constexpr int kPhotoAdds = 7;      // the six sums and the flagged count; slot 7 is the maximum
-
-template <int CTRL> __device__ __forceinline__ double dpp_get_f64(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-__device__ __forceinline__ double max_f64(double a, double b) { return a > b ? a : b; } // (never a NaN: |V| of finite floats)
-
-template <int CTRL> __device__ __forceinline__ void photo_stage(double (&v)[kLkPhotoSums]) {
-#pragma unroll
-  for (int i = 0; i < kPhotoAdds; ++i)
-    v[i] = v[i] + dpp_get_f64<CTRL>(v[i]);
-  v[kPhotoAdds] = max_f64(v[kPhotoAdds], dpp_get_f64<CTRL>(v[kPhotoAdds]));
-}
-
-// The eight numbers over the group, in the order of unc_reduce (lk_uncertainty.hip); every lane ends with the same bits.
-// GROUP <= 64 uses no barrier; GROUP == 512 is the whole (uniform) workgroup.
-template <int GROUP> __device__ __forceinline__ void photo_reduce(double (&v)[kLkPhotoSums], double *lds) {
-  photo_stage<0xB1>(v);  // quad_perm [1,0,3,2]
-  photo_stage<0x4E>(v);  // quad_perm [2,3,0,1]
-  photo_stage<0x141>(v); // row_half_mirror
-  photo_stage<0x140>(v); // row_mirror
-  if constexpr (GROUP >= 64) {
-#pragma unroll
-    for (int i = 0; i < kPhotoAdds; ++i)
-      v[i] = (readlane_f64(v[i], 0) + readlane_f64(v[i], 16)) + (readlane_f64(v[i], 32) + readlane_f64(v[i], 48));
-    v[kPhotoAdds] = max_f64(max_f64(readlane_f64(v[kPhotoAdds], 0), readlane_f64(v[kPhotoAdds], 16)),
-                            max_f64(readlane_f64(v[kPhotoAdds], 32), readlane_f64(v[kPhotoAdds], 48)));
-  }
-  if constexpr (GROUP > 64) {
-    constexpr int WAVES = GROUP / kWave;
-    const int wave = (int)threadIdx.x / kWave;
-    if ((int)threadIdx.x % kWave == 0) {
-#pragma unroll
-      for (int i = 0; i < kLkPhotoSums; ++i)
-        lds[wave * kPhotoLdsStride + i] = v[i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < kLkPhotoSums; ++i) {
-      double t = lds[i];
-      for (int w = 1; w < WAVES; ++w)
-        t = i < kPhotoAdds ? t + lds[w * kPhotoLdsStride + i] : max_f64(t, lds[w * kPhotoLdsStride + i]);
-      v[i] = t;
-    }
-  }
-}
 
 template <int MODEL, int INTERP, int GROUP>
 __global__ void __launch_bounds__(GROUP <= 64 ? 256 : GROUP) lk_photometry_kernel(LkPhotometryArgs a) {
@@ -92,55 +41,27 @@ __global__ void __launch_bounds__(GROUP <= 64 ? 256 : GROUP) lk_photometry_kerne
   const int lane = (int)threadIdx.x % GROUP;
   if (gid >= a.n_sectors) // (GROUP == 512: the whole workgroup; GROUP <= 64: whole rows / wavefronts, no barriers below)
     return;
-  const int s = (int)a.order[gid];
-  const lk_result rec = a.rec[s];
+  const int s = (int)a.ev.order[gid], level = a.level;
+  const lk_result rec = a.ev.rec[s];
   const bool good = reseed_good(rec, P, a.chi_max);
-  // the sector at level L, as lk_uncertainty_kernel sees it
-  const int4 rc = a.rect[s];
-  const uint32_t off = a.off[s];
-  const gptr<uint8_t> und = (gptr<uint8_t>)a.und, def = (gptr<uint8_t>)a.def;
-  const gptr<f32x2> xy = (gptr<f32x2>)(a.xy + off);
-  const int rw = rc.z;
-  const int n = rw > 0 ? rc.w : (int)(a.off[s + 1] - off);
-  const float inv_w = rw > 0 ? 1.f / (float)rw : 0.f;
-  const float2 c0 = a.center[s];
-  const float inv = 1.f / (float)(1 << a.level);
-  const float cx = a.level == 0 ? c0.x : c0.x * inv, cy = a.level == 0 ? c0.y : c0.y * inv;
+  const SectorLevel c = sector_level(a.ev, s, level, a.ev.center[s]);
+  const int n = c.n;
   float p[6];
 #pragma unroll
   for (int i = 0; i < 6; ++i)
     p[i] = i < P ? rec.resultingParameters[i] : 0.f;
-  translate<P>(p, 0, a.level);
+  translate<P>(p, 0, level);
   double v[kLkPhotoSums];
 #pragma unroll
   for (int i = 0; i < kLkPhotoSums; ++i)
     v[i] = 0.0;
-  const int umaxr = a.urows - 1, umaxc = a.ucols - 1;
   for (int k = lane; k < (good ? n : 0); k += GROUP) { // (a record that is not good is not evaluated)
-    f32x2 q;
-    if (rw > 0) { // implicit rectangle, row by row
-      int row = (int)((float)k * inv_w);
-      int col = k - row * rw;
-      if (col < 0) {
-        col += rw;
-        --row;
-      } else if (col >= rw) {
-        col -= rw;
-        ++row;
-      }
-      q.x = (float)(rc.x + col);
-      q.y = (float)(rc.y + row);
-    } else {
-      q = xy[k];
-    }
+    const f32x2 q = sector_sample(c, k);
     float xd, yd, dx = 0.f, dy = 0.f;
-    Warp<MODEL>::apply(q.x, q.y, cx, cy, p, xd, yd, dx, dy);
-    int uix = (int)(q.x + 0.5f), uiy = (int)(q.y + 0.5f); // the node the forward residual reads
-    uix = min(max(uix, 0), umaxc);                          // (memory safety only; valid lists never clamp)
-    uiy = min(max(uiy, 0), umaxr);
-    const float f = (float)und[(size_t)uiy * (size_t)a.ucols + (size_t)uix];
+    Warp<MODEL>::apply(q.x, q.y, c.cx, c.cy, p, xd, yd, dx, dy);
+    const float f = sector_und_node(c, q);
     float g;
-    if (!sample_def_value<INTERP>(def, a.drows, a.dcols, xd, yd, g)) {
+    if (!sample_def_value<INTERP>(c.def, c.drows, c.dcols, xd, yd, g)) {
       v[6] += 1.0;
       continue; // the sums of an evaluation that hit the error are never used
     }
@@ -154,7 +75,7 @@ __global__ void __launch_bounds__(GROUP <= 64 ? 256 : GROUP) lk_photometry_kerne
     v[5] += Vd * Vd;
     v[7] = max_f64(v[7], (double)fabsf(V));
   }
-  photo_reduce<GROUP>(v, lds);
+  reduce_f64<GROUP, kPhotoAdds, kLkPhotoSums - kPhotoAdds, kPhotoLdsStride>(v, lds);
   if (lane != 0)
     return;
   const bool evaluated = good && v[6] == 0.0;
@@ -174,29 +95,6 @@ __global__ void __launch_bounds__(GROUP <= 64 ? 256 : GROUP) lk_photometry_kerne
 #pragma unroll
     for (int i = 0; i < kLkPhotoSums; ++i)
       a.sums[(size_t)s * kLkPhotoSums + i] = sums[i];
-  }
-}
-
-template <int MODEL, int INTERP> hipError_t launch_photo_mi(const LkPhotometryArgs &a, int group, hipStream_t st) {
-  const int per_block = group <= 64 ? 256 / group : 1;
-  const int blocks = (a.n_sectors + per_block - 1) / per_block;
-  if (blocks <= 0)
-    return hipSuccess;
-  if (group == 16)
-    hipLaunchKernelGGL((lk_photometry_kernel<MODEL, INTERP, 16>), dim3(blocks), dim3(256), 0, st, a);
-  else if (group == 64)
-    hipLaunchKernelGGL((lk_photometry_kernel<MODEL, INTERP, 64>), dim3(blocks), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((lk_photometry_kernel<MODEL, INTERP, 512>), dim3(blocks), dim3(512), 0, st, a);
-  return hipGetLastError();
-}
-
-template <int MODEL> hipError_t launch_photo_m(const LkPhotometryArgs &a, int interp, int group, hipStream_t st) {
-  switch (interp) {
-  case LK_IM_NEAREST: return launch_photo_mi<MODEL, LK_IM_NEAREST>(a, group, st);
-  case LK_IM_BILINEAR: return launch_photo_mi<MODEL, LK_IM_BILINEAR>(a, group, st);
-  case LK_IM_BICUBIC: return launch_photo_mi<MODEL, LK_IM_BICUBIC>(a, group, st);
-  default: return launch_photo_mi<MODEL, LK_IM_BICUBIC_SEPARABLE>(a, group, st);
   }
 }
 
@@ -229,13 +127,6 @@ __global__ __launch_bounds__(kBlock) void lk_map_prep_kernel(const lk_result *re
   pack[s] = o;
 }
 
-// the cell coordinate of a level-0 position, as lk_track.hip's: the grid kernel's expression for a centre, clamped to
-// [-2, n + 1]; -2 and n + 1 stand for everything more than a cell (>= radius) from every centre
-__device__ inline int map_cell_coord(double v, double origin, double cell, int n) {
-  const double q = floor((v - origin) / cell);
-  return q >= (double)(n + 1) ? n + 1 : (q > -2.0 ? (int)q : -2);
-}
-
 template <int MODEL, int INTERP> __global__ __launch_bounds__(kBlock) void lk_residual_map_kernel(LkResidualMapArgs a) {
   static_assert(kLkMapTileW * kLkMapTileH == kBlock, "a thread per pixel of the tile");
   __shared__ float s_cx[kLkMapCapacity], s_cy[kLkMapCapacity];
@@ -247,37 +138,18 @@ template <int MODEL, int INTERP> __global__ __launch_bounds__(kBlock) void lk_re
   const int px0 = a.x0 + tile_x * kLkMapTileW, py0 = a.y0 + tile_y * kLkMapTileH;
   const int px1 = min(px0 + kLkMapTileW, a.x0 + a.w) - 1, py1 = min(py0 + kLkMapTileH, a.y0 + a.h) - 1;
   const double up = (double)(1 << a.level);
-  const int S = a.n_sectors;
-  const int cx_lo = map_cell_coord((double)px0 * up, g.x0, g.cell, g.nx), cx_hi = map_cell_coord((double)px1 * up, g.x0, g.cell, g.nx);
-  const int cy_lo = map_cell_coord((double)py0 * up, g.y0, g.cell, g.ny), cy_hi = map_cell_coord((double)py1 * up, g.y0, g.cell, g.ny);
-  const int x_lo = cx_lo > 0 ? cx_lo - 1 : 0, x_hi = cx_hi + 1 < g.nx ? cx_hi + 1 : g.nx - 1;
-  const int y_lo = cy_lo > 0 ? cy_lo - 1 : 0, y_hi = cy_hi + 1 < g.ny ? cy_hi + 1 : g.ny - 1;
-  long long total = 0;
-  if (x_lo <= x_hi)
-    for (int yy = y_lo; yy <= y_hi; ++yy) {
-      const uint32_t b = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_lo];
-      uint32_t e = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_hi + 1];
-      e = e < (uint32_t)S ? e : (uint32_t)S;
-      total += e > b ? (long long)(e - b) : 0;
-    }
+  const uint32_t S = (uint32_t)a.n_sectors;
+  const CellRange cells = cell_range(g, free_cell_coord((double)px0 * up, g.x0, g.cell, g.nx), free_cell_coord((double)px1 * up, g.x0, g.cell, g.nx),
+                                     free_cell_coord((double)py0 * up, g.y0, g.cell, g.ny), free_cell_coord((double)py1 * up, g.y0, g.cell, g.ny));
+  const long long total = cell_range_entries(g, cells, S);
   const bool staged = total <= (long long)kLkMapCapacity;
   if (staged) {
-    int base = 0;
-    if (x_lo <= x_hi)
-      for (int yy = y_lo; yy <= y_hi; ++yy) {
-        const uint32_t b = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_lo];
-        uint32_t e = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_hi + 1];
-        e = e < (uint32_t)S ? e : (uint32_t)S;
-        for (uint32_t k = b + (uint32_t)tid; k < e; k += kBlock) {
-          const uint32_t m = g.members[k];
-          const int at = base + (int)(k - b); // < total <= kLkMapCapacity
-          const bool known = m < (uint32_t)S;
-          s_idx[at] = known ? (int)m : 0;
-          s_cx[at] = known ? a.pack[m].cx0 : __uint_as_float(0x7fc00000u);
-          s_cy[at] = known ? a.pack[m].cy0 : 0.f;
-        }
-        base += e > b ? (int)(e - b) : 0;
-      }
+    walk_entries<kBlock>(g, cells, S, tid, [&](uint32_t at, uint32_t m) { // at < total <= kLkMapCapacity
+      const bool known = m < S;
+      s_idx[at] = known ? (int)m : 0;
+      s_cx[at] = known ? a.pack[m].cx0 : __uint_as_float(0x7fc00000u);
+      s_cy[at] = known ? a.pack[m].cy0 : 0.f;
+    });
     __syncthreads();
   } else if (tid == 0) {
     atomicAdd(a.fallback, 1u);
@@ -298,25 +170,14 @@ template <int MODEL, int INTERP> __global__ __launch_bounds__(kBlock) void lk_re
       }
     }
   } else {
-    const int ix = map_cell_coord(X, g.x0, g.cell, g.nx), iy = map_cell_coord(Y, g.y0, g.cell, g.ny);
-    const int qx_lo = ix > 0 ? ix - 1 : 0, qx_hi = ix + 1 < g.nx ? ix + 1 : g.nx - 1;
-    const int qy_lo = iy > 0 ? iy - 1 : 0, qy_hi = iy + 1 < g.ny ? iy + 1 : g.ny - 1;
-    if (qx_lo <= qx_hi)
-      for (int yy = qy_lo; yy <= qy_hi; ++yy) {
-        const uint32_t b = g.start[(size_t)yy * (size_t)g.nx + (size_t)qx_lo];
-        uint32_t e = g.start[(size_t)yy * (size_t)g.nx + (size_t)qx_hi + 1];
-        e = e < (uint32_t)S ? e : (uint32_t)S;
-        for (uint32_t k = b; k < e; ++k) {
-          const uint32_t m = g.members[k];
-          if (m >= (uint32_t)S)
-            continue;
-          const double d2 = lk_map_d2(a.pack[m].cx0, a.pack[m].cy0, X, Y);
-          if (d2 <= a.r2 && lk_map_better(d2, (int)m, best_d2, best)) {
-            best = (int)m;
-            best_d2 = d2;
-          }
-        }
+    const CellRange around = cell_range(g, free_cell_coord(X, g.x0, g.cell, g.nx), free_cell_coord(Y, g.y0, g.cell, g.ny));
+    walk_members<1>(g, around, S, 0, [&](uint32_t m) {
+      const double d2 = lk_map_d2(a.pack[m].cx0, a.pack[m].cy0, X, Y);
+      if (d2 <= a.r2 && lk_map_better(d2, (int)m, best_d2, best)) {
+        best = (int)m;
+        best_d2 = d2;
       }
+    });
   }
   const float nan = __uint_as_float(0x7fc00000u);
   float W = nan, R = nan;
@@ -346,42 +207,24 @@ template <int MODEL, int INTERP> __global__ __launch_bounds__(kBlock) void lk_re
     a.owner[at] = own;
 }
 
-template <int MODEL> hipError_t launch_map_m(const LkResidualMapArgs &a, int interp, unsigned tiles, hipStream_t st) {
-  const dim3 grid(tiles), block(kBlock);
-  switch (interp) {
-  case LK_IM_NEAREST: hipLaunchKernelGGL((lk_residual_map_kernel<MODEL, LK_IM_NEAREST>), grid, block, 0, st, a); break;
-  case LK_IM_BILINEAR: hipLaunchKernelGGL((lk_residual_map_kernel<MODEL, LK_IM_BILINEAR>), grid, block, 0, st, a); break;
-  case LK_IM_BICUBIC: hipLaunchKernelGGL((lk_residual_map_kernel<MODEL, LK_IM_BICUBIC>), grid, block, 0, st, a); break;
-  default: hipLaunchKernelGGL((lk_residual_map_kernel<MODEL, LK_IM_BICUBIC_SEPARABLE>), grid, block, 0, st, a); break;
-  }
-  return hipGetLastError();
-}
-
 } // namespace
 
 hipError_t lk_launch_photometry(const LkPhotometryArgs &a, int model, int interp, int group, hipStream_t st) {
-  switch (model) {
-  case LK_FM_U: return launch_photo_m<LK_FM_U>(a, interp, group, st);
-  case LK_FM_UV: return launch_photo_m<LK_FM_UV>(a, interp, group, st);
-  case LK_FM_UVQ: return launch_photo_m<LK_FM_UVQ>(a, interp, group, st);
-  default: return launch_photo_m<LK_FM_UVUXUYVXVY>(a, interp, group, st);
-  }
+  return dispatch_sector_kernel(model, interp, group, [&](auto m, auto i, auto g) {
+    constexpr int M = decltype(m)::value, I = decltype(i)::value, G = decltype(g)::value;
+    return launch_sector_groups<G>(lk_photometry_kernel<M, I, G>, a, a.n_sectors, st);
+  });
 }
 
 hipError_t lk_launch_map_prep(const lk_result *rec, const float2 *center, int n_sectors, int model, int level, float chi_max,
                               LkMapSector *pack, hipStream_t st) {
   if (n_sectors <= 0)
     return hipSuccess;
-  const dim3 grid((unsigned)((n_sectors + kBlock - 1) / kBlock)), block(kBlock);
-  switch (model) {
-  case LK_FM_U: hipLaunchKernelGGL(lk_map_prep_kernel<LK_FM_U>, grid, block, 0, st, rec, center, n_sectors, level, chi_max, pack); break;
-  case LK_FM_UV: hipLaunchKernelGGL(lk_map_prep_kernel<LK_FM_UV>, grid, block, 0, st, rec, center, n_sectors, level, chi_max, pack); break;
-  case LK_FM_UVQ: hipLaunchKernelGGL(lk_map_prep_kernel<LK_FM_UVQ>, grid, block, 0, st, rec, center, n_sectors, level, chi_max, pack); break;
-  default:
-    hipLaunchKernelGGL(lk_map_prep_kernel<LK_FM_UVUXUYVXVY>, grid, block, 0, st, rec, center, n_sectors, level, chi_max, pack);
-    break;
-  }
-  return hipGetLastError();
+  return dispatch_model(model, [&](auto m) {
+    hipLaunchKernelGGL(lk_map_prep_kernel<decltype(m)::value>, dim3(blocks_for(n_sectors, kBlock)), dim3(kBlock), 0, st, rec, center,
+                       n_sectors, level, chi_max, pack);
+    return hipGetLastError();
+  });
 }
 
 hipError_t lk_launch_residual_map(const LkResidualMapArgs &a, int model, int interp, int *n_tiles, hipStream_t st) {
@@ -392,10 +235,10 @@ hipError_t lk_launch_residual_map(const LkResidualMapArgs &a, int model, int int
     return hipErrorInvalidValue;
   if (n_tiles)
     *n_tiles = (int)tiles;
-  switch (model) {
-  case LK_FM_U: return launch_map_m<LK_FM_U>(a, interp, (unsigned)tiles, st);
-  case LK_FM_UV: return launch_map_m<LK_FM_UV>(a, interp, (unsigned)tiles, st);
-  case LK_FM_UVQ: return launch_map_m<LK_FM_UVQ>(a, interp, (unsigned)tiles, st);
-  default: return launch_map_m<LK_FM_UVUXUYVXVY>(a, interp, (unsigned)tiles, st);
-  }
+  return dispatch_model(model, [&](auto m) {
+    return dispatch_interp(interp, [&](auto i) {
+      hipLaunchKernelGGL((lk_residual_map_kernel<decltype(m)::value, decltype(i)::value>), dim3((unsigned)tiles), dim3(kBlock), 0, st, a);
+      return hipGetLastError();
+    });
+  });
 }

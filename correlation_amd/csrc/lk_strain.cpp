@@ -61,7 +61,7 @@ int lk_strain_field(lk_engine *e, const lk_strain_config *cfg, const lk_result *
   LkStrainArgs a{};
   if (int rc = lk_pass_grid(e, "lk_strain_field", st, st->bbox, st->grid, v.center, v.S, cfg->radius, v.stream, &a.grid))
     return rc;
-  LK_HIPCHK(lk_launch_strain_prep(d_rec, v.center, v.S, v.model, cfg->chi_max, st->good.as<uint8_t>(), st->pack.as<float4>(), v.stream));
+  LK_HIPCHK(lk_launch_pack_prep(d_rec, v.center, v.S, 1, v.model, cfg->chi_max, 0, st->good.as<uint8_t>(), st->pack.as<float4>(), v.stream));
   a.center = v.center;
   a.rec = d_rec;
   a.good = st->good.as<uint8_t>();

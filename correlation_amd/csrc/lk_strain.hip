@@ -19,25 +19,27 @@
 #include <stdint.h>
 
 #include "lk_device.hpp"
-#include "lk_good.hpp"
 #include "lk_launch.hpp"
+#include "lk_neighbours.hpp"
 #include "lk_strain.hpp"
 
 namespace {
 
-constexpr int kBlock = 256;
-
-__global__ __launch_bounds__(kBlock) void lk_strain_prep_kernel(const lk_result *rec, const float2 *center, int n, int model,
-                                                                float chi_max, uint8_t *good, float4 *pack) {
-  const int s = (int)(blockIdx.x * kBlock + threadIdx.x);
-  if (s >= n)
+// The pack of strain, outlier and track: a thread per record i of [F][S], the good rule once per record.  zero: u + 0 and
+// v + 0 (the outlier test's canonical zero: -0 becomes +0).
+__global__ __launch_bounds__(kBlock) void lk_pack_prep_kernel(const lk_result *rec, const float2 *center, int n_sectors,
+                                                              long long total, int model, float chi_max, int zero,
+                                                              uint8_t *good, float4 *pack) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= total)
     return;
-  const lk_result r = rec[s];
+  const lk_result r = rec[i];
   const bool g = reseed_good(r, n_params_of(model), chi_max);
-  const float2 c = center[s];
-  good[s] = g ? 1 : 0;
-  pack[s] = make_float4(g ? c.x : __uint_as_float(0x7fc00000u), c.y, r.resultingParameters[0],
-                        model == LK_FM_U ? 0.f : r.resultingParameters[1]);
+  const float2 c = center[total == n_sectors ? i : i % n_sectors];
+  if (good)
+    good[i] = g ? 1 : 0;
+  const float u = r.resultingParameters[0], v = model == LK_FM_U ? 0.f : r.resultingParameters[1];
+  pack[i] = make_float4(g ? c.x : __uint_as_float(0x7fc00000u), c.y, zero ? u + 0.0f : u, zero ? v + 0.0f : v);
 }
 
 // one candidate of the walk: is it in the window, and its (dx, dy, u, v)
@@ -70,62 +72,27 @@ template <int GROUP, bool PACKED> __global__ __launch_bounds__(kBlock) void lk_s
   const int s = (int)row;
   const LkReseedGrid &g = a.grid;
   const float2 cs = a.center[s];
-  const int cell = (int)g.cell_of[s], ix = cell % g.nx, iy = cell / g.nx;
-  const int x_lo = ix > 0 ? ix - 1 : 0, x_hi = ix + 1 < g.nx ? ix + 1 : g.nx - 1;
-  const int y_lo = iy > 0 ? iy - 1 : 0, y_hi = iy + 1 < g.ny ? iy + 1 : g.ny - 1;
+  const CellRange cells = cell_range_of(g, s);
   const double r2 = a.radius * a.radius;
   const uint32_t S = (uint32_t)a.n_sectors;
 
   // pass 1: the count and the sums
-  double Sx = 0, Sy = 0, Sxx = 0, Sxy = 0, Syy = 0, Su = 0, Sxu = 0, Syu = 0, Sv = 0, Sxv = 0, Syv = 0;
-  int cnt = 0;
-  for (int yy = y_lo; yy <= y_hi; ++yy) {
-    const uint32_t b = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_lo];
-    uint32_t e = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_hi + 1];
-    e = e < S ? e : S;
-    for (uint32_t k = b + (uint32_t)lane; k < e; k += GROUP) {
-      const uint32_t m = g.members[k];
-      double x, y, u, v;
-      if (m >= S || !strain_visit<PACKED>(a, m, cs, r2, x, y, u, v))
-        continue;
-      Sx += x;
-      Sy += y;
-      Sxx += x * x;
-      Sxy += x * y;
-      Syy += y * y;
-      Su += u;
-      Sxu += x * u;
-      Syu += y * u;
-      Sv += v;
-      Sxv += x * v;
-      Syv += y * v;
-      ++cnt;
-    }
-  }
-  for (int m = GROUP / 2; m >= 1; m >>= 1) {
-    Sx += __shfl_xor(Sx, m, GROUP);
-    Sy += __shfl_xor(Sy, m, GROUP);
-    Sxx += __shfl_xor(Sxx, m, GROUP);
-    Sxy += __shfl_xor(Sxy, m, GROUP);
-    Syy += __shfl_xor(Syy, m, GROUP);
-    Su += __shfl_xor(Su, m, GROUP);
-    Sxu += __shfl_xor(Sxu, m, GROUP);
-    Syu += __shfl_xor(Syu, m, GROUP);
-    Sv += __shfl_xor(Sv, m, GROUP);
-    Sxv += __shfl_xor(Sxv, m, GROUP);
-    Syv += __shfl_xor(Syv, m, GROUP);
-    cnt += __shfl_xor(cnt, m, GROUP);
-  }
+  PlaneSums sums;
+  walk_members<GROUP>(g, cells, S, lane, [&](uint32_t m) {
+    double x, y, u, v;
+    if (strain_visit<PACKED>(a, m, cs, r2, x, y, u, v))
+      sums.add(x, y, u, v);
+  });
+  sums.template join<GROUP>();
 
   // moments, status, gradients: the same bits in every lane of the group
+  const int cnt = sums.n;
   const double n = (double)cnt;
-  const double Cxx = Sxx - Sx * Sx / n, Cxy = Sxy - Sx * Sy / n, Cyy = Syy - Sy * Sy / n;
-  const double Cxu = Sxu - Sx * Su / n, Cyu = Syu - Sy * Su / n, Cxv = Sxv - Sx * Sv / n, Cyv = Syv - Sy * Sv / n;
-  const double CC = Cxx * Cyy, D = CC - Cxy * Cxy;
+  const LkPlaneFit pf = lk_plane_fit(cnt, sums.s);
   int status = LK_STRAIN_OK;
   if (cnt < a.min_neighbours)
     status = LK_STRAIN_TOO_FEW;
-  else if (CC == 0.0 || !(D > 1e-6 * CC))
+  else if (pf.CC == 0.0 || !(pf.D > 1e-6 * pf.CC))
     status = LK_STRAIN_DEGENERATE;
   else if (PACKED ? a.pack[s].x != a.pack[s].x : !a.good[s])
     status = LK_STRAIN_FILLED;
@@ -133,26 +100,17 @@ template <int GROUP, bool PACKED> __global__ __launch_bounds__(kBlock) void lk_s
   double fit[6] = {0, 0, 0, 0, 0, 0}, rr = 0; // u, v, ux, uy, vx, vy of the plane; the residual sum
   const bool valid = status == LK_STRAIN_OK || status == LK_STRAIN_FILLED;
   if (valid) {
-    const double ux = (Cyy * Cxu - Cxy * Cyu) / D, uy = (Cxx * Cyu - Cxy * Cxu) / D;
-    const double vx = (Cyy * Cxv - Cxy * Cyv) / D, vy = (Cxx * Cyv - Cxy * Cxv) / D;
-    const double u0 = Su / n - ux * (Sx / n) - uy * (Sy / n), v0 = Sv / n - vx * (Sx / n) - vy * (Sy / n);
     // pass 2: the residuals of the fitted plane over the same window
-    for (int yy = y_lo; yy <= y_hi; ++yy) {
-      const uint32_t b = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_lo];
-      uint32_t e = g.start[(size_t)yy * (size_t)g.nx + (size_t)x_hi + 1];
-      e = e < S ? e : S;
-      for (uint32_t k = b + (uint32_t)lane; k < e; k += GROUP) {
-        const uint32_t m = g.members[k];
-        double x, y, u, v;
-        if (m >= S || !strain_visit<PACKED>(a, m, cs, r2, x, y, u, v))
-          continue;
-        const double ru = u - (u0 + ux * x + uy * y), rv = v - (v0 + vx * x + vy * y);
-        rr += ru * ru + rv * rv;
-      }
-    }
+    walk_members<GROUP>(g, cells, S, lane, [&](uint32_t m) {
+      double x, y, u, v;
+      if (!strain_visit<PACKED>(a, m, cs, r2, x, y, u, v))
+        return;
+      const double ru = u - (pf.u0 + pf.ux * x + pf.uy * y), rv = v - (pf.v0 + pf.vx * x + pf.vy * y);
+      rr += ru * ru + rv * rv;
+    });
     for (int m = GROUP / 2; m >= 1; m >>= 1)
       rr += __shfl_xor(rr, m, GROUP);
-    fit[0] = u0, fit[1] = v0, fit[2] = ux, fit[3] = uy, fit[4] = vx, fit[5] = vy;
+    fit[0] = pf.u0, fit[1] = pf.v0, fit[2] = pf.ux, fit[3] = pf.uy, fit[4] = pf.vx, fit[5] = pf.vy;
   }
   if (lane != 0)
     return;
@@ -172,16 +130,15 @@ template <int GROUP, bool PACKED> __global__ __launch_bounds__(kBlock) void lk_s
   o[3] = make_float4(residual, __int_as_float(cnt), __int_as_float(status), __int_as_float(0));
 }
 
-inline unsigned blocks_for(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
 } // namespace
 
-hipError_t lk_launch_strain_prep(const lk_result *rec, const float2 *center, int n_sectors, int model, float chi_max,
-                                 uint8_t *good, float4 *pack, hipStream_t st) {
-  if (n_sectors <= 0)
+hipError_t lk_launch_pack_prep(const lk_result *rec, const float2 *center, int n_sectors, int n_frames, int model, float chi_max,
+                               int canonical_zero, uint8_t *good, float4 *pack, hipStream_t st) {
+  if (n_sectors <= 0 || n_frames <= 0)
     return hipSuccess;
-  hipLaunchKernelGGL(lk_strain_prep_kernel, dim3(blocks_for(n_sectors, kBlock)), dim3(kBlock), 0, st, rec, center, n_sectors,
-                     model, chi_max, good, pack);
+  const long long total = (long long)n_sectors * n_frames;
+  hipLaunchKernelGGL(lk_pack_prep_kernel, dim3(blocks_for(total, kBlock)), dim3(kBlock), 0, st, rec, center, n_sectors, total,
+                     model, chi_max, canonical_zero, good, pack);
   return hipGetLastError();
 }
 

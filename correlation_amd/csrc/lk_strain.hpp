@@ -1,11 +1,36 @@
-// lk_strain.hpp - the strain tensor of a displacement gradient (include/lk_engine.h: lk_strain_field,
-// lk_strain_from_gradient).  One function for the kernel (lk_strain.hip) and the host entry point, like lk_compose.hpp:
-// the record's six tensor fields are this function of its four gradient fields, whoever computes them.
+// lk_strain.hpp - the windowed plane fit and the strain tensor of a displacement gradient (include/lk_engine.h:
+// lk_strain_field, lk_strain_from_gradient).  One function each for the kernels (lk_strain.hip, lk_outlier.hip, lk_track.hip
+// through lk_track.hpp) and the host entry points, like lk_compose.hpp: the plane is this function of a window's count and
+// sums, the record's six tensor fields are this function of its four gradient fields, whoever computes them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "../../include/lk_engine.h"
+
+// The least-squares planes u(x, y) = u0 + ux x + uy y and v(x, y) = v0 + vx x + vy y of a window of n centres, from
+// sums11 = {Sx, Sy, Sxx, Sxy, Syy, Su, Sxu, Syu, Sv, Sxv, Syv} in the window's coordinates: the centred moments and the 2 x 2
+// solve, all in double, each product, quotient and difference rounded to double in the order written.  Which windows have
+// a plane (enough centres, CC != 0, D large enough against CC, ...) is the caller's rule: the coefficients of a window that
+// fails it are whatever the divisions give and are not to be read.
+struct LkPlaneFit {
+  double Cxx, Cxy, Cyy, CC, D; // moments of the centres, Cxx Cyy, the determinant
+  double ux, uy, vx, vy, u0, v0;
+};
+__host__ __device__ inline LkPlaneFit lk_plane_fit(int count, const double *sums11) {
+  const double Sx = sums11[0], Sy = sums11[1], Sxx = sums11[2], Sxy = sums11[3], Syy = sums11[4], Su = sums11[5];
+  const double Sxu = sums11[6], Syu = sums11[7], Sv = sums11[8], Sxv = sums11[9], Syv = sums11[10];
+  const double n = (double)count;
+  const double Cxx = Sxx - Sx * Sx / n, Cxy = Sxy - Sx * Sy / n, Cyy = Syy - Sy * Sy / n;
+  const double Cxu = Sxu - Sx * Su / n, Cyu = Syu - Sy * Su / n, Cxv = Sxv - Sx * Sv / n, Cyv = Syv - Sy * Sv / n;
+  const double CC = Cxx * Cyy, D = CC - Cxy * Cxy;
+  LkPlaneFit f;
+  f.Cxx = Cxx, f.Cxy = Cxy, f.Cyy = Cyy, f.CC = CC, f.D = D;
+  f.ux = (Cyy * Cxu - Cxy * Cyu) / D, f.uy = (Cxx * Cyu - Cxy * Cxu) / D;
+  f.vx = (Cyy * Cxv - Cxy * Cyv) / D, f.vy = (Cxx * Cyv - Cxy * Cxv) / D;
+  f.u0 = Su / n - f.ux * (Sx / n) - f.uy * (Sy / n), f.v0 = Sv / n - f.vx * (Sx / n) - f.vy * (Sy / n);
+  return f;
+}
 
 // grad4 = {ux, uy, vx, vy} as stored (float); out6 = {exx, eyy, exy, e1, e2, theta}.  Computed in double, each result
 // rounded to float once.  Returns 1 for an unknown tensor (out6 untouched), else 0.

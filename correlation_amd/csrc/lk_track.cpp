@@ -102,7 +102,7 @@ int lk_track_points(lk_engine *e, const lk_track_config *cfg, int n_points, cons
   LkTrackArgs a{};
   if (int rc = lk_pass_grid(e, "lk_track_points", st, st->bbox, st->grid, v.center, v.S, cfg->radius, v.stream, &a.grid))
     return rc;
-  LK_HIPCHK(lk_launch_track_prep(d_rec, v.center, v.S, n_frames, v.model, cfg->chi_max, st->pack.as<float4>(), v.stream));
+  LK_HIPCHK(lk_launch_pack_prep(d_rec, v.center, v.S, n_frames, v.model, cfg->chi_max, 0, nullptr, st->pack.as<float4>(), v.stream));
   a.pack = st->pack.as<float4>();
   a.state = st->state.as<double>();
   a.out = st->out.as<lk_track>();

@@ -24,12 +24,8 @@ __host__ __device__ inline void lk_track_step_impl(int mode, int min_neighbours,
                                                    int tensor, lk_track *out) {
   const double X = state8[0], Y = state8[1];
   const bool incremental = mode == LK_TRACK_INCREMENTAL;
-  const double Sx = sums11[0], Sy = sums11[1], Sxx = sums11[2], Sxy = sums11[3], Syy = sums11[4], Su = sums11[5];
-  const double Sxu = sums11[6], Syu = sums11[7], Sv = sums11[8], Sxv = sums11[9], Syv = sums11[10];
-  const double dn = (double)n;
-  const double Cxx = Sxx - Sx * Sx / dn, Cxy = Sxy - Sx * Sy / dn, Cyy = Syy - Sy * Sy / dn;
-  const double Cxu = Sxu - Sx * Su / dn, Cyu = Syu - Sy * Su / dn, Cxv = Sxv - Sx * Sv / dn, Cyv = Syv - Sy * Sv / dn;
-  const double CC = Cxx * Cyy, D = CC - Cxy * Cxy;
+  const double Sxx = sums11[2], Syy = sums11[4];
+  const LkPlaneFit pf = lk_plane_fit(n, sums11);
   int status = LK_TRACK_OK;
   if (!lk_track_finite(X) || !lk_track_finite(Y))
     status = LK_TRACK_BAD_POINT;
@@ -38,15 +34,13 @@ __host__ __device__ inline void lk_track_step_impl(int mode, int min_neighbours,
     status = LK_TRACK_LOST;
   else if (n < min_neighbours)
     status = LK_TRACK_TOO_FEW;
-  else if (CC == 0.0 || !(Cxx > kLkTrackNoise * Sxx) || !(Cyy > kLkTrackNoise * Syy) || !(D > 1e-6 * CC))
+  else if (pf.CC == 0.0 || !(pf.Cxx > kLkTrackNoise * Sxx) || !(pf.Cyy > kLkTrackNoise * Syy) || !(pf.D > 1e-6 * pf.CC))
     status = LK_TRACK_DEGENERATE;
 
   float f[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // u, v, ux, uy, vx, vy, exx .. theta
   float px = 0.f, py = 0.f;
   if (status == LK_TRACK_OK) {
-    const double gux = (Cyy * Cxu - Cxy * Cyu) / D, guy = (Cxx * Cyu - Cxy * Cxu) / D;
-    const double gvx = (Cyy * Cxv - Cxy * Cyv) / D, gvy = (Cxx * Cyv - Cxy * Cxv) / D;
-    const double du = Su / dn - gux * (Sx / dn) - guy * (Sy / dn), dv = Sv / dn - gvx * (Sx / dn) - gvy * (Sy / dn);
+    const double gux = pf.ux, guy = pf.uy, gvx = pf.vx, gvy = pf.vy, du = pf.u0, dv = pf.v0;
     double x, y, Fxx, Fxy, Fyx, Fyy;
     if (incremental) { // x_f = x_{f-1} + du(x_{f-1}),  F_f = (I + g) F_{f-1}
       const double a = 1.0 + gux, d = 1.0 + gvy;

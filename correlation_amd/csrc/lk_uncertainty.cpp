@@ -53,24 +53,14 @@ int lk_parameter_uncertainty(lk_engine *e, const lk_uncertainty_config *cfg, con
   if (int rc = lk_pass_records(e, st->rec, records, n, v.stream, &d_rec))
     return rc;
   LkUncertaintyArgs a{};
-  a.und = v.und;
-  a.def = v.def;
-  a.urows = v.urows;
-  a.ucols = v.ucols;
-  a.drows = v.drows;
-  a.dcols = v.dcols;
-  a.xy = v.xy;
-  a.off = v.off;
-  a.rect = v.rect;
-  a.center = v.center;
-  a.rec = d_rec;
+  a.ev = lk_pass_sector_eval(v, d_rec);
+  a.level = v.level;
   a.out = st->out.as<lk_uncertainty>();
   a.sums = sums_out ? st->sums.as<double>() : nullptr;
-  a.level = v.level;
   LK_HIPCHK(st->begin(v.stream));
   const uint32_t *order = st->order.as<uint32_t>();
   for (int g = 0; g < 3; ++g) {
-    a.order = order;
+    a.ev.order = order;
     a.n_sectors = st->count[g];
     if (a.n_sectors > 0)
       LK_HIPCHK(lk_launch_uncertainty(a, v.model, v.interp, kLkPassGroups[g], v.stream));

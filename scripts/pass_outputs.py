@@ -1,0 +1,236 @@
+#!/usr/bin/env python3
+"""Every output of the add-on passes and of the backward solve on one seeded scene, for comparing two builds of the
+library byte for byte - the check behind a change of the passes' device code that must not change a result.
+
+    LK_ENGINE_LIB=/path/to/liblk_engine.so python scripts/pass_outputs.py OUT.npz     (LK_ENGINE_LIB unset: the tree's own)
+    python scripts/pass_outputs.py --compare A.npz B.npz                              (exit status 1 if any array differs)
+
+Two scenes of one 256 x 256 speckle pair: `mix`, the sectors of tests/test_uncertainty_gpu.py (361, 49, 899 and 10000
+samples and an annular list: 16, 64 and 512 lanes all occur), and `grid`, 24 x 24 rectangular sectors for the passes that
+look for neighbours.  Both are solved once; then a few records are made bad (an error code, a NaN parameter, an infinite
+chi) and one u becomes -0.  Every variant below runs in a child process of its own - the lane group and the variant of a
+pass are chosen by environment variables that the library reads per call, and a fault must not reach the next one - under
+a time limit, and the first failure ends the run.  The arrays of all variants go into one .npz, `variant/array`.
+"""
+import argparse
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+TRUTH = (1.3, -0.7, 0.002, 0.0, 0.0, -0.001)
+RECTS = [(8, 8, 26, 26), (40, 8, 46, 14), (8, 60, 38, 88), (140, 140, 239, 239)]
+ANNULAR = [(20.0, 12.0, 0.3, 0.9, 70.0, 190.0, 6)]
+RADIUS = 25.0        # 2.5 pitches of the grid: windows of about 20 sectors
+TINY_RADIUS = 4.0    # less than a pitch: every window is TOO_FEW
+WIDE_RADIUS = 300.0  # one cell holds the whole grid, 576 sectors: more than a tile of the map keeps in LDS, so it falls back
+CHILD_SECONDS = 180
+
+
+def solved(scene, model, interp, update=None):
+    """(engine, records of its solve with a few made bad)"""
+    import correlation_amd as ca
+    und, dfm = ca.speckle.speckle_pair(256, 256, p=TRUTH, seed=5)
+    e = ca.HipCorrelationEngine(interpolation=interp, fitting_model=model, precision=1e-3, py_stop=2)
+    if update is not None:
+        e.set_update(update)
+    e.set_undeformed_image(und)
+    e.set_deformed_image(dfm)
+    if scene == "mix":
+        for s, r in enumerate(RECTS):
+            e.resetPolygon_rect(s, *r)
+        for k, q in enumerate(ANNULAR):
+            e.resetPolygon_annular(len(RECTS) + k, *q)
+    else:
+        e.set_rect_grid(8.0, 8.0, 247.0, 247.0, 24, 24)
+    e.commit_sectors()
+    g = np.zeros((e.n_sectors, 6), np.float32)
+    g[:, :2] = TRUTH[:2]
+    rec = e.correlate_all(g).copy()
+    S = e.n_sectors
+    if scene == "mix":
+        rec["error_code"][1] = 3
+    else:
+        rec["error_code"][np.arange(7, S, 37)] = 3
+        rec["p"][45, 1] = np.nan
+        rec["chi"][210] = np.inf
+        rec["p"][101, 0] = -0.0
+    return e, rec
+
+
+def fields(prefix, a):
+    """a structured array as one plain array per field"""
+    return {prefix + "." + k: np.ascontiguousarray(a[k]) for k in a.dtype.names}
+
+
+def run_strain():
+    import correlation_amd as ca
+    e, rec = solved("grid", ca.FM_UVUXUYVXVY, ca.IM_BICUBIC)
+    out = fields("records", rec)
+    out.update(fields("strain", e.strain_field(RADIUS, records=rec)))
+    out.update(fields("strain_chi_max", e.strain_field(RADIUS, chi_max=float(np.median(rec["chi"])), records=rec)))
+    out.update(fields("strain_too_few", e.strain_field(TINY_RADIUS, records=rec)))
+    return out
+
+
+def run_outlier():
+    import correlation_amd as ca
+    e, rec = solved("grid", ca.FM_UVUXUYVXVY, ca.IM_BICUBIC)
+    rec["p"][[88, 301], 0] += 0.7   # two sectors to flag
+    out = {}
+    for name, kw in (("detrend", dict(detrend=True, passes=2)), ("plain", dict(detrend=False)),
+                     ("too_few", dict(detrend=True, radius=TINY_RADIUS))):
+        kw.setdefault("radius", RADIUS)
+        flags, n, marked = e.flag_outliers(mark=True, records=rec, return_records=True, **kw)
+        out.update(fields("outlier_" + name, flags))
+        out["outlier_" + name + ".flagged"] = np.array([n])
+        out["outlier_" + name + ".error_code"] = marked["error_code"].copy()
+    return out
+
+
+def run_track():
+    import correlation_amd as ca
+    e, rec = solved("grid", ca.FM_UVUXUYVXVY, ca.IM_BICUBIC)
+    frames = np.stack([rec.copy() for _ in range(3)])
+    for f in range(3):   # frame f: f + 1 times the solved field
+        frames["p"][f] *= np.float32(f + 1)
+    frames["error_code"][1][60:64] = 3
+    rng = np.random.default_rng(11)
+    pts = rng.uniform(0.0, 255.0, (61, 2)).astype(np.float32)
+    pts[0] = (-400.0, 90.0)   # far off the grid in x: no cell at all
+    pts[1] = (90.0, 700.0)    # ... in y
+    pts[2] = (-20.0, -20.0)   # one cell beyond the grid: its range still reaches the corner cells
+    pts[3] = (np.nan, 50.0)
+    out = {}
+    for mode, name in ((ca._ffi.TRACK_TOTAL, "total"), (ca._ffi.TRACK_INCREMENTAL, "incremental")):
+        for radius, tag in ((RADIUS, ""), (TINY_RADIUS, "_too_few")):
+            tr, st = e.track_points(pts, radius, records=frames, mode=mode)
+            out.update(fields("track_" + name + tag, tr))
+            out["track_" + name + tag + ".state"] = st
+    return out
+
+
+def run_plan():
+    import correlation_amd as ca
+    out = {}
+    for model, name in ((ca.FM_UVUXUYVXVY, "affine"), (ca.FM_UVQ, "uvq")):
+        e, rec = solved("grid", model, ca.IM_BICUBIC)
+        g, info = e.reseed_plan(rec, RADIUS, min_neighbours=2)
+        out["plan_" + name + ".guess"] = g
+        out.update(fields("plan_" + name, info))
+        e.close()
+    return out
+
+
+def run_map():
+    import correlation_amd as ca
+    e, rec = solved("grid", ca.FM_UVUXUYVXVY, ca.IM_BICUBIC)
+    out = {}
+    for radius, window, name in ((RADIUS, None, "staged"), (WIDE_RADIUS, None, "fallback"), (RADIUS, (3, 5, 77, 41), "window")):
+        warped, residual, owner = e.residual_map(radius, window=window, records=rec)
+        _, tiles, fallback = e.residual_last()
+        assert (fallback > 0) == (name == "fallback"), (name, tiles, fallback)
+        out.update({"map_%s.warped" % name: warped, "map_%s.residual" % name: residual, "map_%s.owner" % name: owner,
+                    "map_%s.tiles" % name: np.array([tiles, fallback])})
+    return out
+
+
+def run_evaluate():
+    import correlation_amd as ca
+    out = {}
+    for scene in ("mix", "grid"):
+        for model, interp, name in ((ca.FM_UVUXUYVXVY, ca.IM_BICUBIC, "affine_bicubic"), (ca.FM_UV, ca.IM_BILINEAR, "uv_bilinear"),
+                                    (ca.FM_UVQ, ca.IM_BICUBIC_SEPARABLE, "uvq_separable"), (ca.FM_U, ca.IM_NEAREST, "u_nearest")):
+            e, rec = solved(scene, model, interp)
+            unc, usums = e.parameter_uncertainty(records=rec, return_sums=True)
+            pho, psums = e.photometry(records=rec, return_sums=True)
+            tag = "%s_%s" % (scene, name)
+            out.update(fields("uncertainty_" + tag, unc))
+            out.update(fields("photometry_" + tag, pho))
+            out["uncertainty_" + tag + ".sums"] = usums
+            out["photometry_" + tag + ".sums"] = psums
+            e.close()
+    return out
+
+
+def run_backward():
+    import correlation_amd as ca
+    out = {}
+    for scene in ("mix", "grid"):
+        for model, interp, name in ((ca.FM_UVUXUYVXVY, ca.IM_BICUBIC, "affine_bicubic"), (ca.FM_UV, ca.IM_BILINEAR, "uv_bilinear")):
+            e, _ = solved(scene, model, interp, update=ca.UPDATE_BACKWARD)
+            g = np.zeros((e.n_sectors, 6), np.float32)
+            g[:, :2] = TRUTH[:2]
+            out.update(fields("backward_%s_%s" % (scene, name), e.correlate_all(g)))   # (the solve's own records, none made bad)
+            e.close()
+    return out
+
+
+# (name, environment, function)
+VARIANTS = [("strain_g%d_packed%d" % (g, p), {"LK_STRAIN_GROUP": str(g), "LK_STRAIN_PACKED": str(p)}, run_strain)
+            for g in (16, 64) for p in (0, 1)]
+VARIANTS += [("outlier_g%d_cap%s" % (g, cap), {"LK_OUTLIER_GROUP": str(g), "LK_OUTLIER_LDS_CAP": cap}, run_outlier)
+             for g in (16, 64) for cap in ("0", "100000")]
+VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (16, 64)]
+VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward)]
+
+
+def compare(path_a, path_b):
+    a, b = np.load(path_a), np.load(path_b)
+    bad = sorted(set(a.files) ^ set(b.files))
+    for k in bad:
+        print("ONLY in one file: " + k)
+    same = 0
+    for k in sorted(set(a.files) & set(b.files)):
+        x, y = a[k], b[k]
+        if x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes():
+            same += 1
+            continue
+        n = int((x.view(np.uint8) != y.view(np.uint8)).sum()) if x.shape == y.shape and x.dtype == y.dtype else -1
+        print("DIFFERS: %s (%s %s / %s %s, bytes that differ: %d)" % (k, x.dtype, x.shape, y.dtype, y.shape, n))
+        bad.append(k)
+    print("%d arrays equal byte for byte, %d not" % (same, len(bad)))
+    return 1 if bad else 0
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("out", nargs="?")
+    ap.add_argument("--compare", nargs=2, metavar=("A", "B"))
+    ap.add_argument("--variant", help=argparse.SUPPRESS)   # (the child)
+    args = ap.parse_args()
+    if args.compare:
+        return compare(*args.compare)
+    if not args.out:
+        ap.error("an output file, or --compare A B")
+    if args.variant:
+        fn = {name: f for name, _, f in VARIANTS}[args.variant]
+        np.savez(args.out, **fn())
+        return 0
+    merged = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, env, _ in VARIANTS:
+            part = os.path.join(tmp, name + ".npz")
+            try:
+                status = subprocess.run([sys.executable, os.path.abspath(__file__), part, "--variant", name],
+                                        env=dict(os.environ, **env), timeout=CHILD_SECONDS).returncode
+            except subprocess.TimeoutExpired:
+                status = "none within %d s" % CHILD_SECONDS
+            if status != 0:
+                print("variant %s failed (exit status %s): stopping" % (name, status), flush=True)
+                return 1
+            with np.load(part) as z:
+                merged.update({name + "/" + k: z[k] for k in z.files})
+            print("variant %s: %d arrays" % (name, len(merged)), flush=True)
+    np.savez(args.out, **merged)
+    print("%d arrays -> %s" % (len(merged), args.out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
