@@ -162,6 +162,34 @@ PHOTOMETRY_DTYPE = np.dtype([("n_points", np.int32), ("status", np.int32)] +
                             [("reserved", np.int32, (3,))])
 assert PHOTOMETRY_DTYPE.itemsize == 64 and C.sizeof(LkPhotometryConfig) == 16 and C.sizeof(LkResidualMapConfig) == 32
 
+# speckle quality (include/lk_engine.h: lk_pattern_quality, lk_suggest_subset)
+PATTERN_OK, PATTERN_TOO_FEW, PATTERN_FLAT, PATTERN_APERTURE, PATTERN_SATURATED = range(5)
+SUBSET_OK, SUBSET_NONE, SUBSET_BAD_POINT = range(3)
+PATTERN_SUMS = 9       # int64 per sector: sum I, sum I^2, Gxx, Gyy, Gxy, n_low, n_high, min I, max I
+PATTERN_MAX_HALF = 128
+
+
+class LkPatternConfig(C.Structure):
+    _fields_ = [("slot", C.c_int), ("grey_low", C.c_int), ("grey_high", C.c_int), ("noise_sigma", C.c_float),
+                ("max_saturated", C.c_float), ("reserved", C.c_int * 3)]
+
+
+class LkSubsetConfig(C.Structure):
+    _fields_ = [("slot", C.c_int), ("half_min", C.c_int), ("half_max", C.c_int), ("half_step", C.c_int),
+                ("sssig_min", C.c_float), ("noise_sigma", C.c_float), ("reserved", C.c_int * 2)]
+
+
+# struct lk_pattern and struct lk_subset as numpy records
+PATTERN_DTYPE = np.dtype([("n_points", np.int32), ("status", np.int32), ("mean", np.float32), ("std", np.float32),
+                          ("grey_min", np.int32), ("grey_max", np.int32)] +
+                         [(k, np.float32) for k in ("frac_low", "frac_high", "sssig_x", "sssig_y", "mig", "sigma_u", "sigma_v",
+                                                    "sigma_major", "theta")] +
+                         [("reserved", np.int32)])
+SUBSET_DTYPE = np.dtype([(k, np.int32) for k in ("half", "status", "n_pixels", "clipped")] +
+                        [(k, np.float32) for k in ("sssig_x", "sssig_y", "sigma_u", "sigma_v")])
+assert PATTERN_DTYPE.itemsize == 64 and SUBSET_DTYPE.itemsize == 32
+assert C.sizeof(LkPatternConfig) == 32 and C.sizeof(LkSubsetConfig) == 32
+
 # layout of lk_result == CorrelationResult (domains.hpp:110-118), 48 bytes
 RESULT_DTYPE = np.dtype([("p", np.float32, (6,)), ("chi", np.float32),
                          ("n_points", np.int32), ("iterations", np.int32),
@@ -251,6 +279,9 @@ SYMBOLS = {
     "lk_photometry_from_sums": (C.c_int, [C.c_int, _P, _P]),
     "lk_residual_map": (C.c_int, [_P, C.POINTER(LkResidualMapConfig), _P, _P, _P, _P]),
     "lk_map_owner": (C.c_int, [C.c_int, _F, _P, C.c_double, C.c_double, C.c_double]),
+    "lk_pattern_quality": (C.c_int, [_P, C.POINTER(LkPatternConfig), _P, _P, _P]),
+    "lk_pattern_from_sums": (C.c_int, [C.c_int, _P, C.c_double, C.c_float, C.c_float, _P]),
+    "lk_suggest_subset": (C.c_int, [_P, C.POINTER(LkSubsetConfig), C.c_int, _F, _P, _P]),
     "lk_evaluate": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_evaluate_backward": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_compose_inverse": (C.c_int, [C.c_int, _F, _F, _F]),
@@ -434,6 +465,21 @@ def photometry_from_sums(n, sums8):
     out = np.zeros(1, PHOTOMETRY_DTYPE)
     if _compose_lib.lk_photometry_from_sums(int(n), s.ctypes.data_as(_P), out.ctypes.data_as(_P)) != 0:
         raise ValueError("lk_photometry_from_sums: n < 0")
+    return out[0]
+
+
+def pattern_from_sums(n, sums9, mig_sum, noise_sigma=1.0, max_saturated=1.0):
+    """lk_pattern_from_sums (host, the kernel's function): the PATTERN_DTYPE record of one sector of n samples whose nine
+    integer sums are sums9 (sum I, sum I^2, Gxx, Gyy, Gxy, n_low, n_high, min I, max I) and whose gradient-magnitude sum is
+    mig_sum."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.ascontiguousarray(sums9, np.int64).reshape(PATTERN_SUMS)
+    out = np.zeros(1, PATTERN_DTYPE)
+    if _compose_lib.lk_pattern_from_sums(int(n), s.ctypes.data_as(_P), float(mig_sum), float(noise_sigma), float(max_saturated),
+                                         out.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_pattern_from_sums: n < 0, or a noise_sigma or max_saturated that is not finite")
     return out[0]
 
 

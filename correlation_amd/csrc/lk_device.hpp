@@ -379,3 +379,40 @@ struct LkResidualMapArgs {
   double r2;                 // (double)radius squared
 };
 constexpr int kLkMapTileW = 32, kLkMapTileH = 8; // pixels per workgroup: x fastest, a wavefront covers two rows of 32
+
+// Speckle quality (lk_pattern.hip, include/lk_engine.h: lk_pattern_quality, lk_suggest_subset).  The sector pass walks the
+// level-L lists over ONE image slot (ev.und = ev.def = that image; ev.rec is not read).
+struct LkPatternArgs {
+  LkSectorEvalArgs ev;
+  struct lk_pattern *out;   // [S]
+  long long *sums;          // [S][9] or null (lk_pattern.hpp: kLkPatternSums)
+  double *mig_sum;          // [S] or null
+  int n_sectors, level;
+  int grey_low, grey_high;
+  float noise_sigma, max_saturated;
+};
+// The summed-area tables of gx2^2 and gy2^2 over a whole level-L image: two uint32 planes of rows x pitch words that wrap,
+// plane 1 (gy2^2) behind plane 0.  pitch = cols rounded up to 4, so that a thread's four columns are one aligned 16-byte
+// access; the columns behind cols repeat the row's total.
+constexpr int kLkSatThreads = 256;                           // row step: threads of the workgroup that owns an image row
+constexpr int kLkSatPixels = 4;                              //   consecutive pixels per thread
+constexpr int kLkSatRowTile = kLkSatThreads * kLkSatPixels;  //   pixels per pass of the workgroup; a longer row carries on
+constexpr int kLkSatBandRows = 32;                           // column step: rows per band
+constexpr int kLkSatColThreads = 64;                         //   a wavefront per band and 256 columns, four columns per lane
+struct LkSatArgs {
+  const uint8_t *img;       // level-L image, pitch == cols
+  int rows, cols, pitch;
+  uint32_t *table;          // [2][rows][pitch]
+  uint32_t *band;           // [2][n_bands][pitch] band totals, then their exclusive prefix over the bands
+  int n_bands;
+};
+struct LkSubsetArgs {
+  const uint32_t *table;    // [2][rows][pitch]
+  int rows, cols, pitch;
+  const float2 *points;     // [n_points] level-L positions
+  struct lk_subset *out;    // [n_points]
+  uint32_t *sums;           // [n_points][n_cand][2] or null: Gxx, Gyy of every candidate box
+  int n_points, n_cand, half_min, half_step;
+  uint32_t threshold;       // T = ceil(4 sssig_min)
+  float noise_sigma;
+};

@@ -2968,6 +2968,49 @@ int lk_internal_pass_view(lk_engine *e, const char *who, unsigned need, int def_
   return LK_ERROR_NONE;
 }
 
+int lk_internal_image_view(lk_engine *e, const char *who, int slot, int need_sectors, LkPassView *v) {
+  const std::string w(who);
+  if (slot != LK_IMG_UND && slot != LK_IMG_DEF && slot != LK_IMG_NXT)
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": unknown slot (LK_IMG_UND, LK_IMG_DEF or LK_IMG_NXT)");
+  if (need_sectors && (!e->committed || e->S <= 0))
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": no committed sectors (call lk_commit_sectors)");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  *v = LkPassView{};
+  const int level = e->cfg.py_start;
+  if (need_sectors && e->recommit_pending) { // lk_update_sector moved lists: rebuild them as the next solve would
+    e->recommit_pending = false;
+    if (int rc = commit_impl(e, true))
+      return rc;
+  }
+  {
+    std::unique_lock<std::mutex> lock(e->nxt_mu, std::defer_lock);
+    if (slot == LK_IMG_NXT)
+      lock.lock();
+    const DevImage &im = e->img[slot];
+    if (!im.valid || !im.lvl[level])
+      return e->fail(LK_ERROR_BAD_DOMAIN, w + ": the image of that slot is not set (lk_set_image)");
+    if (slot == LK_IMG_NXT && e->nxt_pending) // filled on its own stream: the engine's stream must see the finished pyramid
+      HIPCHK(hipStreamWaitEvent(e->stream, e->nxt_done, 0));
+    v->und = v->def = im.lvl[level];
+    v->urows = v->drows = im.rows >> level;
+    v->ucols = v->dcols = im.cols >> level;
+  }
+  v->level = level;
+  v->stream = e->stream;
+  v->model = e->cfg.fitting_model;
+  v->interp = e->cfg.interpolation;
+  if (need_sectors) {
+    v->S = e->S;
+    v->xy = e->d_xy[level].p;
+    v->off = e->d_off[level].p;
+    v->rect = e->d_rect[level].p;
+    v->h_rect0 = e->h_rect[0].data();
+    v->h_off0 = e->h_off[0].data();
+    v->center = e->d_center.p;
+  }
+  return LK_ERROR_NONE;
+}
+
 extern "C" {
 
 int lk_get_results_device(lk_engine *e, const void **d_records) {

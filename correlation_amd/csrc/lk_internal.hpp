@@ -86,7 +86,8 @@ int lk_internal_reseed_stats(lk_engine *e, const unsigned long long totals[5]);
 struct LkPassSlot {
   virtual ~LkPassSlot() = default;
 };
-enum LkPass { LK_PASS_RESEED, LK_PASS_STRAIN, LK_PASS_UNCERTAINTY, LK_PASS_OUTLIER, LK_PASS_TRACK, LK_PASS_RESIDUAL, LK_PASS_COUNT };
+enum LkPass { LK_PASS_RESEED, LK_PASS_STRAIN, LK_PASS_UNCERTAINTY, LK_PASS_OUTLIER, LK_PASS_TRACK, LK_PASS_RESIDUAL, LK_PASS_PATTERN,
+              LK_PASS_COUNT };
 LkPassSlot **lk_internal_pass_slot(lk_engine *e, int which);
 
 // What a post-processing pass reads of the engine (lk_strain_field, lk_parameter_uncertainty, lk_flag_outliers,
@@ -118,6 +119,12 @@ struct LkPassView {
   int window_frames;
 };
 int lk_internal_pass_view(lk_engine *e, const char *who, unsigned need, int def_slot, LkPassView *v);
+// What a pass reads that looks at ONE image (lk_pattern_quality, lk_suggest_subset): the level-L pyramid of `slot`
+// (LK_IMG_UND, LK_IMG_DEF or LK_IMG_NXT, whose fill the engine's stream then waits for), L = py_start, as both `und` and
+// `def` of the view with its dimensions - no other slot has to be set.  need_sectors: the committed sectors with the
+// level-L lists, a pending rebuild of them finished first as for LK_VIEW_IMAGES; without it the call needs no sectors and
+// the view has S = 0 and no lists.  Allowed in every mode; every refusal is prefixed with `who`.
+int lk_internal_image_view(lk_engine *e, const char *who, int slot, int need_sectors, LkPassView *v);
 
 // Bench hooks (scripts/*_bench.py; exported, not part of include/*.h): of the last call of a pass, the HIP-event time of its
 // device part - for the passes with a cell grid the bounding box with its round trip, the grid kernels, the prep and the
@@ -134,4 +141,8 @@ int lk_internal_track_last(lk_engine *e, float *device_ms, int *group, double *m
 // lk_photometry or lk_residual_map: the pixel tiles of a map (0 after lk_photometry) and how many of them walked global
 // memory because their candidates did not fit into LDS
 int lk_internal_residual_last(lk_engine *e, float *device_ms, int *tiles, int *fallback_tiles);
+// lk_pattern_quality or lk_suggest_subset: the two tile constants of the table build (pixels a workgroup scans per pass of
+// the row step, rows per band of the column step), and of that time the table build and the query (both 0 after
+// lk_pattern_quality)
+int lk_internal_pattern_last(lk_engine *e, float *device_ms, int *row_tile, int *band_rows, float *build_ms, float *query_ms);
 }

@@ -124,3 +124,12 @@ hipError_t lk_launch_map_prep(const lk_result *rec, const float2 *center, int n_
                               LkMapSector *pack, hipStream_t st);
 // one workgroup per tile of kLkMapTileW x kLkMapTileH pixels of the window; *n_tiles = the tiles launched
 hipError_t lk_launch_residual_map(const LkResidualMapArgs &a, int model, int interp, int *n_tiles, hipStream_t st);
+
+// ---- lk_pattern.hip: speckle quality (lk_pattern_quality, lk_suggest_subset)
+// group: 16, 64 or 512 lanes per sector (lk_bw_group of the level-0 sample count); a.ev.order lists that group's sectors
+hipError_t lk_launch_pattern(const LkPatternArgs &a, int group, hipStream_t st);
+// the two tables of one image: a row step, then the column step's three kernels (band totals, their prefix over the bands,
+// the seeded band scans); the kernel boundaries on the stream are the only ordering between workgroups
+hipError_t lk_launch_sat_build(const LkSatArgs &a, hipStream_t st);
+// a thread per point: every candidate's box sums from the four corners, the smallest passing candidate, the record
+hipError_t lk_launch_subset_query(const LkSubsetArgs &a, hipStream_t st);

@@ -486,6 +486,53 @@ class HipCorrelationEngine:
         """lk_map_owner: the residual map's owner rule on the host (no engine needed)."""
         return _ffi.map_owner(centers, X, Y, radius, good)
 
+    # ---- speckle quality: is the pattern good enough, how large must the subsets be ----------------------
+    def pattern_quality(self, slot=_ffi.IMG_UND, grey_low=0, grey_high=255, noise_sigma=1.0, max_saturated=1.0,
+                        return_sums=False):
+        """lk_pattern_quality: a PATTERN_DTYPE array [S] (mean, contrast, SSSIG, MIG, saturated fractions and the predicted
+        displacement error of every committed sector) from the level-py_start image of `slot` alone; with return_sums also
+        the nine int64 sums [S][9] and the gradient-magnitude sums [S].  No engine state changes."""
+        cfg = _ffi.LkPatternConfig(int(slot), int(grey_low), int(grey_high), float(noise_sigma), float(max_saturated))
+        out = np.zeros(self.n_sectors, _ffi.PATTERN_DTYPE)
+        sums = np.zeros((self.n_sectors, _ffi.PATTERN_SUMS), np.int64) if return_sums else None
+        mig = np.zeros(self.n_sectors, np.float64) if return_sums else None
+        self._chk(self.lib.lk_pattern_quality(self._h, C.byref(cfg), out.ctypes.data_as(C.c_void_p),
+                                              sums.ctypes.data_as(C.c_void_p) if return_sums else None,
+                                              mig.ctypes.data_as(C.c_void_p) if return_sums else None))
+        return (out, sums, mig) if return_sums else out
+
+    def suggest_subset(self, points, sssig_min, half_min=5, half_max=40, half_step=1, slot=_ffi.IMG_UND, noise_sigma=1.0,
+                       return_sums=False):
+        """lk_suggest_subset: a SUBSET_DTYPE array [Q], for every point [Q][2] (level-py_start pixels of the image of `slot`)
+        the smallest half-width of half_min, half_min + half_step, ... <= half_max whose box has SSSIG_x and SSSIG_y >=
+        sssig_min; with return_sums also Gxx and Gyy of every candidate box, uint32 [Q][n_cand][2].  Needs no sectors; no
+        engine state changes."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        cfg = _ffi.LkSubsetConfig(int(slot), int(half_min), int(half_max), int(half_step), float(sssig_min), float(noise_sigma))
+        n_cand = max((int(half_max) - int(half_min)) // max(int(half_step), 1) + 1, 1)
+        out = np.zeros(len(pts), _ffi.SUBSET_DTYPE)
+        sums = np.zeros((len(pts), n_cand, 2), np.uint32) if return_sums else None
+        self._chk(self.lib.lk_suggest_subset(self._h, C.byref(cfg), len(pts), _ffi.fptr(pts), out.ctypes.data_as(C.c_void_p),
+                                             sums.ctypes.data_as(C.c_void_p) if return_sums else None))
+        return (out, sums) if return_sums else out
+
+    def pattern_last(self):
+        """Bench hook: (device ms, pixels per pass of the row step, rows per band of the column step, table build ms, query
+        ms) of the last pattern_quality or suggest_subset call (the last two 0 after pattern_quality)."""
+        ms, build, query = C.c_float(), C.c_float(), C.c_float()
+        tile, band = C.c_int(), C.c_int()
+        fn = self.lib.lk_internal_pattern_last
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float),
+                       C.POINTER(C.c_float)]
+        self._chk(fn(self._h, C.byref(ms), C.byref(tile), C.byref(band), C.byref(build), C.byref(query)))
+        return ms.value, tile.value, band.value, build.value, query.value
+
+    @staticmethod
+    def pattern_from_sums(n, sums9, mig_sum, noise_sigma=1.0, max_saturated=1.0):
+        """lk_pattern_from_sums: the kernel's record arithmetic on the host (no engine needed)."""
+        return _ffi.pattern_from_sums(n, sums9, mig_sum, noise_sigma, max_saturated)
+
     # ---- material-point tracks: chosen points carried through a solved sequence --------------------------
     def track_points(self, points, radius, n_frames=None, records=None, mode=_ffi.TRACK_TOTAL, source=None, state=None,
                      chi_max=0.0, min_neighbours=3, tensor=_ffi.STRAIN_GREEN_LAGRANGE):

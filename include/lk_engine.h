@@ -929,6 +929,117 @@ int lk_residual_map(lk_engine *e, const lk_residual_map_config *cfg, const lk_re
  * that is not finite and positive. */
 int lk_map_owner(int n, const float *centers_xy, const uint8_t *good, double X, double Y, double radius);
 
+/* ---- speckle quality: is the pattern good enough, and how large must the subsets be ---------------- */
+/* Every pass above judges a field after the solve.  These two answer what a user asks before the first one, from one image
+ * alone: lk_pattern_quality gives every committed sector the classical figures of its speckle pattern - the sum of squared
+ * subset intensity gradients (SSSIG) and the mean intensity gradient (MIG) of Pan et al., the structure tensor and the
+ * displacement error it predicts for a given camera noise, the saturated fraction; lk_suggest_subset gives, for any points,
+ * the smallest square subset around each whose SSSIG reaches a threshold - it needs no sectors: it is what one runs to
+ * choose them (csrc/lk_pattern.hip).
+ *   level     both calls work at L = py_start and read ONE image slot, cfg->slot = LK_IMG_UND, LK_IMG_DEF or LK_IMG_NXT; only
+ *             that slot has to be set.  Ring slots are out of scope.
+ *   pixels    I(x, y) of the level-L image, u8 taken as integers.  The doubled central differences use clamped neighbours:
+ *               gx2 = I(min(x + 1, cols - 1), y) - I(max(x - 1, 0), y),  gy2 alike in y;
+ *             the gradient is gx2 / 2, so every sum below is an integer: Gxx = sum gx2^2, Gyy = sum gy2^2,
+ *             Gxy = sum gx2 gy2, and SSSIG_x = Gxx / 4, SSSIG_y = Gyy / 4.
+ *
+ * lk_pattern_quality
+ *   samples   the sector's level-L list or implicit rectangle, by lk_parameter_uncertainty's walk and lane groups (16 / 64 /
+ *             512 lanes from the level-0 sample count; lane j takes the samples j, j + G, ...).  A sample's pixel is its node
+ *             ((int)(x + 0.5f), (int)(y + 0.5f)), clamped to the image, read from the chosen slot.
+ *   sums      nine int64 per sector, in this order: sum I, sum I^2, Gxx, Gyy, Gxy, n_low = the samples with I <= grey_low,
+ *             n_high = those with I >= grey_high, min I, max I.  Integer sums are the same bits in any order.  And one
+ *             double: mig_sum = sum sqrt((double)(gx2^2 + gy2^2)), added in the uncertainty pass's fixed order, so a
+ *             sector's numbers and its record are the same bytes in any batch or mode.
+ *   record    lk_pattern_from_sums (one function for the kernel and the host, csrc/lk_pattern.hpp): the sums converted to
+ *             double first, all in double without fused multiply-add, each output rounded to float once; N = (double)n:
+ *               mean = S1 / N;  std = sqrt(max(0, N S2 - S1 S1)) / N (population);  grey_min, grey_max;
+ *               frac_low = n_low / N, frac_high = n_high / N;  sssig_x = Gxx / 4, sssig_y = Gyy / 4 (sums, as Pan's);
+ *               mig = mig_sum / (2 N);
+ *               det = Gxx Gyy - Gxy Gxy;  sigma_u = s sqrt(8 Gyy / det), sigma_v = s sqrt(8 Gxx / det) with
+ *               s = noise_sigma (<= 0 means 1): Cov = 2 s^2 G^-1 - noise s in both images, G the structure tensor in
+ *               gradient units - so c00 = s^2 (8 Gyy / det), c11 = s^2 (8 Gxx / det), c01 = s^2 (-8 Gxy / det);
+ *               sigma_major = sqrt((c00 + c11) / 2 + sqrt(((c00 - c11) / 2)^2 + c01^2)), theta = atan2(2 c01, c00 - c11) / 2,
+ *               the ellipse formulas of lk_parameter_uncertainty.  Level-L pixels.
+ *             The image decides the record, not the fitting model: it is always two-dimensional.
+ *   status    checked in this order: TOO_FEW  n < 2 (every field but n_points is 0);  FLAT  Gxx + Gyy == 0;  APERTURE
+ *             det <= 1e-6 Gxx Gyy in double (one of them 0 included; scale-free, lk_strain_field's degenerate rule);
+ *             SATURATED  (double)(n_low + n_high) > (double)max_saturated N;  OK.  FLAT and APERTURE leave the four sigma
+ *             fields and theta at 0; everything else is filled.
+ *
+ * lk_suggest_subset
+ *   candidates half-widths h = half_min, half_min + half_step, ... <= half_max, with 1 <= half_min <= half_max <=
+ *             LK_PATTERN_MAX_HALF and half_step >= 1; n_cand = (half_max - half_min) / half_step + 1.
+ *   point     (x, y), a float position in level-L pixels; its node is ((int)(x + 0.5f), (int)(y + 0.5f)).  A position that
+ *             is not finite or a node outside the image: BAD_POINT (every other field and the point's sums are 0).
+ *   box       of a candidate: node +- h, clipped to the image.  Gxx and Gyy of a box are sums over its pixels of the
+ *             definitions above (the clamped neighbours are those of the IMAGE, not of the box).
+ *   rule      T = ceil(4 (double)sssig_min) as an integer; a candidate passes when Gxx >= T and Gyy >= T, compared as
+ *             integers.  The suggestion is the smallest passing candidate (status OK); if none passes the status is NONE and
+ *             the box reported is the largest candidate's.  Nested boxes of non-negative terms make the rule monotone.
+ *   record    half, status, n_pixels and clipped (0 / 1) of the reported box, sssig_x = Gxx / 4, sssig_y = Gyy / 4, and Pan's
+ *             sigma_u = s sqrt(2 / sssig_x), sigma_v = s sqrt(2 / sssig_y) in double, rounded to float once (0 where the
+ *             sum is 0).  A point's record depends on that point, the image and the configuration only.
+ *   tables    the call builds summed-area tables of gx2^2 and gy2^2 over the whole level-L image, on every call, and answers
+ *             every candidate from four corners.  The tables are uint32 and wrap: a clipped box has at most 257 x 257 pixels
+ *             of at most 255^2 each, 4 294 836 225 < 2^32 in all, so the four-corner difference modulo 2^32 is the exact sum
+ *             although the table itself wraps many times.  That is why LK_PATTERN_MAX_HALF is 128; it halves the footprint
+ *             and the traffic against 64-bit tables.
+ *
+ *   modes     both calls are allowed in every mode, reference-order mode included, and change no engine state: records,
+ *             guesses, last parameters, counters and lk_get_reseed_info stay byte for byte.  lk_pattern_quality carries out a
+ *             rebuild of the sample lists that waits for the next solve first, as lk_parameter_uncertainty does.  Both
+ *             synchronise the engine's stream before they return.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message prefixed by the function's name, outputs untouched: null configuration or
+ *             output; unknown slot, or slot not set; non-zero reserved words; grey_low / grey_high outside 0 .. 255;
+ *             noise_sigma or max_saturated not finite; lk_pattern_quality without committed sectors; lk_suggest_subset with
+ *             n_points < 1, null points, a bad candidate range, or a threshold that is not finite, <= 0 or above 2^32 - 1.
+ *   scope     one engine, one grey image.  lk_group, lk_tracker, the report CSV and the CudaClass adapter do not call them. */
+#define LK_PATTERN_MAX_HALF 128
+enum { LK_PATTERN_OK = 0, LK_PATTERN_TOO_FEW = 1, LK_PATTERN_FLAT = 2, LK_PATTERN_APERTURE = 3, LK_PATTERN_SATURATED = 4 };
+enum { LK_SUBSET_OK = 0, LK_SUBSET_NONE = 1, LK_SUBSET_BAD_POINT = 2 };
+typedef struct lk_pattern_config {
+  int slot;                 /* LK_IMG_UND, LK_IMG_DEF or LK_IMG_NXT */
+  int grey_low, grey_high;  /* 0 .. 255: I <= grey_low counts as low, I >= grey_high as high */
+  float noise_sigma;        /* camera noise in grey levels; <= 0: 1 */
+  float max_saturated;      /* SATURATED when (n_low + n_high) / n exceeds it */
+  int reserved[3];          /* must be 0 */
+} lk_pattern_config;
+/* (struct tags without typedefs, as struct lk_photometry) */
+struct lk_pattern {                       /* 64 bytes, one per sector */
+  int32_t n_points, status;
+  float mean, std;                        /* grey levels; population standard deviation */
+  int32_t grey_min, grey_max;
+  float frac_low, frac_high;
+  float sssig_x, sssig_y;                 /* Gxx / 4, Gyy / 4 */
+  float mig;                              /* mean intensity gradient */
+  float sigma_u, sigma_v;                 /* predicted standard deviation of u and v, level-L pixels */
+  float sigma_major, theta;               /* major axis of that covariance and its angle */
+  int32_t reserved;
+};
+/* out: [S].  sums_out: [S][9] int64 or NULL.  mig_sum_out: [S] doubles or NULL.  Synchronous.  Changes no engine state. */
+int lk_pattern_quality(lk_engine *e, const lk_pattern_config *cfg, struct lk_pattern *out, int64_t *sums_out, double *mig_sum_out);
+/* the kernel's own function compiled for the host: the record of one sector of n samples with the nine sums `sums9` and
+ * mig_sum.  LK_ERROR_BAD_DOMAIN for a null pointer, n < 0, or a noise_sigma or max_saturated that is not finite. */
+int lk_pattern_from_sums(int n, const int64_t *sums9, double mig_sum, float noise_sigma, float max_saturated, struct lk_pattern *out);
+typedef struct lk_subset_config {
+  int slot;                           /* as lk_pattern_config */
+  int half_min, half_max, half_step;  /* candidates: box side = 2 h + 1 */
+  float sssig_min;                    /* the threshold on SSSIG_x and SSSIG_y, squared grey levels */
+  float noise_sigma;                  /* as lk_pattern_config */
+  int reserved[2];                    /* must be 0 */
+} lk_subset_config;
+struct lk_subset {                    /* 32 bytes, one per point */
+  int32_t half, status;               /* the suggested half-width (NONE: the largest candidate; BAD_POINT: 0) */
+  int32_t n_pixels, clipped;          /* of the reported box: pixels after clipping to the image; 1 if it was clipped */
+  float sssig_x, sssig_y;
+  float sigma_u, sigma_v;             /* s sqrt(2 / sssig) */
+};
+/* points_xy: [n_points][2] level-L positions.  out: [n_points].  sums_out: [n_points][n_cand][2] uint32 {Gxx, Gyy} of every
+ * candidate box, or NULL.  Synchronous.  Changes no engine state; needs no committed sectors. */
+int lk_suggest_subset(lk_engine *e, const lk_subset_config *cfg, int n_points, const float *points_xy, struct lk_subset *out,
+                      uint32_t *sums_out);
+
 /* ---- stand-alone pieces (known-answer tests, same kernels as the batch path) ------- */
 /* one evaluation of one sector at one level: raw sums A (6x6 row-major, upper valid),
  * b, chi (unscaled), error flag (apply_model_and_interpolate, correlation_class.cpp:131) */

@@ -171,13 +171,36 @@ def run_backward():
     return out
 
 
+def run_pattern():
+    import correlation_amd as ca
+    out = {}
+    rng = np.random.default_rng(13)
+    pts = rng.uniform(-3.0, 258.0, (97, 2)).astype(np.float32)
+    pts[5] = (np.nan, 40.0)
+    for scene in ("mix", "grid"):
+        e, _ = solved(scene, ca.FM_UVUXUYVXVY, ca.IM_BICUBIC)
+        for slot, name in ((ca.IMG_UND, "und"), (ca.IMG_DEF, "def")):
+            pat, sums, mig = e.pattern_quality(slot=slot, grey_low=20, grey_high=235, noise_sigma=0.75, max_saturated=0.3,
+                                               return_sums=True)
+            tag = "pattern_%s_%s" % (scene, name)
+            out.update(fields(tag, pat))
+            out[tag + ".sums"] = sums
+            out[tag + ".mig_sum"] = mig
+        sub, box = e.suggest_subset(pts, 1e5, 2, 40, 3, return_sums=True)
+        out.update(fields("subset_" + scene, sub))
+        out["subset_" + scene + ".sums"] = box
+        e.close()
+    return out
+
+
 # (name, environment, function)
 VARIANTS = [("strain_g%d_packed%d" % (g, p), {"LK_STRAIN_GROUP": str(g), "LK_STRAIN_PACKED": str(p)}, run_strain)
             for g in (16, 64) for p in (0, 1)]
 VARIANTS += [("outlier_g%d_cap%s" % (g, cap), {"LK_OUTLIER_GROUP": str(g), "LK_OUTLIER_LDS_CAP": cap}, run_outlier)
              for g in (16, 64) for cap in ("0", "100000")]
 VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (16, 64)]
-VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward)]
+VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
+             ("pattern", {}, run_pattern)]
 
 
 def compare(path_a, path_b):
