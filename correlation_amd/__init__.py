@@ -27,6 +27,9 @@ from ._ffi import (MAP_NO_OWNER, PHOTO_BAD_RECORD, PHOTO_FLAT, PHOTO_OK, PHOTO_O
                    PHOTO_TOO_FEW, PHOTOMETRY_DTYPE, map_owner, photometry_from_sums)
 from ._ffi import (PATTERN_APERTURE, PATTERN_DTYPE, PATTERN_FLAT, PATTERN_MAX_HALF, PATTERN_OK, PATTERN_SATURATED,  # noqa: F401
                    PATTERN_SUMS, PATTERN_TOO_FEW, SUBSET_BAD_POINT, SUBSET_DTYPE, SUBSET_NONE, SUBSET_OK, pattern_from_sums)
+from ._ffi import (FIELD_ALL, FIELD_BISQUARE, FIELD_CHANNELS, FIELD_DEFORMED, FIELD_DEGENERATE, FIELD_E1, FIELD_E2,  # noqa: F401
+                   FIELD_EXX, FIELD_EXY, FIELD_EYY, FIELD_MISFIT, FIELD_OK, FIELD_REFERENCE, FIELD_THETA, FIELD_TOO_FEW, FIELD_U,
+                   FIELD_UNIFORM, FIELD_UX, FIELD_UY, FIELD_V, FIELD_VX, FIELD_VY, FIELD_X0, FIELD_Y0, field_from_sums)
 from .engine import HipCorrelationEngine, LkError  # noqa: F401
 from . import speckle  # noqa: F401
 from . import tracker  # noqa: F401

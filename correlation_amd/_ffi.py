@@ -190,6 +190,24 @@ SUBSET_DTYPE = np.dtype([(k, np.int32) for k in ("half", "status", "n_pixels", "
 assert PATTERN_DTYPE.itemsize == 64 and SUBSET_DTYPE.itemsize == 32
 assert C.sizeof(LkPatternConfig) == 32 and C.sizeof(LkSubsetConfig) == 32
 
+# field map (include/lk_engine.h: lk_field_map)
+FIELD_OK, FIELD_TOO_FEW, FIELD_DEGENERATE = range(3)
+FIELD_UNIFORM, FIELD_BISQUARE = 0, 1
+FIELD_REFERENCE, FIELD_DEFORMED = 0, 1
+FIELD_CHANNELS = ("u", "v", "ux", "uy", "vx", "vy", "exx", "eyy", "exy", "e1", "e2", "theta", "x0", "y0", "misfit")
+(FIELD_U, FIELD_V, FIELD_UX, FIELD_UY, FIELD_VX, FIELD_VY, FIELD_EXX, FIELD_EYY, FIELD_EXY, FIELD_E1, FIELD_E2, FIELD_THETA,
+ FIELD_X0, FIELD_Y0, FIELD_MISFIT) = (1 << i for i in range(15))
+FIELD_ALL = (1 << 15) - 1
+
+
+class LkFieldMapConfig(C.Structure):
+    _fields_ = [("radius", C.c_float), ("chi_max", C.c_float), ("min_neighbours", C.c_int), ("tensor", C.c_int),
+                ("weight", C.c_int), ("frame", C.c_int), ("iterations", C.c_int), ("x0", C.c_int), ("y0", C.c_int),
+                ("nx", C.c_int), ("ny", C.c_int), ("stride", C.c_int), ("channels", C.c_uint32), ("reserved", C.c_int * 3)]
+
+
+assert C.sizeof(LkFieldMapConfig) == 64
+
 # layout of lk_result == CorrelationResult (domains.hpp:110-118), 48 bytes
 RESULT_DTYPE = np.dtype([("p", np.float32, (6,)), ("chi", np.float32),
                          ("n_points", np.int32), ("iterations", np.int32),
@@ -279,6 +297,8 @@ SYMBOLS = {
     "lk_photometry_from_sums": (C.c_int, [C.c_int, _P, _P]),
     "lk_residual_map": (C.c_int, [_P, C.POINTER(LkResidualMapConfig), _P, _P, _P, _P]),
     "lk_map_owner": (C.c_int, [C.c_int, _F, _P, C.c_double, C.c_double, C.c_double]),
+    "lk_field_map": (C.c_int, [_P, C.POINTER(LkFieldMapConfig), _P, _P, _P, _P]),
+    "lk_field_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_double, _P, C.c_int, _F, _I]),
     "lk_pattern_quality": (C.c_int, [_P, C.POINTER(LkPatternConfig), _P, _P, _P]),
     "lk_pattern_from_sums": (C.c_int, [C.c_int, _P, C.c_double, C.c_float, C.c_float, _P]),
     "lk_suggest_subset": (C.c_int, [_P, C.POINTER(LkSubsetConfig), C.c_int, _F, _P, _P]),
@@ -516,6 +536,21 @@ def track_step(mode, min_neighbours, n, sums11, state8, tensor=STRAIN_GREEN_LAGR
                                   int(tensor), out.ctypes.data_as(_P)) != 0:
         raise ValueError("lk_track_step: n < 0, min_neighbours < 3, or an unknown mode or tensor")
     return out[0], st
+
+
+def field_from_sums(min_neighbours, n, W, sums11, tensor=STRAIN_GREEN_LAGRANGE):
+    """lk_field_from_sums (host, the kernel's fit of one node): the window's count n, weight sum W and 11 weighted sums ->
+    (status, float32 [12] = u, v, ux, uy, vx, vy, exx, eyy, exy, e1, e2, theta; all NaN unless the status is FIELD_OK)."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.ascontiguousarray(sums11, np.float64).reshape(11)
+    out = np.zeros(12, np.float32)
+    status = C.c_int(-1)
+    if _compose_lib.lk_field_from_sums(int(min_neighbours), int(n), float(W), s.ctypes.data_as(_P), int(tensor), fptr(out),
+                                       C.byref(status)) != 0:
+        raise ValueError("lk_field_from_sums: n < 0, min_neighbours < 3 or an unknown tensor")
+    return status.value, out
 
 
 def gauges_from_tracks(tracks, pairs):

@@ -380,6 +380,23 @@ struct LkResidualMapArgs {
 };
 constexpr int kLkMapTileW = 32, kLkMapTileH = 8; // pixels per workgroup: x fastest, a wavefront covers two rows of 32
 
+// Field map (lk_field.hip, include/lk_engine.h: lk_field_map): the windowed plane fit at the nodes of a regular grid, a
+// thread per node, in tiles of kLkMapTileW x kLkMapTileH nodes.
+struct LkFieldArgs {
+  LkReseedGrid grid;         // over the level-0 centres, cell = radius
+  const float4 *pack;        // [S] {cx, cy, u, v} of a good sector, cx = NaN for one that is not (lk_pack_prep_kernel)
+  float *maps;               // [C][ny][nx], the selected channels in ascending bit order; null when channels == 0
+  int32_t *neighbours;       // [ny][nx] or null
+  uint8_t *status;           // [ny][nx] or null
+  uint32_t *fallback;        // [1] tiles whose candidates were not staged in LDS (zeroed before the launch)
+  int n_sectors, min_neighbours, tensor, iterations;
+  int x0, y0, nx, ny, stride; // node (i, j) is the level-0 position (x0 + i stride, y0 + j stride)
+  int tiles_x;
+  int walk;                  // != 0: no tile stages (the LK_FIELD_WALK hook)
+  uint32_t channels;
+  double r2;                 // (double)radius squared
+};
+
 // Speckle quality (lk_pattern.hip, include/lk_engine.h: lk_pattern_quality, lk_suggest_subset).  The sector pass walks the
 // level-L lists over ONE image slot (ev.und = ev.def = that image; ev.rec is not read).
 struct LkPatternArgs {

@@ -87,11 +87,11 @@ struct LkPassSlot {
   virtual ~LkPassSlot() = default;
 };
 enum LkPass { LK_PASS_RESEED, LK_PASS_STRAIN, LK_PASS_UNCERTAINTY, LK_PASS_OUTLIER, LK_PASS_TRACK, LK_PASS_RESIDUAL, LK_PASS_PATTERN,
-              LK_PASS_COUNT };
+              LK_PASS_FIELD, LK_PASS_COUNT };
 LkPassSlot **lk_internal_pass_slot(lk_engine *e, int which);
 
 // What a post-processing pass reads of the engine (lk_strain_field, lk_parameter_uncertainty, lk_flag_outliers,
-// lk_track_points, lk_photometry, lk_residual_map).  Allowed in every mode, reference-order included.  `need` says what the
+// lk_track_points, lk_photometry, lk_residual_map, lk_field_map).  Allowed in every mode, reference-order included.  `need` says what the
 // call depends on; every refusal is prefixed with `who`, the function the caller called.
 enum : unsigned {
   LK_VIEW_RECORDS = 1u, // the engine-held records of a finished batch solve of the committed sectors (`result`)
@@ -145,4 +145,7 @@ int lk_internal_residual_last(lk_engine *e, float *device_ms, int *tiles, int *f
 // the row step, rows per band of the column step), and of that time the table build and the query (both 0 after
 // lk_pattern_quality)
 int lk_internal_pattern_last(lk_engine *e, float *device_ms, int *row_tile, int *band_rows, float *build_ms, float *query_ms);
+// lk_field_map: the node tiles of the map and how many of them walked global memory because their candidates did not fit
+// into LDS (all of them under LK_FIELD_WALK=1)
+int lk_internal_field_last(lk_engine *e, float *device_ms, int *tiles, int *fallback_tiles);
 }

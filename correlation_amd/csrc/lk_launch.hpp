@@ -133,3 +133,7 @@ hipError_t lk_launch_pattern(const LkPatternArgs &a, int group, hipStream_t st);
 hipError_t lk_launch_sat_build(const LkSatArgs &a, hipStream_t st);
 // a thread per point: every candidate's box sums from the four corners, the smallest passing candidate, the record
 hipError_t lk_launch_subset_query(const LkSubsetArgs &a, hipStream_t st);
+
+// ---- lk_field.hip: dense displacement and strain maps (lk_field_map)
+// one workgroup per tile of kLkMapTileW x kLkMapTileH nodes; weight, frame: LK_FIELD_*; *n_tiles = the tiles launched
+hipError_t lk_launch_field_map(const LkFieldArgs &a, int weight, int frame, int *n_tiles, hipStream_t st);

@@ -1,5 +1,5 @@
 // lk_neighbours.hpp - device side of the passes that look for a position's neighbours on the cell grid over the sector
-// centres (lk_reseed.hip, lk_strain.hip, lk_outlier.hip, lk_track.hip, the residual map of lk_residual.hip): the good rule
+// centres (lk_reseed.hip, lk_strain.hip, lk_outlier.hip, lk_track.hip, lk_field.hip, the residual map of lk_residual.hip): the good rule
 // of a record, the cell of a position, the 3 x 3 cells around it, the walk of their members by a lane group, and the sums
 // of the windowed plane fit.  The device half of lk_pass.hpp; light on purpose - nothing of the solve (lk_solver_common.hpp)
 // comes with it.  A new neighbour pass starts here ("adding a pass").

@@ -17,10 +17,10 @@ struct LkPlaneFit {
   double Cxx, Cxy, Cyy, CC, D; // moments of the centres, Cxx Cyy, the determinant
   double ux, uy, vx, vy, u0, v0;
 };
-__host__ __device__ inline LkPlaneFit lk_plane_fit(int count, const double *sums11) {
+// lk_plane_fit_w is the same fit of a weighted window (lk_field.hpp): n = the sum of the weights, the sums weighted alike.
+__host__ __device__ inline LkPlaneFit lk_plane_fit_w(double n, const double *sums11) {
   const double Sx = sums11[0], Sy = sums11[1], Sxx = sums11[2], Sxy = sums11[3], Syy = sums11[4], Su = sums11[5];
   const double Sxu = sums11[6], Syu = sums11[7], Sv = sums11[8], Sxv = sums11[9], Syv = sums11[10];
-  const double n = (double)count;
   const double Cxx = Sxx - Sx * Sx / n, Cxy = Sxy - Sx * Sy / n, Cyy = Syy - Sy * Sy / n;
   const double Cxu = Sxu - Sx * Su / n, Cyu = Syu - Sy * Su / n, Cxv = Sxv - Sx * Sv / n, Cyv = Syv - Sy * Sv / n;
   const double CC = Cxx * Cyy, D = CC - Cxy * Cxy;
@@ -31,6 +31,7 @@ __host__ __device__ inline LkPlaneFit lk_plane_fit(int count, const double *sums
   f.u0 = Su / n - f.ux * (Sx / n) - f.uy * (Sy / n), f.v0 = Sv / n - f.vx * (Sx / n) - f.vy * (Sy / n);
   return f;
 }
+__host__ __device__ inline LkPlaneFit lk_plane_fit(int count, const double *sums11) { return lk_plane_fit_w((double)count, sums11); }
 
 // grad4 = {ux, uy, vx, vy} as stored (float); out6 = {exx, eyy, exy, e1, e2, theta}.  Computed in double, each result
 // rounded to float once.  Returns 1 for an unknown tensor (out6 untouched), else 0.

@@ -533,6 +533,57 @@ class HipCorrelationEngine:
         """lk_pattern_from_sums: the kernel's record arithmetic on the host (no engine needed)."""
         return _ffi.pattern_from_sums(n, sums9, mig_sum, noise_sigma, max_saturated)
 
+    # ---- field map: dense displacement and strain maps on a regular grid of nodes ------------------------
+    def field_map(self, radius, window, stride=1, channels=("u", "v"), weight=_ffi.FIELD_UNIFORM, frame=_ffi.FIELD_REFERENCE,
+                  iterations=4, records=None, chi_max=0.0, min_neighbours=3, tensor=_ffi.STRAIN_GREEN_LAGRANGE,
+                  want=("neighbours", "status")):
+        """lk_field_map: the windowed (optionally bisquare-weighted) plane fit of the good sectors at every node
+        (x0 + i stride, y0 + j stride) of window = (x0, y0, nx, ny), level-0 pixels, in the reference frame or - frame =
+        FIELD_DEFORMED, `iterations` fixed-point steps - at the material point that moved onto the node.  channels: names of
+        FIELD_CHANNELS or a mask of FIELD_* bits.  Returns a dict: every selected channel by name as float32 [ny][nx] (NaN
+        where a node has no fit), plus "neighbours" int32 [ny][nx] and "status" uint8 [ny][nx] (those named in `want`).  No
+        engine state changes."""
+        if isinstance(channels, int):
+            mask = int(channels)
+        else:
+            mask = 0
+            for name in channels:
+                mask |= 1 << _ffi.FIELD_CHANNELS.index(name)
+        x0, y0, nx, ny = (int(t) for t in window)
+        cfg = _ffi.LkFieldMapConfig(float(radius), float(chi_max), int(min_neighbours), int(tensor), int(weight), int(frame),
+                                    int(iterations), x0, y0, nx, ny, int(stride), mask & 0xffffffff)
+        names = [k for i, k in enumerate(_ffi.FIELD_CHANNELS) if mask >> i & 1]
+        shape = (max(ny, 0), max(nx, 0))
+        rec = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        maps = np.zeros((len(names),) + shape, np.float32) if names else None
+        nbrs = np.zeros(shape, np.int32) if "neighbours" in want else None
+        status = np.zeros(shape, np.uint8) if "status" in want else None
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self.lib.lk_field_map(self._h, C.byref(cfg), ptr(rec), ptr(maps), ptr(nbrs), ptr(status)))
+        out = {k: maps[c] for c, k in enumerate(names)}
+        if nbrs is not None:
+            out["neighbours"] = nbrs
+        if status is not None:
+            out["status"] = status
+        return out
+
+    def field_last(self):
+        """Bench hook: (device ms, node tiles, tiles that walked global memory) of the last field_map call."""
+        ms, tiles, fb = C.c_float(), C.c_int(), C.c_int()
+        fn = self.lib.lk_internal_field_last
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self._chk(fn(self._h, C.byref(ms), C.byref(tiles), C.byref(fb)))
+        return ms.value, tiles.value, fb.value
+
+    @staticmethod
+    def field_from_sums(min_neighbours, n, W, sums11, tensor=_ffi.STRAIN_GREEN_LAGRANGE):
+        """lk_field_from_sums: the kernel's fit of one node on the host (no engine needed)."""
+        return _ffi.field_from_sums(min_neighbours, n, W, sums11, tensor)
+
     # ---- material-point tracks: chosen points carried through a solved sequence --------------------------
     def track_points(self, points, radius, n_frames=None, records=None, mode=_ffi.TRACK_TOTAL, source=None, state=None,
                      chi_max=0.0, min_neighbours=3, tensor=_ffi.STRAIN_GREEN_LAGRANGE):

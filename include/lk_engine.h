@@ -929,6 +929,92 @@ int lk_residual_map(lk_engine *e, const lk_residual_map_config *cfg, const lk_re
  * that is not finite and positive. */
 int lk_map_owner(int n, const float *centers_xy, const uint8_t *good, double X, double Y, double radius);
 
+/* ---- field map: dense displacement and strain maps on a regular grid of nodes ---------------- */
+/* lk_field_map gives the full-field picture a DIC user looks at first: u, v, the gradients, the strain tensor and its
+ * principal values on a regular grid of nodes - every pixel, or every stride-th - drawn in the reference image or over the
+ * deformed frame, for a colour map or for comparison with an FE result on the same grid.  Per node it is lk_track_points'
+ * windowed least-squares plane (LK_TRACK_TOTAL) around the node's position, optionally with a weight that falls to zero at
+ * the rim of the window, so that the map has no steps where a sector enters or leaves it (csrc/lk_field.hip, DESIGN.md
+ * section 22).  The call reads no image: the nodes need not lie inside any.
+ *   data      lk_strain_field's and lk_track_points': position of a sector = the engine's committed centre c; u = p[0],
+ *             v = p[1], v = 0 for LK_FM_U; the record's gradient parameters are not used.
+ *   good      the shared rule (one device function): LK_ERROR_NONE, finite parameters (the model's P), finite chi and, if
+ *             chi_max > 0, chi <= chi_max.
+ *   nodes     node (i, j), 0 <= i < nx, 0 <= j < ny, is the level-0 position (x0 + i stride, y0 + j stride): exact doubles
+ *             formed from the integers (in 64-bit arithmetic).
+ *   window    of a position (X, Y): every good sector with d2 = dx^2 + dy^2 <= r2, where dx = (double)cx - X, dy alike,
+ *             each product and the sum rounded to double (no fused multiply-add) and r2 = (double)radius squared.  n = the
+ *             number of such sectors, the members.
+ *   weight    LK_FIELD_UNIFORM: w = 1.  LK_FIELD_BISQUARE: t = 1.0 - d2 / r2, w = t t.  A member on the rim has w = 0 and
+ *             still counts in n.
+ *   sums      in the order the members are met (`order`): W += w; with wx = w x and wy = w y (x = dx, y = dy) the eleven
+ *             sums Sx += wx, Sy += wy, Sxx += wx x, Sxy += wx y, Syy += wy y, Su += w u, Sxu += wx u, Syu += wy u, Sv += w v,
+ *             Sxv += wx v, Syv += wy v, each product and each sum rounded to double.  With w = 1 these are the bits of
+ *             lk_track_points' sums added in that order.
+ *   fit       lk_field_from_sums (one function for the kernel and the host, csrc/lk_field.hpp): lk_strain_field's `fit`
+ *             formulas with n replaced by W - Cxx = Sxx - Sx Sx / W, ..., D = Cxx Cyy - Cxy Cxy, ux = (Cyy Cxu - Cxy Cyu) / D,
+ *             ..., u0 = Su / W - ux (Sx / W) - uy (Sy / W) (the plane at the position), v0 alike.  Status, checked in this
+ *             order: TOO_FEW  n < min_neighbours;  DEGENERATE  not W > 0, Cxx Cyy == 0, not Cxx > 2^-40 Sxx, not
+ *             Cyy > 2^-40 Syy, or not D > 1e-6 Cxx Cyy (lk_track_points' `degenerate` paragraph on the weighted moments);
+ *             OK.  The twelve values u0, v0, ux, uy, vx, vy - each rounded to float once - and lk_strain_from_gradient of
+ *             those four float gradients: exx, eyy, exy, e1, e2, theta.
+ *   frame     LK_FIELD_REFERENCE: one fit at the node.  The twelve values, X0 = Y0 = the node, MISFIT = 0.
+ *             LK_FIELD_DEFORMED: the node x is a position on the deformed frame, and the map shows the material point that
+ *             moved there.  X_0 = x; for k = 0 .. K - 1, K = iterations: X_{k+1} = x - (u0, v0) of the fit at X_k, in
+ *             double; there is no early exit.  The twelve values are those of the fit at X_K - Lagrangian gradients and
+ *             strain, drawn at the deformed position; X0, Y0 = (float)X_K; MISFIT = (float)hypot(ex, ey) with
+ *             ex = (X_K + u0) - x, ey alike, of that last fit: how far the point found is from moving onto the node.  If any
+ *             of the K + 1 fits is not OK, the node gets that fit's status and n and no later fit is made.
+ *   outputs   maps is [C][ny][nx] floats, C = the number of bits set in `channels`, the planes in ascending bit order;
+ *             neighbours (n of the node's last fit) and status (LK_FIELD_*) are [ny][nx], each may be NULL.  A node without
+ *             a fit has NaN in every float channel, like lk_residual_map.
+ *   order     fixed: the members of a position are met cell by cell of a grid of cell size `radius` over the centres - the
+ *             rows iy - 1, iy, iy + 1 of cells ascending, the cells ix - 1 .. ix + 1 ascending within a row, ascending
+ *             sector index within a cell (the position's cell as for lk_track_points, clamped to [-2, nx + 1]) - and summed
+ *             by one thread.  A tile of 32 x 8 nodes keeps the members of all cells its nodes reach in LDS in that same
+ *             order and every node scans them all; when they do not fit, or an iterate of the deformed frame leaves them,
+ *             the node walks its own 3 x 3 cells in global memory.  A superset of cells adds only sectors farther than a
+ *             cell = radius away, which fail the distance test.  A node's bytes therefore depend on that node, the centres,
+ *             the records and the configuration only - not on the window it is part of, the stride, the channel selection,
+ *             the tile or the path taken.  A float64 restatement reproduces them up to the order of the double sums.
+ *   modes     allowed in every mode, reference-order mode included: the call writes nothing of the engine's - records,
+ *             guesses, last parameters, counters and the other passes' outputs stay byte for byte - and, as for
+ *             lk_strain_field, a rebuild of the sample lists that waits for the next solve keeps waiting.  Synchronous.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message, outputs untouched: what lk_strain_field refuses (null configuration; no
+ *             committed sectors; records == NULL before any batch solve of the committed sectors, or with one in flight;
+ *             radius not finite or <= 0; chi_max not finite; min_neighbours < 3; unknown tensor); an unknown weight or
+ *             frame; iterations outside 1 .. 16 in the deformed frame; nx, ny or stride < 1; nx ny > 2^31 - 1; unknown
+ *             channel bits; channels == 0 with both integer maps NULL; maps == NULL with channels != 0; non-zero reserved
+ *             words.
+ *   scope     one engine; the maps are host arrays.  lk_group, lk_tracker, the report CSV and the CudaClass adapter do not
+ *             call it.  No image is read or drawn: a channel is a plain [ny][nx] float array (README: one written as CSV). */
+enum { LK_FIELD_OK = 0, LK_FIELD_TOO_FEW = 1, LK_FIELD_DEGENERATE = 2 };
+enum { LK_FIELD_UNIFORM = 0, LK_FIELD_BISQUARE = 1 };    /* weight */
+enum { LK_FIELD_REFERENCE = 0, LK_FIELD_DEFORMED = 1 };  /* frame */
+/* channel bits, in this order in the output */
+enum { LK_FIELD_U = 1 << 0, LK_FIELD_V = 1 << 1, LK_FIELD_UX = 1 << 2, LK_FIELD_UY = 1 << 3, LK_FIELD_VX = 1 << 4,
+       LK_FIELD_VY = 1 << 5, LK_FIELD_EXX = 1 << 6, LK_FIELD_EYY = 1 << 7, LK_FIELD_EXY = 1 << 8, LK_FIELD_E1 = 1 << 9,
+       LK_FIELD_E2 = 1 << 10, LK_FIELD_THETA = 1 << 11, LK_FIELD_X0 = 1 << 12, LK_FIELD_Y0 = 1 << 13,
+       LK_FIELD_MISFIT = 1 << 14, LK_FIELD_ALL = (1 << 15) - 1 };
+typedef struct lk_field_map_config {
+  float radius, chi_max;        /* as lk_strain_config */
+  int min_neighbours, tensor;
+  int weight;                   /* LK_FIELD_UNIFORM / LK_FIELD_BISQUARE */
+  int frame;                    /* LK_FIELD_REFERENCE / LK_FIELD_DEFORMED */
+  int iterations;               /* K, 1 .. 16; read in the deformed frame only */
+  int x0, y0, nx, ny, stride;   /* nodes (x0 + i stride, y0 + j stride), level-0 pixels; nx, ny, stride >= 1 */
+  uint32_t channels;            /* LK_FIELD_U | ... : the planes of `maps` */
+  int reserved[3];              /* must be 0 */
+} lk_field_map_config;
+/* records: host [S], or NULL = the engine-held records of the last finished batch solve.  maps: host [C][ny][nx] (NULL only
+ * with channels == 0); neighbours, status: host [ny][nx] or NULL.  Synchronous.  Changes no engine state. */
+int lk_field_map(lk_engine *e, const lk_field_map_config *cfg, const lk_result *records, float *maps, int32_t *neighbours,
+                 uint8_t *status);
+/* the kernel's own fit compiled for the host (csrc/lk_field.hpp): n, W and the eleven sums of the `sums` paragraph ->
+ * *status and the twelve floats {u, v, ux, uy, vx, vy, exx, eyy, exy, e1, e2, theta} (all NaN unless *status is LK_FIELD_OK).
+ * LK_ERROR_BAD_DOMAIN for a null pointer, n < 0, min_neighbours < 3 or an unknown tensor. */
+int lk_field_from_sums(int min_neighbours, int n, double W, const double *sums11, int tensor, float *out12, int32_t *status);
+
 /* ---- speckle quality: is the pattern good enough, and how large must the subsets be ---------------- */
 /* Every pass above judges a field after the solve.  These two answer what a user asks before the first one, from one image
  * alone: lk_pattern_quality gives every committed sector the classical figures of its speckle pattern - the sum of squared

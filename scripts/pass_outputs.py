@@ -140,6 +140,22 @@ def run_map():
     return out
 
 
+def run_field():
+    import correlation_amd as ca
+    e, rec = solved("grid", ca.FM_UVUXUYVXVY, ca.IM_BICUBIC)
+    out = {}
+    window = (-40, -37, 333, 331)   # ragged tiles, two radii beyond the grid
+    for name, kw in (("uniform", dict()), ("bisquare", dict(weight=ca.FIELD_BISQUARE)),
+                     ("deformed", dict(weight=ca.FIELD_BISQUARE, frame=ca.FIELD_DEFORMED, iterations=4)),
+                     ("stride", dict(stride=3)), ("too_few", dict(radius=TINY_RADIUS)), ("wide", dict(radius=WIDE_RADIUS))):
+        kw.setdefault("radius", RADIUS)
+        got = e.field_map(kw.pop("radius"), window, channels=ca.FIELD_ALL, records=rec, **kw)
+        _, tiles, fallback = e.field_last()
+        assert fallback == (tiles if os.environ.get("LK_FIELD_WALK") == "1" else 0), (name, tiles, fallback)
+        out.update({"field_%s.%s" % (name, k): v for k, v in got.items()})
+    return out
+
+
 def run_evaluate():
     import correlation_amd as ca
     out = {}
@@ -199,6 +215,7 @@ VARIANTS = [("strain_g%d_packed%d" % (g, p), {"LK_STRAIN_GROUP": str(g), "LK_STR
 VARIANTS += [("outlier_g%d_cap%s" % (g, cap), {"LK_OUTLIER_GROUP": str(g), "LK_OUTLIER_LDS_CAP": cap}, run_outlier)
              for g in (16, 64) for cap in ("0", "100000")]
 VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (16, 64)]
+VARIANTS += [("field_walk%d" % w, {"LK_FIELD_WALK": str(w)}, run_field) for w in (0, 1)]
 VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
              ("pattern", {}, run_pattern)]
 
