@@ -162,6 +162,24 @@ PHOTOMETRY_DTYPE = np.dtype([("n_points", np.int32), ("status", np.int32)] +
                             [("reserved", np.int32, (3,))])
 assert PHOTOMETRY_DTYPE.itemsize == 64 and C.sizeof(LkPhotometryConfig) == 16 and C.sizeof(LkResidualMapConfig) == 32
 
+# ZNSSD refinement (include/lk_engine.h: lk_refine_znssd)
+(ZN_CONVERGED, ZN_MAX_ITERS, ZN_STALLED, ZN_BAD_SEED, ZN_OUT_OF_IMAGE, ZN_TOO_FEW, ZN_FLAT, ZN_NEGATIVE,
+ ZN_SINGULAR) = range(9)
+ZN_SUMS = 45   # doubles per sector: Sf, Sg, Sff, Sgg, Sfg, SH[P], SHH[P (P + 1) / 2], SHf[P], SHg[P], flagged samples, zeros
+
+
+class LkZnssdConfig(C.Structure):
+    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float),
+                ("lambda0", C.c_float), ("reserved", C.c_int * 3)]
+
+
+# struct lk_znssd as a numpy record
+ZNSSD_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "iterations", "evaluations")] +
+                       [(k, np.float32) for k in ("zncc", "gain", "offset", "znssd", "zncc_seed", "shift", "lambda",
+                                                  "last_step")] +
+                       [("reserved", np.int32, (4,))])
+assert ZNSSD_DTYPE.itemsize == 64 and C.sizeof(LkZnssdConfig) == 32
+
 # speckle quality (include/lk_engine.h: lk_pattern_quality, lk_suggest_subset)
 PATTERN_OK, PATTERN_TOO_FEW, PATTERN_FLAT, PATTERN_APERTURE, PATTERN_SATURATED = range(5)
 SUBSET_OK, SUBSET_NONE, SUBSET_BAD_POINT = range(3)
@@ -297,6 +315,8 @@ SYMBOLS = {
     "lk_photometry_from_sums": (C.c_int, [C.c_int, _P, _P]),
     "lk_residual_map": (C.c_int, [_P, C.POINTER(LkResidualMapConfig), _P, _P, _P, _P]),
     "lk_map_owner": (C.c_int, [C.c_int, _F, _P, C.c_double, C.c_double, C.c_double]),
+    "lk_refine_znssd": (C.c_int, [_P, C.POINTER(LkZnssdConfig), _P, _F, _P, _P, _P]),
+    "lk_znssd_step_from_sums": (C.c_int, [C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "lk_field_map": (C.c_int, [_P, C.POINTER(LkFieldMapConfig), _P, _P, _P, _P]),
     "lk_field_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_double, _P, C.c_int, _F, _I]),
     "lk_pattern_quality": (C.c_int, [_P, C.POINTER(LkPatternConfig), _P, _P, _P]),
@@ -486,6 +506,22 @@ def photometry_from_sums(n, sums8):
     if _compose_lib.lk_photometry_from_sums(int(n), s.ctypes.data_as(_P), out.ctypes.data_as(_P)) != 0:
         raise ValueError("lk_photometry_from_sums: n < 0")
     return out[0]
+
+
+def znssd_step_from_sums(model, n, sums, lam):
+    """lk_znssd_step_from_sums (host, the kernel's function): (status, delta [6], crit, gain, offset) of one sector of n
+    samples whose sums, in the model's layout, are `sums` (ZN_SUMS doubles or fewer), at the damping `lam`."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.zeros(ZN_SUMS, np.float64)
+    flat = np.asarray(sums, np.float64).reshape(-1)
+    s[:len(flat)] = flat
+    delta, crit, go, status = np.zeros(6, np.float64), C.c_double(), np.zeros(2, np.float64), C.c_int32(-1)
+    if _compose_lib.lk_znssd_step_from_sums(int(model), int(n), s.ctypes.data_as(_P), float(lam), delta.ctypes.data_as(_P),
+                                            C.byref(crit), go.ctypes.data_as(_P), C.byref(status)) != 0:
+        raise ValueError(f"lk_znssd_step_from_sums: bad model {model}, n < 0 or a bad lambda")
+    return status.value, delta, crit.value, float(go[0]), float(go[1])
 
 
 def pattern_from_sums(n, sums9, mig_sum, noise_sigma=1.0, max_saturated=1.0):

@@ -358,6 +358,19 @@ struct LkPhotometryArgs {
   float chi_max;
 };
 
+// ZNSSD refinement (lk_znssd.hip, include/lk_engine.h: lk_refine_znssd): the same walk inside a Levenberg-Marquardt loop
+// per lane group, from records (ev.rec) or from guesses.
+struct LkZnssdArgs {
+  LkSectorEvalArgs ev;      // ev.rec: [S] the seed records, read when guess is null
+  const float *guess;       // [S][6] level-0 seeds or null
+  const int32_t *count0;    // [S] level-0 sample counts (the records' numberOfPoints)
+  lk_result *rec_out;       // [S]
+  struct lk_znssd *out;     // [S]
+  double *sums;             // [S][45] or null (lk_znssd.hpp: kLkZnSums)
+  int n_sectors, level, max_iters;
+  float chi_max, precision, lambda0;
+};
+
 // Residual map (lk_residual.hip, include/lk_engine.h: lk_residual_map): what a pixel needs of a sector, 48 bytes.
 struct LkMapSector {
   float cx0, cy0; // level-0 centre; cx0 = NaN for a sector that is not good (it then fails the distance test by itself)

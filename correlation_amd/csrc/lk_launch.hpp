@@ -125,6 +125,11 @@ hipError_t lk_launch_map_prep(const lk_result *rec, const float2 *center, int n_
 // one workgroup per tile of kLkMapTileW x kLkMapTileH pixels of the window; *n_tiles = the tiles launched
 hipError_t lk_launch_residual_map(const LkResidualMapArgs &a, int model, int interp, int *n_tiles, hipStream_t st);
 
+// ---- lk_znssd.hip: the ZNSSD refinement (lk_refine_znssd)
+// group: 16, 64 or 512 lanes per sector (lk_bw_group of the level-0 sample count); a.ev.order lists that group's sectors.
+// One launch carries every sector of the group from its seed to its final record.
+hipError_t lk_launch_znssd(const LkZnssdArgs &a, int model, int interp, int group, hipStream_t st);
+
 // ---- lk_pattern.hip: speckle quality (lk_pattern_quality, lk_suggest_subset)
 // group: 16, 64 or 512 lanes per sector (lk_bw_group of the level-0 sample count); a.ev.order lists that group's sectors
 hipError_t lk_launch_pattern(const LkPatternArgs &a, int group, hipStream_t st);

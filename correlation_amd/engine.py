@@ -486,6 +486,42 @@ class HipCorrelationEngine:
         """lk_map_owner: the residual map's owner rule on the host (no engine needed)."""
         return _ffi.map_owner(centers, X, Y, radius, good)
 
+    # ---- ZNSSD refinement: the sub-pixel solve that does not mind the lighting ----------------------------
+    def refine_znssd(self, records=None, guesses=None, def_slot=-1, chi_max=0.0, max_iters=-1, precision=0.0, lambda0=0.0,
+                     return_sums=False):
+        """lk_refine_znssd: every sector refined by Levenberg-Marquardt on the zero-mean normalised criterion at pyramid
+        level py_start, from `guesses` [S][6] (level-0 scale, as search_guesses returns them) or from records - those
+        given [S], else the engine-held ones of the last batch solve.  max_iters < 0 and precision <= 0: the engine's own.
+        Returns (records RESULT_DTYPE [S], info ZNSSD_DTYPE [S]) and, with return_sums, the 45 double sums of every sector
+        at the returned parameters [S][45].  No engine state changes."""
+        cfg = _ffi.LkZnssdConfig(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
+                                 float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0))
+        rec = g = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        if guesses is not None:
+            g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
+        out = np.zeros(self.n_sectors, RESULT_DTYPE)
+        info = np.zeros(self.n_sectors, _ffi.ZNSSD_DTYPE)
+        sums = np.zeros((self.n_sectors, _ffi.ZN_SUMS), np.float64) if return_sums else None
+        self._chk(self.lib.lk_refine_znssd(self._h, C.byref(cfg), rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
+                                           _ffi.fptr(g) if g is not None else None, out.ctypes.data_as(C.c_void_p),
+                                           info.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p) if return_sums else None))
+        return (out, info, sums) if return_sums else (out, info)
+
+    def znssd_last(self):
+        """Bench hook: (device ms, the sectors the 16-, 64- and 512-lane groups took) of the last refine_znssd call."""
+        ms, cnt = C.c_float(), (C.c_int * 3)()
+        fn = self.lib.lk_internal_znssd_last
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        self._chk(fn(self._h, C.byref(ms), cnt))
+        return ms.value, tuple(cnt)
+
+    @staticmethod
+    def znssd_step_from_sums(model, n, sums, lam):
+        """lk_znssd_step_from_sums: the kernel's criterion and step on the host (no engine needed)."""
+        return _ffi.znssd_step_from_sums(model, n, sums, lam)
+
     # ---- speckle quality: is the pattern good enough, how large must the subsets be ----------------------
     def pattern_quality(self, slot=_ffi.IMG_UND, grey_low=0, grey_high=255, noise_sigma=1.0, max_saturated=1.0,
                         return_sums=False):

@@ -929,6 +929,113 @@ int lk_residual_map(lk_engine *e, const lk_residual_map_config *cfg, const lk_re
  * that is not finite and positive. */
 int lk_map_owner(int n, const float *centers_xy, const uint8_t *good, double X, double Y, double radius);
 
+/* ---- ZNSSD refinement: a sub-pixel solve that does not mind the lighting ------------------- */
+/* lk_photometry shows that a high chi comes from lighting; lk_refine_znssd repairs the match.  It takes records or guesses
+ * as seeds and refines every sector by Levenberg-Marquardt on the zero-mean normalised sum of squared differences, with
+ * gain and offset eliminated in closed form, in a kernel of its own (csrc/lk_znssd.hip).  Refined
+ * records come out; the user hands them to lk_strain_field, lk_field_map, lk_flag_outliers and the rest through their
+ * `records` argument.  With guesses from lk_search_guesses - which scores by ZNCC - the pair is a lighting-robust pipeline
+ * in which no batch solve runs.
+ *   level     L = py_start, as the other evaluation passes: the seed goes to level L by the solve's parameter translation
+ *             and the result comes back the same way; the committed centre times 2^-L.
+ *   seeds     guesses == NULL: `records` [S] on the host or, records == NULL, the engine-held records of the last finished
+ *             batch solve.  A record that fails the shared good rule (chi_max as for lk_photometry) is LK_ZN_BAD_SEED: its 48
+ *             bytes are copied to records_out and nothing is evaluated.  guesses != NULL (records must be NULL): host
+ *             [S][6] in level-0 scale, the shape lk_search_guesses and lk_get_guesses return; every sector whose first P
+ *             guesses are finite is refined, any other is LK_ZN_BAD_SEED with errorCode LK_ERROR_BAD_DOMAIN and the guess
+ *             as its parameters.
+ *   sample    lk_parameter_uncertainty's walk and lane groups (16 / 64 / 512 lanes from the level-0 sample count; lane j
+ *             takes the samples j, j + G, ...).  Per sample, in float, the solve's device functions: f = the undeformed
+ *             node, g, g_x, g_y = the deformed image and its gradient at W(x; p), H = dg/dp.
+ *   sums      45 doubles for six parameters (kLkZnSums; a smaller model's come first, zeros behind): Sf, Sg, Sff, Sgg, Sfg,
+ *             SH[P], SHH[P (P + 1) / 2] upper triangle row-major, SHf[P], SHg[P], then the samples the sampler flagged.
+ *             Every product is formed in double from the floats without fused multiply-add; the sums are added by the
+ *             uncertainty pass's fixed butterfly.  A sector's sums, and therefore its whole trajectory, record and info,
+ *             are the same bytes in any batch, shard, mode or ring slot.
+ *   step      lk_znssd_step_from_sums (one function for the kernel and the host, csrc/lk_znssd.hpp), in double without
+ *             fused multiply-add; with N = (double)n:
+ *               vf = N Sff - Sf Sf, vg = N Sgg - Sg Sg, c = N Sfg - Sf Sg;
+ *               LK_ZN_TOO_FEW if n < P + 2;  LK_ZN_FLAT by photometry's rule, vx <= 1e-12 N Sxx for x = f or g;
+ *               gain = c / vg, offset = (Sf - gain Sg) / N (least squares f ~ gain g + offset), zncc = c / sqrt(vf vg),
+ *               crit = max(0, 1 - c c / (vf vg)) = the smallest sum (f - gain g - offset)^2 over sum (f - mean f)^2;
+ *               LK_ZN_NEGATIVE if c <= 0 (the four numbers above are filled);
+ *               A_kl = gain^2 (SHH_kl - SH_k SH_l / N) / N,  b_k = gain ((SHf_k - SH_k Sf / N) - gain (SHg_k - SH_k Sg / N)) / N,
+ *               diag(A) times (1 + lambda), A delta = b: the Gauss-Newton step of the criterion.  A is scaled to a diagonal
+ *               of 1 + lambda and factored as L D L^T without pivoting, the uncertainty pass's factorisation and
+ *               scale-free pivot rule: A_kk <= 0 or a pivot <= 1e-10 is LK_ZN_SINGULAR.
+ *   loop      in the kernel, one launch per lane group.  Evaluate at the seed: a flagged sample is LK_ZN_OUT_OF_IMAGE, a
+ *             refusal of the step function is the status; neither is iterated.  lambda = lambda0.  Then trips, up to
+ *             max_iters: delta from the kept sums; LK_ZN_SINGULAR: lambda *= 10 without an evaluation; else evaluate at
+ *             (float)((double)p + delta) and accept when no sample is flagged, the criterion is not refused and crit' <
+ *             crit strictly - then p and the sums are replaced and lambda = max(0.1 lambda, 1e-9) - else lambda *= 10.
+ *             lambda >= 1e9: LK_ZN_STALLED.  An accepted step with max_k w_k |delta_k| < precision: LK_ZN_CONVERGED, with
+ *             w = 1 for the translations (level-L pixels) and w = max(1, sqrt(n_L) / 2) for every other parameter - the
+ *             half-width of a square subset, so the test bounds how far any sample moved.  A step that small whose
+ *             evaluation is neither flagged nor refused but does not lower crit is LK_ZN_CONVERGED too, p and lambda
+ *             unchanged: the float sample positions leave a noise of a few 1e-5 of crit, below which a step of less than
+ *             the precision cannot be told from none, and without this rule such a sector would climb to STALLED.  No
+ *             trips left:
+ *             LK_ZN_MAX_ITERS (also after max_iters = 0, which evaluates the seed only).  The returned state is always the
+ *             best accepted one.
+ *   records   records_out [S]: the refined parameters in level-0 scale (zeros behind P), the committed centre, the level-0
+ *             count, iterations = the trips taken, chi = (Sff - 2 Sfg + Sgg) / n_L of the kept sums in double - the mean
+ *             squared difference that lk_evaluate's chi, scaled by 1 / n as the solve scales it, gives at the returned
+ *             parameters up to its float summation - so chi_max keeps its meaning downstream (0 for LK_ZN_OUT_OF_IMAGE).
+ *             errorCode: CONVERGED -> LK_ERROR_NONE; MAX_ITERS, STALLED -> LK_ERROR_CORRELATION_MAX_ITERS_REACHED;
+ *             OUT_OF_IMAGE -> LK_ERROR_INTERPOLATION_OUT_OF_IMAGE; TOO_FEW, FLAT, NEGATIVE, SINGULAR -> LK_ERROR_SOLVER.
+ *   info      n_points = n_L; evaluations = the passes over the samples; zncc, gain, offset and znssd (= crit) at the
+ *             returned parameters, each a double rounded to float once; zncc_seed at the seed; shift = |(u, v) returned -
+ *             (u, v) seed| in level-0 pixels; lambda = the final damping; last_step = max_k w_k |delta_k| of the last
+ *             accepted step.  BAD_SEED and OUT_OF_IMAGE: floats and sums 0.  FLAT and TOO_FEW: the seed's sums, floats 0.
+ *   modes     allowed in every mode, reference-order mode included; synchronous; writes nothing of the engine's; carries
+ *             out a rebuild of the sample lists that waits for the next solve first, as lk_parameter_uncertainty does.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message, outputs untouched: null configuration; records_out and info_out both
+ *             NULL (either alone may be); non-zero reserved words; records and guesses both given; chi_max, precision or
+ *             lambda0 not finite; and what lk_parameter_uncertainty refuses (its accessor is used, its messages carry this
+ *             function's name): no committed sectors; records == guesses == NULL before any batch solve of the committed
+ *             sectors, or with one in flight; images not set; a bad def_slot.
+ *   defaults  max_iters < 0 is 50 and precision <= 0 is 1e-3, lk_config's defaults: the pass reads the engine through the
+ *             accessor of the add-on passes, which does not carry the engine's configuration.  The Python method passes
+ *             the engine's own values.  lambda0 <= 0 is 1e-3.
+ *   scope     one engine, level py_start only - no coarser levels, so the seed must lie within the sampler's reach of the
+ *             answer (a pixel or two; lk_search_guesses brings it there); the engine-held records are never written;
+ *             lk_group, lk_tracker, the report CSV and the CudaClass adapter do not call it; windows with
+ *             reference_previous are not covered; inputs and outputs are host arrays; no colour frames; lk_solve_kernel
+ *             and lk_backward_kernel keep the plain sum of squares. */
+enum { LK_ZN_CONVERGED = 0, LK_ZN_MAX_ITERS = 1, LK_ZN_STALLED = 2,   /* lambda reached 1e9 */
+       LK_ZN_BAD_SEED = 3, LK_ZN_OUT_OF_IMAGE = 4, LK_ZN_TOO_FEW = 5, LK_ZN_FLAT = 6,
+       LK_ZN_NEGATIVE = 7,  /* c <= 0 at the seed: anti-correlated patches */
+       LK_ZN_SINGULAR = 8 };
+typedef struct lk_znssd_config {
+  int def_slot;       /* as lk_photometry_config */
+  float chi_max;      /* good rule for record seeds; <= 0: error code alone */
+  int max_iters;      /* LM trips; 0: evaluate the seed only; < 0: 50 */
+  float precision;    /* <= 0: 1e-3 */
+  float lambda0;      /* <= 0: 1e-3 */
+  int reserved[3];    /* must be 0 */
+} lk_znssd_config;
+/* (a struct tag without a typedef, as struct lk_photometry) */
+struct lk_znssd {     /* 64 bytes, one per sector */
+  int32_t n_points, status, iterations, evaluations;
+  float zncc, gain, offset, znssd;     /* at the returned parameters; f ~ gain g + offset */
+  float zncc_seed;                     /* at the seed */
+  float shift;                         /* |(u, v) returned - (u, v) seed|, level-0 pixels */
+  float lambda, last_step;             /* final damping; max weighted |delta| of the last accepted step */
+  int32_t reserved[4];
+};
+/* records: host [S], or NULL = the engine-held records (guesses == NULL), or guesses: host [S][6].  records_out: [S],
+ * info_out: [S], either may be NULL, not both.  sums_out: [S][45] doubles or NULL, the kept sums at the returned parameters.
+ * Synchronous.  Changes no engine state. */
+int lk_refine_znssd(lk_engine *e, const lk_znssd_config *cfg, const lk_result *records, const float *guesses,
+                    lk_result *records_out, struct lk_znssd *info_out, double *sums_out);
+/* the kernel's own function compiled for the host: criterion and damped step of one sector of n samples with the sums `sums`
+ * (the model's layout, 45 doubles or fewer).  *status = 0, or LK_ZN_TOO_FEW, LK_ZN_FLAT, LK_ZN_NEGATIVE or LK_ZN_SINGULAR;
+ * delta6 (zeros behind P, and all zeros unless *status = 0), crit and gain_offset2 may each be NULL.  LK_ERROR_BAD_DOMAIN
+ * (outputs untouched) for a null sums or status pointer, an unknown model, n < 0 or a lambda that is negative or not
+ * finite. */
+int lk_znssd_step_from_sums(int model, int n, const double *sums, float lambda, double *delta6, double *crit,
+                            double *gain_offset2, int32_t *status);
+
 /* ---- field map: dense displacement and strain maps on a regular grid of nodes ---------------- */
 /* lk_field_map gives the full-field picture a DIC user looks at first: u, v, the gradients, the strain tensor and its
  * principal values on a regular grid of nodes - every pixel, or every stride-th - drawn in the reference image or over the
