@@ -49,6 +49,7 @@
 
 #include <atomic>
 
+#include "lk_rect_walk.hpp"
 #include "lk_solver_common.hpp"
 
 namespace {
@@ -65,7 +66,6 @@ struct LevelCtx { // what a lane needs to know about its sector at the current l
   int n;
   int urows, ucols, drows, dcols;
   float cx, cy, scaling;
-  float inv_w; // 1 / rw (implicit rectangles: sample index -> row), once per level instead of once per evaluation
 };
 
 // sum inside each 16-lane row: every lane of the row ends with the same bits
@@ -173,7 +173,25 @@ __device__ __forceinline__ bool team_all_to_all(SumsT &S, bool any_bad, float *l
   return any_bad;
 }
 
-template <int MODEL, int INTERP, int GROUP, int THREADS, bool SCATTER = false>
+// The instances that keep the closed form of the implicit rectangle's index rule (WALK = false in evaluate<>): with the
+// walk they would need one more block of eight VGPRs or more scratch than without ("the head of a trip").
+// The six-parameter separable bicubic in 256-lane groups (130 -> 137 VGPRs) and in the 16-lane sequence kernel, which is
+// held at 128 registers (28 -> 36 bytes of scratch); of the stand-alone evaluation kernels four (40 -> 42, 48 -> 50 twice,
+// 79 -> 81 VGPRs).  The lists are ROCm 7.2's register allocation and nothing derives them: after a toolchain change build
+// with `return GROUP > 1;` in both, compare scripts/resource_usage.py of `build.py --force -v` logs with the build before the
+// walk, and list what grew.  These instances form 1 / rw once per evaluation, not once per level as before.
+template <int MODEL, int INTERP, int GROUP, bool SAFE, bool REF, bool SEQ> constexpr bool solve_walks_rects() {
+  if (MODEL == LK_FM_UVUXUYVXVY && INTERP == LK_IM_BICUBIC_SEPARABLE && !SAFE && !REF && ((GROUP == 256 && !SEQ) || (GROUP == 16 && SEQ)))
+    return false;
+  return GROUP > 1;
+}
+template <int MODEL, int INTERP, int GROUP> constexpr bool eval_walks_rects() {
+  return GROUP > 1 && !(MODEL == LK_FM_UV && INTERP == LK_IM_BICUBIC && GROUP == 64) &&
+         !(MODEL == LK_FM_UVQ && INTERP == LK_IM_BICUBIC && (GROUP == 32 || GROUP == 64)) &&
+         !(MODEL == LK_FM_UVUXUYVXVY && INTERP == LK_IM_BICUBIC_SEPARABLE && GROUP == 32);
+}
+
+template <int MODEL, int INTERP, int GROUP, int THREADS, bool SCATTER = false, bool WALK = (GROUP > 1)>
 __device__ __forceinline__ bool evaluate(const LevelCtx &c, const float (&p)[6],
                                          Sums<n_params(MODEL)> &S, float *lds, TeamCtx *team = nullptr,
                                          bool wide = false, bool ordered = false, int width = 0) {
@@ -279,8 +297,16 @@ __device__ __forceinline__ bool evaluate(const LevelCtx &c, const float (&p)[6],
   // lane walks the samples in the REFERENCE's order and accumulates with a separate
   // multiply and add, exactly like interpolation_class.cpp:722-749, so A, b and chi are
   // bit-identical to the reference's.
-  // (16-lane rows divide here: one more live register per row would cost that kernel its fourth wavefront per SIMD)
-  const float inv_w = GROUP == 16 ? (c.rw > 0 ? 1.f / (float)c.rw : 0.f) : c.inv_w;
+  // The lane groups do not divide k by the width every trip: (row, col) of the lane's first sample once per evaluation
+  // (lane0 and stride change with `wide`, `width` and the team), then the constant step with one carry (lk_rect_walk.hpp).
+  // (WALK = false: the instances that have no register for it divide, by the reciprocal and a correction, every trip)
+  static_assert(!WALK || GROUP > 1, "one lane per sector walks in the reference's order");
+  RectWalk walk{};
+  float inv_w = 0.f;
+  if constexpr (WALK)
+    walk = RectWalk::start(c.rw, lane0, stride);
+  else if constexpr (GROUP > 1)
+    inv_w = c.rw > 0 ? 1.f / (float)c.rw : 0.f;
   const int rh = (GROUP == 1 && c.rw > 0) ? c.n / c.rw : 1; // height of the implicit rectangle
 #ifndef LK_PIPE_MIN_GROUP // lane groups at least this wide prefetch the next sample (tuning hook)
 #define LK_PIPE_MIN_GROUP 256
@@ -353,12 +379,18 @@ __device__ __forceinline__ bool evaluate(const LevelCtx &c, const float (&p)[6],
       cur = nxt;
     }
   } else
-  for (int k = lane0; k < c.n; k += stride) {
+  for (int k = lane0; k < c.n; k += stride, WALK ? walk.step(c.rw) : void()) {
     f32x2 q;
+    int uix, uiy; // the undeformed pixel of the sample
     if (GROUP == 1 && c.rw > 0) { // reference order: x outer, y inner
       const int col = k / rh;
       q.x = (float)(c.rx + col);
       q.y = (float)(c.ry + (k - col * rh));
+      uix = (int)(q.x + 0.5f), uiy = (int)(q.y + 0.5f);
+    } else if (WALK && c.rw > 0) { // (row, column) of sample k in the rectangle: the integers are the pixel
+      uix = c.rx + walk.col, uiy = c.ry + walk.row;
+      q.x = (float)uix;
+      q.y = (float)uiy;
     } else if (c.rw > 0) { // k -> (row, column) of the rectangle
       int row = (int)((float)k * inv_w);
       int col = k - row * c.rw;
@@ -371,12 +403,13 @@ __device__ __forceinline__ bool evaluate(const LevelCtx &c, const float (&p)[6],
       }
       q.x = (float)(c.rx + col);
       q.y = (float)(c.ry + row);
+      uix = (int)(q.x + 0.5f), uiy = (int)(q.y + 0.5f);
     } else {
       q = c.xy[k];
+      uix = (int)(q.x + 0.5f), uiy = (int)(q.y + 0.5f);
     }
     float xd, yd, dx = 0.f, dy = 0.f;
     Warp<MODEL>::apply(q.x, q.y, c.cx, c.cy, p, xd, yd, dx, dy);
-    int uix = (int)(q.x + 0.5f), uiy = (int)(q.y + 0.5f);
     uix = min(max(uix, 0), umaxc); // memory safety only; valid sample lists never clamp
     uiy = min(max(uiy, 0), umaxr);
     float und_w = (float)c.und[(size_t)uiy * (size_t)c.ucols + (size_t)uix];
@@ -1377,8 +1410,6 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
     c.drows = lv.drows;
     c.dcols = lv.dcols;
     c.scaling = 1.f / ((float)c.n);
-    if constexpr (GROUP != 16)
-      c.inv_w = c.rw > 0 ? 1.f / (float)c.rw : 0.f;
     const float inv = 1.f / (float)(1 << k.level); // pyramid_class.cpp:357-361
     c.cx = k.level == 0 ? k.c0x : k.c0x * inv;
     c.cy = k.level == 0 ? k.c0y : k.c0y * inv;
@@ -1756,7 +1787,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
             take(p[i]);
           take(c.rx), take(c.ry), take(c.rw), take(c.n);
           take(c.urows), take(c.ucols), take(c.drows), take(c.dcols);
-          take(c.scaling), take(c.cx), take(c.cy), take(c.inv_w);
+          take(c.scaling), take(c.cx), take(c.cy);
           auto take_ptr = [&](auto &ptr) {
             unsigned long long bits = (unsigned long long)(uintptr_t)ptr;
             uint32_t lo32 = (uint32_t)bits, hi32 = (uint32_t)(bits >> 32);
@@ -1804,7 +1835,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
             take(p[i]);
           take(c.rx), take(c.ry), take(c.rw), take(c.n);
           take(c.urows), take(c.ucols), take(c.drows), take(c.dcols);
-          take(c.scaling), take(c.cx), take(c.cy); // (c.inv_w: not used by 16-lane groups)
+          take(c.scaling), take(c.cx), take(c.cy);
           auto take_ptr = [&](auto &ptr) {
             unsigned long long bits = (unsigned long long)(uintptr_t)ptr;
             uint32_t lo32 = (uint32_t)bits, hi32 = (uint32_t)(bits >> 32);
@@ -1874,7 +1905,8 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
       err = a.reference_order > 1 ? evaluate_ordered<MODEL, INTERP, GROUP, true>(ce, p, S, ord_lds, a.reference_order)
                                   : evaluate_ordered<MODEL, INTERP, GROUP, false>(ce, p, S, ord_lds, 1);
     } else {
-      err = evaluate<MODEL, INTERP, GROUP, THREADS, SCATTER>(ce, p, S, lds, &team, wide, row_ordered, GROUP == 16 ? width : 0);
+      err = evaluate<MODEL, INTERP, GROUP, THREADS, SCATTER, solve_walks_rects<MODEL, INTERP, GROUP, SAFE, REF, SEQ>()>(
+          ce, p, S, lds, &team, wide, row_ordered, GROUP == 16 ? width : 0);
     }
 #ifdef LK_TRACE
     tr_eval += __builtin_amdgcn_s_memtime() - tr_e0;
@@ -2276,7 +2308,6 @@ __global__ void __launch_bounds__(256) lk_eval_kernel(LkEvalArgs a) {
   c.dcols = lv.dcols;
   c.cx = a.level == 0 ? c0.x : c0.x * inv;
   c.cy = a.level == 0 ? c0.y : c0.y * inv;
-  c.inv_w = c.rw > 0 ? 1.f / (float)c.rw : 0.f;
   float p[6];
 #pragma unroll
   for (int i = 0; i < 6; ++i)
@@ -2294,7 +2325,7 @@ __global__ void __launch_bounds__(256) lk_eval_kernel(LkEvalArgs a) {
                               : evaluate_ordered<MODEL, INTERP, OG, false>(c, p, S, ord_lds, 1);
     }
   } else {
-    err = evaluate<MODEL, INTERP, GROUP, 256>(c, p, S, lds);
+    err = evaluate<MODEL, INTERP, GROUP, 256, false, eval_walks_rects<MODEL, INTERP, GROUP>()>(c, p, S, lds);
   }
   if (threadIdx.x == 0) {
     for (int i = 0; i < 44; ++i)
