@@ -9,13 +9,14 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblk_engine.so")
-SOURCES = ["lk_engine.cpp", "lk_tracker.cpp", "lk_group.cpp", "lk_image_io.cpp", "lk_kernels.hip", "lk_guess_search.cpp",
+SOURCES = ["lk_engine.cpp", "lk_engine_images.cpp", "lk_engine_sectors.cpp", "lk_engine_moves.cpp", "lk_engine_solve.cpp",
+           "lk_engine_sequence.cpp", "lk_tracker.cpp", "lk_group.cpp", "lk_image_io.cpp", "lk_kernels.hip", "lk_guess_search.cpp",
            "lk_guess_search.hip", "lk_backward.hip", "lk_reseed.cpp", "lk_reseed.hip",
            "lk_strain.cpp", "lk_strain.hip", "lk_uncertainty.cpp", "lk_uncertainty.hip",
            "lk_outlier.cpp", "lk_outlier.hip", "lk_track.cpp", "lk_track.hip",
            "lk_residual.cpp", "lk_residual.hip", "lk_pattern.cpp", "lk_pattern.hip",
            "lk_field.cpp", "lk_field.hip", "lk_znssd.cpp", "lk_znssd.hip"]
-HEADERS = ["lk_device.hpp", "lk_roi.hpp", "lk_solver_common.hpp", "lk_compose.hpp", "lk_launch.hpp", "lk_neighbours.hpp", "lk_rect_walk.hpp", "lk_sector_eval.hpp", "lk_cell_grid.hpp", "lk_pass.hpp", "lk_strain.hpp", "lk_uncertainty.hpp", "lk_outlier.hpp", "lk_track.hpp", "lk_residual.hpp", "lk_pattern.hpp", "lk_field.hpp", "lk_znssd.hpp", os.path.join("..", "..", "include", "lk_engine.h"),
+HEADERS = ["lk_engine_state.hpp", "lk_device.hpp", "lk_roi.hpp", "lk_solver_common.hpp", "lk_compose.hpp", "lk_launch.hpp", "lk_neighbours.hpp", "lk_rect_walk.hpp", "lk_sector_eval.hpp", "lk_cell_grid.hpp", "lk_pass.hpp", "lk_strain.hpp", "lk_uncertainty.hpp", "lk_outlier.hpp", "lk_track.hpp", "lk_residual.hpp", "lk_pattern.hpp", "lk_field.hpp", "lk_znssd.hpp", os.path.join("..", "..", "include", "lk_engine.h"),
            os.path.join("..", "..", "include", "lk_tracker.h"), os.path.join("..", "..", "include", "lk_group.h")]
 
 
@@ -78,7 +79,7 @@ def build(force=False, verbose=False):
     with open(tag, "w") as f:
         f.write(" ".join(flags))
     link = [hipcc_path(), "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB] + [o for o, _ in results] + [
-        "-lrocprofiler-sdk-roctx",   # roctx ranges (lk_engine.cpp: struct Range)
+        "-lrocprofiler-sdk-roctx",   # roctx ranges (lk_engine_state.hpp: struct Range)
         "-lrccl",                    # lk_group.cpp: ncclBroadcast / ncclAllGather over xGMI
         "-lz",                       # lk_image_io.cpp: inflate + crc32 for PNG
     ]

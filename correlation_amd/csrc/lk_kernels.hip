@@ -1245,7 +1245,7 @@ __global__ void __launch_bounds__(THREADS, (THREADS == 64 ? (GROUP == 16 && !SAF
   static_assert(!REF || (SAFE && ((THREADS == kWave && (GROUP == 16 || GROUP == kWave)) || (THREADS == 512 && GROUP == 512))), "reference-order instances");
   static_assert(!SEQ || (THREADS == kWave && GROUP >= 16 && GROUP <= kWave), "frame-pipelined instances: one wavefront per workgroup");
   if constexpr (SEQ) {
-    // the SAFE pass of a window (lk_engine.cpp: launch_window): enqueued behind the fast flavour on the same stream, so the
+    // the SAFE pass of a window (lk_engine_sequence.cpp: launch_window): enqueued behind the fast flavour on the same stream, so the
     // flag is final here - no bad pivot, nothing to solve again
     if (a.seq_gate && __hip_atomic_load(a.seq_gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
       return;
@@ -3569,7 +3569,7 @@ hipError_t lk_launch_stale_iterations_window(lk_result *all, int n, int n_ranks,
 }
 
 // ------------------------------------------------------------------------------------
-// launch wrappers (called from lk_engine.cpp)
+// launch wrappers (called from the lk_engine*.cpp units)
 // ------------------------------------------------------------------------------------
 // Persistent launch: as many workgroups as the device keeps resident (or fewer when there
 // is less work).  Nothing waits on another workgroup, so an over-estimate is harmless.
@@ -3657,7 +3657,7 @@ static hipError_t launch_solve_gs(const LkSolveArgs &a, hipStream_t st) {
   int grid_persistent = resident;
   if (GROUP == 512 && a.slots_permille > 0) {
     // the one-workgroup class beside a team launch: a persistent grid on its share of the slots (largest sectors first in
-    // the queue, lk_engine.cpp), so that the team's workgroups are all resident next to it from the start
+    // the queue, lk_engine_sectors.cpp), so that the team's workgroups are all resident next to it from the start
     b.persistent = 1;
     const int all = resident / (a.gpu_share > 1 ? a.gpu_share : 1);
     const int share = (all & ~7) - split_slots(all, 1000 - a.slots_permille); // (what the team launch leaves, see split_slots)

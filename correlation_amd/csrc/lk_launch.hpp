@@ -1,4 +1,4 @@
-// lk_launch.hpp - the kernel launchers: what the host code (lk_engine.cpp, lk_group.cpp, lk_guess_search.cpp) calls
+// lk_launch.hpp - the kernel launchers: what the host code (lk_engine*.cpp, lk_group.cpp, lk_guess_search.cpp) calls
 // and the .hip files define.  Every file on either side includes this header, so each declaration meets its definition
 // in front of a compiler.  Same shared library; nothing here is part of include/*.h.
 #pragma once

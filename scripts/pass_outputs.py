@@ -11,9 +11,16 @@ look for neighbours.  Both are solved once; then a few records are made bad (an 
 chi) and one u becomes -0.  Every variant below runs in a child process of its own - the lane group and the variant of a
 pass are chosen by environment variables that the library reads per call, and a fault must not reach the next one - under
 a time limit, and the first failure ends the run.  The arrays of all variants go into one .npz, `variant/array`.
+
+The `solve_all_*`, `correlate_one*`, `window_*` and `reseed_failed` variants are the engine's own launch paths - for a change of
+the host side of the solve (lk_engine_solve.cpp, lk_engine_sequence.cpp) that must not change a record: lk_correlate_all of
+`mix` in every mode, without class streams and with forced teams; lk_correlate on each of its sectors; one window of four
+frames (`mix_small`: mix without the 10 000-sample rectangle, so that it is frame-pipelined; `grid` with a starved level);
+a recovery pass that re-solves a sector subset.  `--only REGEX` runs some of the variants.
 """
 import argparse
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -228,7 +235,106 @@ def run_znssd():
     return out
 
 
+# ---- the solve's own launch paths (lk_engine_solve.cpp, lk_engine_sequence.cpp): records of the engine itself -----------
+MODES = ("default", "batch_invariant", "reference_order1", "reference_order4", "backward")
+
+
+def committed(scene, mode, py_stop=2):
+    """(engine with the pair and the scene's sectors committed in `mode`, its guesses); `mix_small`: mix without its
+    10 000-sample rectangle, whose lane group has no frame-pipelined instance"""
+    import correlation_amd as ca
+    und, dfm = ca.speckle.speckle_pair(256, 256, p=TRUTH, seed=5)
+    e = ca.HipCorrelationEngine(interpolation=ca.IM_BICUBIC, fitting_model=ca.FM_UVUXUYVXVY, precision=1e-3, py_stop=py_stop)
+    if mode == "batch_invariant":
+        e.set_batch_invariant(True)
+    elif mode.startswith("reference_order"):
+        e.set_reference_order(int(mode[len("reference_order"):]))
+    elif mode == "backward":
+        e.set_update(ca.UPDATE_BACKWARD)
+    e.set_undeformed_image(und)
+    e.set_deformed_image(dfm)
+    if scene == "grid":
+        e.set_rect_grid(8.0, 8.0, 247.0, 247.0, 24, 24)
+    else:
+        rects = RECTS if scene == "mix" else RECTS[:3]
+        for s, r in enumerate(rects):
+            e.resetPolygon_rect(s, *r)
+        for k, q in enumerate(ANNULAR):
+            e.resetPolygon_annular(len(rects) + k, *q)
+    e.commit_sectors()
+    g = np.zeros((e.n_sectors, 6), np.float32)
+    g[:, :2] = TRUTH[:2]
+    return e, g
+
+
+def solve_all(mode):
+    def run():
+        e, g = committed("mix", mode)
+        out = fields("all", e.correlate_all(g))
+        out["all.sector_stats"] = e.sector_stats()
+        return out
+    return run
+
+
+def correlate_one(modes):
+    def run():
+        out = {}
+        for mode in modes:
+            e, g = committed("mix", mode)
+            for s in range(e.n_sectors):   # 361, 49, 899 and 10 000 samples and the annular list: every lane group
+                rec, guess = e.correlate(s, g[s])
+                out.update(fields("one_%s_%d" % (mode, s), np.array([rec])))
+                out["one_%s_%d.guess" % (mode, s)] = guess
+            out["one_%s.sector_stats" % mode] = e.sector_stats()
+            e.close()
+        return out
+    return run
+
+
+def window(scene, mode, py_stop=2):
+    def run():
+        import correlation_amd as ca
+        e, g = committed(scene, mode, py_stop)
+        e.sequence_reserve(4)
+        for f in range(4):   # frame f: (f + 1) / 2 of the pair's deformation
+            e.sequence_set_frame(f, ca.speckle.speckle_pair(256, 256, p=tuple(0.5 * (f + 1) * t for t in TRUTH), seed=5)[1])
+        g[:, :2] *= np.float32(0.5)
+        e.correlate_all(g)   # (leaves the guesses of frame 0 with the engine)
+        rec = e.correlate_sequence(4, keep_guesses=True)
+        out = fields("window", rec)
+        out["window.guesses"] = e.sequence_guesses()
+        out["window.pipelined"] = np.array([int(e.sequence_is_pipelined)])
+        out["window.after"] = e.correlate_all()   # (the sequence state the window leaves behind)
+        return out
+    return run
+
+
+def run_reseed():
+    import correlation_amd as ca
+    e, g = committed("grid", "batch_invariant")
+    clean = e.correlate_all(g)
+    chi_max = 4.0 * float(clean["chi"][clean["error_code"] == 0].max())
+    g[7::37, 0] = 300.0   # beyond the image: these sectors fail by their error code
+    out = fields("before", e.correlate_all(g))
+    rec, n = e.reseed_failed(RADIUS, chi_max=chi_max, min_neighbours=1, max_rounds=2)
+    out.update(fields("reseeded", rec))
+    out.update(fields("info", e.reseed_info()))
+    out["recovered"] = np.array([n])
+    return out
+
+
 # (name, environment, function)
+SOLVES = [("solve_all_" + m, {}, solve_all(m)) for m in MODES[:4]]
+SOLVES += [("solve_all_class_streams0", {"LK_CLASS_STREAMS": "0"}, solve_all("default")),
+           ("solve_all_force_team2", {"LK_FORCE_TEAM": "2"}, solve_all("default")),
+           ("correlate_one", {}, correlate_one(("default", "reference_order1", "backward"))),
+           ("correlate_one_force_team2", {"LK_FORCE_TEAM": "2"}, correlate_one(("default", "reference_order1", "backward"))),
+           ("window_default", {}, window("mix_small", "default")),
+           ("window_batch_invariant", {}, window("mix_small", "batch_invariant")),   # (several classes side by side)
+           ("window_pipeline0", {"LK_SEQ_PIPELINE": "0"}, window("mix_small", "default")),
+           ("window_reference_order", {}, window("mix_small", "reference_order1")),
+           ("window_grid_starved", {}, window("grid", "default", py_stop=3)),
+           ("reseed_failed", {}, run_reseed)]
 VARIANTS = [("strain_g%d_packed%d" % (g, p), {"LK_STRAIN_GROUP": str(g), "LK_STRAIN_PACKED": str(p)}, run_strain)
             for g in (16, 64) for p in (0, 1)]
 VARIANTS += [("outlier_g%d_cap%s" % (g, cap), {"LK_OUTLIER_GROUP": str(g), "LK_OUTLIER_LDS_CAP": cap}, run_outlier)
@@ -237,6 +343,7 @@ VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (
 VARIANTS += [("field_walk%d" % w, {"LK_FIELD_WALK": str(w)}, run_field) for w in (0, 1)]
 VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
              ("pattern", {}, run_pattern), ("znssd", {}, run_znssd)]
+VARIANTS += SOLVES
 
 
 def compare(path_a, path_b):
@@ -262,6 +369,7 @@ def main():
     ap.add_argument("out", nargs="?")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"))
     ap.add_argument("--variant", help=argparse.SUPPRESS)   # (the child)
+    ap.add_argument("--only", metavar="REGEX", help="run the variants whose name matches (default: all)")
     args = ap.parse_args()
     if args.compare:
         return compare(*args.compare)
@@ -274,6 +382,8 @@ def main():
     merged = {}
     with tempfile.TemporaryDirectory() as tmp:
         for name, env, _ in VARIANTS:
+            if args.only and not re.search(args.only, name):
+                continue
             part = os.path.join(tmp, name + ".npz")
             try:
                 status = subprocess.run([sys.executable, os.path.abspath(__file__), part, "--variant", name],

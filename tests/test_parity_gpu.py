@@ -356,6 +356,59 @@ def test_team_launches_of_two_engines_take_turns(monkeypatch, speckle512):
         assert hip.hipStreamDestroy(st) == 0
 
 
+def test_one_sector_team_solve_takes_its_turn(monkeypatch):
+    """lk_correlate on a sector that has a team (the third launch path with a team turn: the batch paths are the test
+    above) while another engine of the process has a team solve in flight on a stream of its own: the call returns, and
+    with the record the engine gets alone; so does the other engine's batch."""
+    import ctypes
+    import threading
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipStreamCreateWithFlags.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint]
+    hip.hipStreamDestroy.argtypes = [ctypes.c_void_p]
+    monkeypatch.setenv("LK_FORCE_TEAM", "2")    # the sector a team of 2 workgroups
+    und, dfm = ca.speckle.speckle_pair(128, 128, seed=11)
+
+    def engine(stream=None):
+        e = ca.HipCorrelationEngine(interpolation=ca.IM_BILINEAR, py_stop=1)
+        if stream is not None:
+            e.set_stream(stream.value)
+        e.set_undeformed_image(und)
+        e.set_deformed_image(dfm)
+        e.resetPolygon_rect(0, 32, 32, 95, 95)
+        e.commit_sectors()
+        return e
+
+    zero = np.zeros(6, np.float32)
+    one = engine()
+    want, want_guess = one.correlate(0, zero)
+    assert want["error_code"] == 0
+    st = ctypes.c_void_p()
+    assert hip.hipStreamCreateWithFlags(ctypes.byref(st), 1) == 0
+    other = engine(st)
+    other_want = other.correlate_all(np.zeros((1, 6), np.float32))
+    got = []
+
+    def work():
+        for rep in range(4):
+            other.adjust_initial_guess(0, False, zero, (64.0, 64.0))
+            other.correlate_all_async()             # a team solve in flight ...
+            got.append(one.correlate(0, zero))      # ... and the one-sector call takes the next turn
+            got.append(other.wait_results())
+
+    t = threading.Thread(target=work, daemon=True)
+    t.start()
+    t.join(60.0)
+    assert not t.is_alive(), "lk_correlate did not return while another engine's team solve was in flight"
+    assert len(got) == 8
+    for rep in range(4):
+        rec, guess = got[2 * rep]
+        assert rec.tobytes() == want.tobytes() and guess.tobytes() == want_guess.tobytes(), rep
+        assert got[2 * rep + 1].tobytes() == other_want.tobytes(), rep
+    one.close()
+    other.close()
+    assert hip.hipStreamDestroy(st) == 0
+
+
 @pytest.mark.parametrize("interp", [ca.IM_NEAREST, ca.IM_BILINEAR, ca.IM_BICUBIC])
 def test_sampling_bit_exact(oracle, speckle512, interp):
     und, dfm = speckle512
