@@ -180,6 +180,24 @@ ZNSSD_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "iteration
                        [("reserved", np.int32, (4,))])
 assert ZNSSD_DTYPE.itemsize == 64 and C.sizeof(LkZnssdConfig) == 32
 
+# second-order refinement (include/lk_engine.h: lk_refine_quadratic); the statuses are ZN_*
+QD_SUMS = 88   # doubles per sector: Sf, Sg, Sff, Sgg, Sfg, 3 x 15 moments of gx gx, gx gy, gy gy, 12 sums t, t f, t g, 0, flagged
+QD_PARAMS = 12
+
+
+class LkQuadraticConfig(C.Structure):
+    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float),
+                ("lambda0", C.c_float), ("reserved", C.c_int * 3)]
+
+
+# struct lk_quadratic as a numpy record
+QUADRATIC_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "iterations", "evaluations")] +
+                           [("p", np.float32, (12,))] +
+                           [(k, np.float32) for k in ("zncc", "gain", "offset", "znssd", "zncc_seed", "shift", "lambda",
+                                                      "last_step", "bend")] +
+                           [("reserved", np.int32, (7,))])
+assert QUADRATIC_DTYPE.itemsize == 128 and C.sizeof(LkQuadraticConfig) == 32
+
 # speckle quality (include/lk_engine.h: lk_pattern_quality, lk_suggest_subset)
 PATTERN_OK, PATTERN_TOO_FEW, PATTERN_FLAT, PATTERN_APERTURE, PATTERN_SATURATED = range(5)
 SUBSET_OK, SUBSET_NONE, SUBSET_BAD_POINT = range(3)
@@ -317,6 +335,8 @@ SYMBOLS = {
     "lk_map_owner": (C.c_int, [C.c_int, _F, _P, C.c_double, C.c_double, C.c_double]),
     "lk_refine_znssd": (C.c_int, [_P, C.POINTER(LkZnssdConfig), _P, _F, _P, _P, _P]),
     "lk_znssd_step_from_sums": (C.c_int, [C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
+    "lk_refine_quadratic": (C.c_int, [_P, C.POINTER(LkQuadraticConfig), _P, _F, _F, _P, _P, _P]),
+    "lk_quadratic_step_from_sums": (C.c_int, [C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "lk_field_map": (C.c_int, [_P, C.POINTER(LkFieldMapConfig), _P, _P, _P, _P]),
     "lk_field_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_double, _P, C.c_int, _F, _I]),
     "lk_pattern_quality": (C.c_int, [_P, C.POINTER(LkPatternConfig), _P, _P, _P]),
@@ -521,6 +541,20 @@ def znssd_step_from_sums(model, n, sums, lam):
     if _compose_lib.lk_znssd_step_from_sums(int(model), int(n), s.ctypes.data_as(_P), float(lam), delta.ctypes.data_as(_P),
                                             C.byref(crit), go.ctypes.data_as(_P), C.byref(status)) != 0:
         raise ValueError(f"lk_znssd_step_from_sums: bad model {model}, n < 0 or a bad lambda")
+    return status.value, delta, crit.value, float(go[0]), float(go[1])
+
+
+def quadratic_step_from_sums(n, sums, lam):
+    """lk_quadratic_step_from_sums (host, the kernel's function): (status, delta [12], crit, gain, offset) of one sector of n
+    samples whose QD_SUMS sums are `sums`, at the damping `lam`."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.ascontiguousarray(sums, np.float64).reshape(QD_SUMS)
+    delta, crit, go, status = np.zeros(QD_PARAMS, np.float64), C.c_double(), np.zeros(2, np.float64), C.c_int32(-1)
+    if _compose_lib.lk_quadratic_step_from_sums(int(n), s.ctypes.data_as(_P), float(lam), delta.ctypes.data_as(_P), C.byref(crit),
+                                                go.ctypes.data_as(_P), C.byref(status)) != 0:
+        raise ValueError("lk_quadratic_step_from_sums: n < 0 or a bad lambda")
     return status.value, delta, crit.value, float(go[0]), float(go[1])
 
 

@@ -371,6 +371,20 @@ struct LkZnssdArgs {
   float chi_max, precision, lambda0;
 };
 
+// Second-order refinement (lk_quadratic.hip, include/lk_engine.h: lk_refine_quadratic): the ZNSSD pass's loop on twelve
+// parameters; the engine's model only says how a seed is read and a record written.
+struct LkQuadraticArgs {
+  LkSectorEvalArgs ev;      // ev.rec: [S] the seed records, read when guess is null
+  const float *guess;       // [S][6] level-0 seeds in the engine model's meaning, or null
+  const float *second;      // [S][6] level-0 second-order seeds, or null: zeros
+  const int32_t *count0;    // [S] level-0 sample counts (the records' numberOfPoints)
+  lk_result *rec_out;       // [S]
+  struct lk_quadratic *out; // [S]
+  double *sums;             // [S][88] or null (lk_quadratic.hpp: kLkQdSums)
+  int n_sectors, level, max_iters, model;
+  float chi_max, precision, lambda0;
+};
+
 // Residual map (lk_residual.hip, include/lk_engine.h: lk_residual_map): what a pixel needs of a sector, 48 bytes.
 struct LkMapSector {
   float cx0, cy0; // level-0 centre; cx0 = NaN for a sector that is not good (it then fails the distance test by itself)

@@ -130,6 +130,10 @@ hipError_t lk_launch_residual_map(const LkResidualMapArgs &a, int model, int int
 // One launch carries every sector of the group from its seed to its final record.
 hipError_t lk_launch_znssd(const LkZnssdArgs &a, int model, int interp, int group, hipStream_t st);
 
+// ---- lk_quadratic.hip: the second-order refinement (lk_refine_quadratic)
+// as lk_launch_znssd; the engine's model travels in a.model (the kernel has no model template)
+hipError_t lk_launch_quadratic(const LkQuadraticArgs &a, int interp, int group, hipStream_t st);
+
 // ---- lk_pattern.hip: speckle quality (lk_pattern_quality, lk_suggest_subset)
 // group: 16, 64 or 512 lanes per sector (lk_bw_group of the level-0 sample count); a.ev.order lists that group's sectors
 hipError_t lk_launch_pattern(const LkPatternArgs &a, int group, hipStream_t st);

@@ -522,6 +522,45 @@ class HipCorrelationEngine:
         """lk_znssd_step_from_sums: the kernel's criterion and step on the host (no engine needed)."""
         return _ffi.znssd_step_from_sums(model, n, sums, lam)
 
+    # ---- second-order refinement: a subset model that can bend ----------------------------------------------
+    def refine_quadratic(self, records=None, guesses=None, second=None, def_slot=-1, chi_max=0.0, max_iters=-1, precision=0.0,
+                         lambda0=0.0, return_sums=False):
+        """lk_refine_quadratic: refine_znssd with second-order shape functions - twelve parameters (u, v, ux, uy, vx, vy, uxx,
+        uxy, uyy, vxx, vxy, vyy) whatever the engine's model, which only says how `guesses` [S][6] and the records are read
+        and the returned records written.  second: [S][6] second-order seeds in level-0 scale (None: zeros); feeding
+        (records, info["p"][:, 6:]) back in continues a refinement.  Returns (records RESULT_DTYPE [S], info QUADRATIC_DTYPE
+        [S]) and, with return_sums, the 88 double sums of every sector at the returned parameters.  No engine state changes."""
+        cfg = _ffi.LkQuadraticConfig(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
+                                     float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0))
+        rec = g = g2 = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        if guesses is not None:
+            g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
+        if second is not None:
+            g2 = np.ascontiguousarray(second, np.float32).reshape(self.n_sectors, 6)
+        out = np.zeros(self.n_sectors, RESULT_DTYPE)
+        info = np.zeros(self.n_sectors, _ffi.QUADRATIC_DTYPE)
+        sums = np.zeros((self.n_sectors, _ffi.QD_SUMS), np.float64) if return_sums else None
+        self._chk(self.lib.lk_refine_quadratic(self._h, C.byref(cfg), rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
+                                               _ffi.fptr(g) if g is not None else None, _ffi.fptr(g2) if g2 is not None else None,
+                                               out.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p),
+                                               sums.ctypes.data_as(C.c_void_p) if return_sums else None))
+        return (out, info, sums) if return_sums else (out, info)
+
+    def quadratic_last(self):
+        """Bench hook: (device ms, the sectors the 16-, 64- and 512-lane groups took) of the last refine_quadratic call."""
+        ms, cnt = C.c_float(), (C.c_int * 3)()
+        fn = self.lib.lk_internal_quadratic_last
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        self._chk(fn(self._h, C.byref(ms), cnt))
+        return ms.value, tuple(cnt)
+
+    @staticmethod
+    def quadratic_step_from_sums(n, sums, lam):
+        """lk_quadratic_step_from_sums: the kernel's criterion and step on the host (no engine needed)."""
+        return _ffi.quadratic_step_from_sums(n, sums, lam)
+
     # ---- speckle quality: is the pattern good enough, how large must the subsets be ----------------------
     def pattern_quality(self, slot=_ffi.IMG_UND, grey_low=0, grey_high=255, noise_sigma=1.0, max_saturated=1.0,
                         return_sums=False):

@@ -1036,6 +1036,89 @@ int lk_refine_znssd(lk_engine *e, const lk_znssd_config *cfg, const lk_result *r
 int lk_znssd_step_from_sums(int model, int n, const double *sums, float lambda, double *delta6, double *crit,
                             double *gain_offset2, int32_t *status);
 
+/* ---- second-order refinement: a subset model that can bend ------------------------------------ */
+/* Every solve of the engine, lk_refine_znssd included, matches a subset with an affine shape function at most.  Where the
+ * displacement curves inside a subset - next to a hole, a notch, a bend - that model is too poor and the answer carries a
+ * systematic error that grows with the subset.  lk_refine_quadratic is lk_refine_znssd with second-order shape functions
+ * (Lu & Cary 2000): the same seeds, level, walk, sampler, criterion, loop, statuses (LK_ZN_*), records and refusals, on
+ * twelve parameters, in a kernel of its own (csrc/lk_quadratic.hip).  What is not said here is as
+ * for lk_refine_znssd.
+ *   model     p = (u, v, ux, uy, vx, vy, uxx, uxy, uyy, vxx, vxy, vyy), whatever the engine's fitting model is:
+ *               x' = x + u + ux dx + uy dy + uxx dx^2 / 2 + uxy dx dy + uyy dy^2 / 2,  y' alike with v,
+ *             dx = x - cx, dy = y - cy about the committed centre (times 2^-L).  In float, without contraction:
+ *               hxx = 0.5f (dx dx), hxy = dx dy, hyy = 0.5f (dy dy),
+ *               x' = (((((x + p0) + p2 dx) + p3 dy) + p6 hxx) + p7 hxy) + p8 hyy,  y' from p1, p4, p5, p9, p10, p11;
+ *             with zero second-order terms these are the bits of the affine warp of the solve.
+ *   level     L = py_start.  Seeds go to level L and results come back by the solve's translation: u and v times 2^-L, the
+ *             four gradients unchanged, the six second-order terms times 2^L (and 2^-L on the way back).
+ *   seeds     `records` and `guesses` as for lk_refine_znssd (the good rule with the engine model's P; guesses [S][6] in the
+ *             engine model's meaning).  The engine model maps onto the first six parameters by its own warp: LK_FM_U: u;
+ *             LK_FM_UV: u, v; LK_FM_UVQ: u, v, uy = -q, vx = q; LK_FM_UVUXUYVXVY: all six; the rest 0.  second: host
+ *             [S][6] = (uxx, uxy, uyy, vxx, vxy, vyy) in level-0 scale, NULL = zeros; with it, feeding (records_out,
+ *             info.p + 6) back in continues a refinement.  A sector whose second-order seeds are not all finite is
+ *             LK_ZN_BAD_SEED like one whose guesses are not: errorCode LK_ERROR_BAD_DOMAIN, the first-order seed as its
+ *             parameters.  (A record that fails the good rule is copied, as for lk_refine_znssd.)
+ *   sums      88 doubles per evaluation (kLkQdSums), from the floats f, g, gx, gy, dx, dy of a sample; every product is
+ *             formed in double and rounded once, no fused multiply-add.  X = (double)dx, X2 = X X, X3 = X2 X, X4 = X2 X2,
+ *             Y alike; the 15 monomials M[k] = X^a Y^b, a + b <= 4, by degree, then by falling a, each formed as Xa Yb:
+ *               [0..4]    Sf, Sg, Sff, Sgg, Sfg
+ *               [5..49]   sum w M[k] for w = gx gx, then gx gy, then gy gy; k = 0 .. 14 each
+ *               [50..61]  sum t for t = gx M[k], k = 0 .. 5, then t = gy M[k]
+ *               [62..73]  sum t f over the same twelve t
+ *               [74..85]  sum t g over the same twelve t
+ *               [86]      0
+ *               [87]      the samples the sampler flagged
+ *             H of the twelve parameters is gx or gy times a monomial of degree <= 2 times 1 or 1/2, so SH, SHH, SHf and
+ *             SHg of lk_refine_znssd's step are these moments times 1, 1/2 or 1/4, exactly.  The kernel forms the sums in
+ *             three sweeps over the samples ([0..4], [50..73], [87]; [5..19], [74..85]; [20..49]); every sweep computes a
+ *             sample's floats identically and adds in the uncertainty pass's fixed order, so a sector's sums, trajectory,
+ *             record and info are the same bytes in any batch, shard, mode or ring slot.
+ *   step      lk_quadratic_step_from_sums (one function for the kernel and the host, csrc/lk_quadratic.hpp): the
+ *             criterion and the formulas of lk_znssd_step_from_sums with P = 12 - LK_ZN_TOO_FEW if n < 14; FLAT,
+ *             NEGATIVE; A, b; the scaling to a diagonal of 1 + lambda; the unpivoted L D L^T; LK_ZN_SINGULAR for A_kk <= 0
+ *             or a pivot <= 1e-10.
+ *   loop      lk_refine_znssd's, with the weights, for h = max(1, sqrt(n_L) / 2): 1 for u, v; h for the four gradients;
+ *             h^2 / 2 for uxx, uyy, vxx, vyy; h^2 for uxy, vxy - so max_k w_k |delta_k| bounds how far any sample moved.
+ *   records   records_out [S] as lk_refine_znssd's - chi = (Sff - 2 Sfg + Sgg) / n_L, the counts, the centre, the
+ *             errorCode mapping - with the parameters in the engine model's own layout, so that every downstream pass
+ *             reads them as it reads the solve's: LK_FM_U: u; LK_FM_UV: u, v; LK_FM_UVQ: u, v, q = (vx - uy) / 2 in
+ *             float; LK_FM_UVUXUYVXVY: the six first-order terms; zeros behind P.  The twelve parameters are in the info.
+ *   info      as struct lk_znssd, and p[12] in level-0 scale (zeros for BAD_SEED and OUT_OF_IMAGE), shift from (u, v)
+ *             both, and bend = h0^2 max(|uxx| / 2 + |uxy| + |uyy| / 2, |vxx| / 2 + |vxy| + |vyy| / 2), h0 = sqrt(n_0) / 2: the
+ *             second-order displacement at the rim of the subset in level-0 pixels - where it is large, the affine model
+ *             was under-matched.  BAD_SEED and OUT_OF_IMAGE: floats and sums 0.  FLAT and TOO_FEW: the seed's sums, p and
+ *             bend the seed's, the other floats 0.
+ *   modes     as lk_refine_znssd: every mode, synchronous, nothing of the engine is written.
+ *   errors    as lk_refine_znssd, with this function's name in the messages.
+ *   defaults  as lk_refine_znssd.
+ *   scope     as lk_refine_znssd; and no batch solve or sequence window gets second-order terms, lk_result stays 48 bytes. */
+typedef struct lk_quadratic_config {
+  int def_slot;       /* the words of lk_znssd_config */
+  float chi_max;
+  int max_iters;
+  float precision;
+  float lambda0;
+  int reserved[3];    /* must be 0 */
+} lk_quadratic_config;
+struct lk_quadratic { /* 128 bytes, one per sector */
+  int32_t n_points, status, iterations, evaluations;   /* status: LK_ZN_* */
+  float p[12];                         /* level-0 scale, the order above */
+  float zncc, gain, offset, znssd;     /* as struct lk_znssd */
+  float zncc_seed, shift, lambda, last_step;
+  float bend;                          /* second-order displacement at the subset rim, level-0 pixels */
+  int32_t reserved[7];
+};
+/* records, guesses, records_out, info_out: as lk_refine_znssd.  second: host [S][6] or NULL.  sums_out: [S][88] doubles or
+ * NULL, the kept sums at the returned parameters.  Synchronous.  Changes no engine state. */
+int lk_refine_quadratic(lk_engine *e, const lk_quadratic_config *cfg, const lk_result *records, const float *guesses,
+                        const float *second, lk_result *records_out, struct lk_quadratic *info_out, double *sums_out);
+/* the kernel's own function compiled for the host: criterion and damped step of one sector of n samples with the 88 sums
+ * `sums88`.  *status = 0, or LK_ZN_TOO_FEW, LK_ZN_FLAT, LK_ZN_NEGATIVE or LK_ZN_SINGULAR; delta12 (all zeros unless
+ * *status = 0), crit and gain_offset2 may each be NULL.  LK_ERROR_BAD_DOMAIN (outputs untouched) for a null sums or status
+ * pointer, n < 0 or a lambda that is negative or not finite. */
+int lk_quadratic_step_from_sums(int n, const double *sums88, float lambda, double *delta12, double *crit,
+                                double *gain_offset2, int32_t *status);
+
 /* ---- field map: dense displacement and strain maps on a regular grid of nodes ---------------- */
 /* lk_field_map gives the full-field picture a DIC user looks at first: u, v, the gradients, the strain tensor and its
  * principal values on a regular grid of nodes - every pixel, or every stride-th - drawn in the reference image or over the

@@ -235,6 +235,27 @@ def run_znssd():
     return out
 
 
+def run_quadratic():
+    import correlation_amd as ca
+    out = {}
+    for scene in ("mix", "grid"):
+        for model, interp, name in ((ca.FM_UVUXUYVXVY, ca.IM_BICUBIC, "affine_bicubic"), (ca.FM_UV, ca.IM_BILINEAR, "uv_bilinear"),
+                                    (ca.FM_UVQ, ca.IM_BICUBIC_SEPARABLE, "uvq_separable"), (ca.FM_U, ca.IM_BICUBIC, "u_bicubic")):
+            e, rec = solved(scene, model, interp)
+            g = np.zeros((e.n_sectors, 6), np.float32)
+            g[:, :2] = TRUTH[:2]
+            g2 = np.tile(np.float32([1e-4, -1e-4, 5e-5, -5e-5, 1e-4, -1e-4]), (e.n_sectors, 1))
+            for seeds, kw in (("records", dict(records=rec)), ("guesses", dict(guesses=g)), ("second", dict(guesses=g, second=g2)),
+                              ("one_trip", dict(guesses=g, max_iters=1))):
+                refined, info, sums = e.refine_quadratic(return_sums=True, **kw)
+                tag = "quadratic_%s_%s_%s" % (scene, name, seeds)
+                out.update(fields(tag + ".records", refined))
+                out.update(fields(tag, info))
+                out[tag + ".sums"] = sums
+            e.close()
+    return out
+
+
 # ---- the solve's own launch paths (lk_engine_solve.cpp, lk_engine_sequence.cpp): records of the engine itself -----------
 MODES = ("default", "batch_invariant", "reference_order1", "reference_order4", "backward")
 
@@ -342,7 +363,7 @@ VARIANTS += [("outlier_g%d_cap%s" % (g, cap), {"LK_OUTLIER_GROUP": str(g), "LK_O
 VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (16, 64)]
 VARIANTS += [("field_walk%d" % w, {"LK_FIELD_WALK": str(w)}, run_field) for w in (0, 1)]
 VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
-             ("pattern", {}, run_pattern), ("znssd", {}, run_znssd)]
+             ("pattern", {}, run_pattern), ("znssd", {}, run_znssd), ("quadratic", {}, run_quadratic)]
 VARIANTS += SOLVES
 
 
