@@ -198,6 +198,14 @@ QUADRATIC_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "itera
                            [("reserved", np.int32, (7,))])
 assert QUADRATIC_DTYPE.itemsize == 128 and C.sizeof(LkQuadraticConfig) == 32
 
+# B-spline refinement (include/lk_engine.h: lk_refine_spline); statuses ZN_*, info ZNSSD_DTYPE, sums ZN_SUMS
+class LkSplineConfig(C.Structure):
+    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float),
+                ("lambda0", C.c_float), ("order", C.c_int), ("reserved", C.c_int * 2)]
+
+
+assert C.sizeof(LkSplineConfig) == 32
+
 # speckle quality (include/lk_engine.h: lk_pattern_quality, lk_suggest_subset)
 PATTERN_OK, PATTERN_TOO_FEW, PATTERN_FLAT, PATTERN_APERTURE, PATTERN_SATURATED = range(5)
 SUBSET_OK, SUBSET_NONE, SUBSET_BAD_POINT = range(3)
@@ -336,6 +344,10 @@ SYMBOLS = {
     "lk_refine_znssd": (C.c_int, [_P, C.POINTER(LkZnssdConfig), _P, _F, _P, _P, _P]),
     "lk_znssd_step_from_sums": (C.c_int, [C.c_int, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "lk_refine_quadratic": (C.c_int, [_P, C.POINTER(LkQuadraticConfig), _P, _F, _F, _P, _P, _P]),
+    "lk_refine_spline": (C.c_int, [_P, C.POINTER(LkSplineConfig), _P, _F, _P, _P, _P]),
+    "lk_spline_coefficients": (C.c_int, [_P, C.c_int, C.c_int, _F]),
+    "lk_spline_sample": (C.c_int, [_P, C.c_int, C.c_int, _F, C.c_int, _F]),
+    "lk_spline_weights": (C.c_int, [C.c_int, C.c_float, _F, _F]),
     "lk_quadratic_step_from_sums": (C.c_int, [C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "lk_field_map": (C.c_int, [_P, C.POINTER(LkFieldMapConfig), _P, _P, _P, _P]),
     "lk_field_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_double, _P, C.c_int, _F, _I]),
@@ -556,6 +568,19 @@ def quadratic_step_from_sums(n, sums, lam):
                                                 go.ctypes.data_as(_P), C.byref(status)) != 0:
         raise ValueError("lk_quadratic_step_from_sums: n < 0 or a bad lambda")
     return status.value, delta, crit.value, float(go[0]), float(go[1])
+
+
+def spline_weights(order, t):
+    """lk_spline_weights (host, the kernel's function): (w, g), the order + 1 float32 weights and derivative weights of the
+    B-spline sampler at the fraction t."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    w, g = np.zeros(6, np.float32), np.zeros(6, np.float32)
+    if _compose_lib.lk_spline_weights(int(order), float(t), fptr(w), fptr(g)) != 0:
+        raise ValueError(f"lk_spline_weights: order {order} is not 3 or 5, or t is not finite")
+    n = (int(order) or 5) + 1
+    return w[:n], g[:n]
 
 
 def pattern_from_sums(n, sums9, mig_sum, noise_sigma=1.0, max_saturated=1.0):

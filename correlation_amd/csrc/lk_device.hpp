@@ -371,6 +371,13 @@ struct LkZnssdArgs {
   float chi_max, precision, lambda0;
 };
 
+// B-spline refinement (lk_spline.hip, include/lk_engine.h: lk_refine_spline): the ZNSSD pass's arguments and the coefficient
+// image its sampler reads in place of zn.ev.def.
+struct LkSplineArgs {
+  LkZnssdArgs zn;
+  const float *coef;        // [zn.ev.drows][zn.ev.dcols]
+};
+
 // Second-order refinement (lk_quadratic.hip, include/lk_engine.h: lk_refine_quadratic): the ZNSSD pass's loop on twelve
 // parameters; the engine's model only says how a seed is read and a record written.
 struct LkQuadraticArgs {

@@ -130,6 +130,16 @@ hipError_t lk_launch_residual_map(const LkResidualMapArgs &a, int model, int int
 // One launch carries every sector of the group from its seed to its final record.
 hipError_t lk_launch_znssd(const LkZnssdArgs &a, int model, int interp, int group, hipStream_t st);
 
+// ---- lk_spline.hip: the B-spline refinement (lk_refine_spline, lk_spline_coefficients, lk_spline_sample)
+// order: 3 or 5.  The coefficient image [rows][cols] of a level image (pitch == cols; rows, cols >= 2): the row step, then
+// the column step in place; the kernel boundary on the stream is the only ordering between them
+hipError_t lk_launch_spline_build(int order, const uint8_t *img, int rows, int cols, float *coef, hipStream_t st);
+// a thread per point: out[k] = {W, Wx, Wy, 1}, or zeros where the sampler's window leaves the image
+hipError_t lk_launch_spline_sample(int order, const float *coef, int rows, int cols, const float2 *pts, int n, float4 *out,
+                                   hipStream_t st);
+// as lk_launch_znssd, sampling a.coef
+hipError_t lk_launch_spline(const LkSplineArgs &a, int model, int order, int group, hipStream_t st);
+
 // ---- lk_quadratic.hip: the second-order refinement (lk_refine_quadratic)
 // as lk_launch_znssd; the engine's model travels in a.model (the kernel has no model template)
 hipError_t lk_launch_quadratic(const LkQuadraticArgs &a, int interp, int group, hipStream_t st);

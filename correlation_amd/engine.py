@@ -561,6 +561,59 @@ class HipCorrelationEngine:
         """lk_quadratic_step_from_sums: the kernel's criterion and step on the host (no engine needed)."""
         return _ffi.quadratic_step_from_sums(n, sums, lam)
 
+    # ---- B-spline refinement: the sub-pixel solve without the bicubic's interpolation bias ------------------
+    def refine_spline(self, records=None, guesses=None, order=5, def_slot=-1, chi_max=0.0, max_iters=-1, precision=0.0,
+                      lambda0=0.0, return_sums=False):
+        """lk_refine_spline: refine_znssd with the deformed image and its gradient taken from a cubic (order 3) or quintic
+        (order 5) B-spline of the prefiltered level-py_start image; the engine's interpolation plays no part.  Arguments and
+        return as refine_znssd: (records RESULT_DTYPE [S], info ZNSSD_DTYPE [S]) and, with return_sums, the 45 double sums
+        [S][45].  No engine state changes."""
+        cfg = _ffi.LkSplineConfig(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
+                                  float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0), int(order))
+        rec = g = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        if guesses is not None:
+            g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
+        out = np.zeros(self.n_sectors, RESULT_DTYPE)
+        info = np.zeros(self.n_sectors, _ffi.ZNSSD_DTYPE)
+        sums = np.zeros((self.n_sectors, _ffi.ZN_SUMS), np.float64) if return_sums else None
+        self._chk(self.lib.lk_refine_spline(self._h, C.byref(cfg), rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
+                                            _ffi.fptr(g) if g is not None else None, out.ctypes.data_as(C.c_void_p),
+                                            info.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p) if return_sums else None))
+        return (out, info, sums) if return_sums else (out, info)
+
+    def spline_last(self):
+        """Bench hook: (device ms, the sectors the 16-, 64- and 512-lane groups took, of that time the build of the
+        coefficient image) of the last refine_spline call."""
+        ms, cnt, build = C.c_float(), (C.c_int * 3)(), C.c_float()
+        fn = self.lib.lk_internal_spline_last
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        self._chk(fn(self._h, C.byref(ms), cnt, C.byref(build)))
+        return ms.value, tuple(cnt), build.value
+
+    def spline_coefficients(self, slot, order=5):
+        """lk_spline_coefficients: the float32 B-spline coefficient image [rows][cols] of the level-py_start image of `slot`,
+        as the pass builds it.  Needs no sectors; no engine state changes."""
+        r, c = C.c_int(), C.c_int()
+        self._chk(self.lib.lk_get_pyramid_level(self._h, int(slot), self.cfg.py_start, None, C.byref(r), C.byref(c)))
+        out = np.zeros((r.value, c.value), np.float32)
+        self._chk(self.lib.lk_spline_coefficients(self._h, int(slot), int(order), _ffi.fptr(out)))
+        return out
+
+    def spline_sample(self, slot, xy, order=5):
+        """lk_spline_sample: [n][4] float32 = W, Wx, Wy, ok of the pass's sampler at the points xy [n][2] (level-py_start
+        pixels of the image of `slot`); ok = 1, or a row of zeros where the sampler's window leaves the image."""
+        a = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.zeros((a.shape[0], 4), np.float32)
+        self._chk(self.lib.lk_spline_sample(self._h, int(slot), int(order), _ffi.fptr(a), a.shape[0], _ffi.fptr(out)))
+        return out
+
+    @staticmethod
+    def spline_weights(order, t):
+        """lk_spline_weights: the sampler's weights and derivative weights on the host (no engine needed)."""
+        return _ffi.spline_weights(order, t)
+
     # ---- speckle quality: is the pattern good enough, how large must the subsets be ----------------------
     def pattern_quality(self, slot=_ffi.IMG_UND, grey_low=0, grey_high=255, noise_sigma=1.0, max_saturated=1.0,
                         return_sums=False):

@@ -1119,6 +1119,61 @@ int lk_refine_quadratic(lk_engine *e, const lk_quadratic_config *cfg, const lk_r
 int lk_quadratic_step_from_sums(int n, const double *sums88, float lambda, double *delta12, double *crit,
                                 double *gain_offset2, int32_t *status);
 
+/* ---- B-spline refinement: a sub-pixel solve without the bicubic's interpolation bias ---------- */
+/* Every other sub-pixel solve of the engine reads the deformed image through the Keys / Catmull-Rom cubic, whose phase error
+ * gives a measured displacement a systematic error that follows its sub-pixel part (about 0 at 0 and 0.5 px, opposite signs
+ * at 0.25 and 0.75 px).  lk_refine_spline is lk_refine_znssd with g, g_x and g_y taken from a cubic or quintic B-spline of
+ * the prefiltered deformed image (Unser's recursive filter; Schreier, Braasch & Sutton 2000), in kernels of its own
+ * (csrc/lk_spline.hip).  What is not said here is as for lk_refine_znssd: seeds, level, walk, lane
+ * groups, warp, the 45 sums, criterion and step (lk_znssd_step_from_sums), loop, statuses (LK_ZN_*), records, info.
+ *   image     f stays the u8 node of the undeformed level image.  The engine's `interpolation` plays no part.
+ *   prefilter every call builds the float coefficient image [rows][cols] of the level-py_start deformed image anew (no
+ *             cache that could go stale).  Along every row, then along every column, for a line s[0 .. N - 1], in float,
+ *             each product and each sum rounded:
+ *               s[k] = lam s[k],  lam = prod (1 - z)(1 - 1 / z) = 6 (order 3) or 120 (order 5);
+ *               then per pole z - order 3: sqrt(3) - 2; order 5: sqrt(67.5 - sqrt(4436.25)) + sqrt(26.25) - 6.5, then
+ *               sqrt(67.5 + sqrt(4436.25)) - sqrt(26.25) - 6.5; each the float nearest the double value -
+ *               c[0] = s[0] + sum zp_k s[k], k = 1 .. min(N, 28) - 1 added in ascending k, zp_1 = z, zp_(k + 1) = zp_k z;
+ *               c[k] = s[k] + z c[k - 1] up to N - 1;
+ *               c[N - 1] = (z / (z z - 1)) (z c[N - 2] + c[N - 1]);   c[k] = z (c[k + 1] - c[k]) down to 0
+ *             (the mirror boundary).  A line is filtered in this order whatever the launch, so the coefficients are the
+ *             same bytes in any call.
+ *   sampler   at (x, y): ix = (int)x, t = x - ix, alike in y; nodes ix - 1 .. ix + 2 (order 3) or ix - 2 .. ix + 3 (order 5).
+ *             Valid for x > 1 && x < cols - 2 (order 3, the bicubic's rule) or x > 2 && x < cols - 3 (order 5), alike in y;
+ *             anything else is a flagged sample, LK_ZN_OUT_OF_IMAGE.  The weights w[] and the derivative weights g[] are
+ *             the pieces of the uniform B-spline as polynomials in t, every coefficient the float nearest the fraction,
+ *             by Horner's rule with one fused multiply-add per power (lk_spline_weights is that function on the host).
+ *             Per image row j: v_j = fma(wx[n], c[n], ... fma(wx[1], c[1], wx[0] c[0])) and d_j alike with gx; then, folded
+ *             in row by row from j = 0, W = fma(wy[j], v_j, W), Wx = fma(wy[j], d_j, Wx), Wy = fma(gy[j], v_j, Wy).
+ *   modes     as lk_refine_znssd: every mode, synchronous, nothing of the engine is written.
+ *   errors    as lk_refine_znssd, with this function's name in the messages; and an order that is not 0, 3 or 5; a level
+ *             image with a side below 8.
+ *   defaults  as lk_refine_znssd; order 0 is 5.
+ *   scope     as lk_refine_znssd.  lk_refine_quadratic keeps the engine's interpolator: giving it this sampler is a
+ *             follow-up.  The batch solve, the backward solve and the sequence windows keep theirs too. */
+typedef struct lk_spline_config {
+  int def_slot;       /* the words and defaults of lk_znssd_config */
+  float chi_max;
+  int max_iters;
+  float precision;
+  float lambda0;
+  int order;          /* 3 or 5; 0: 5 */
+  int reserved[2];    /* must be 0 */
+} lk_spline_config;
+/* records, guesses, records_out, info_out, sums_out: as lk_refine_znssd.  Synchronous.  Changes no engine state. */
+int lk_refine_spline(lk_engine *e, const lk_spline_config *cfg, const lk_result *records, const float *guesses,
+                     lk_result *records_out, struct lk_znssd *info_out, double *sums_out);
+/* The coefficient image of the level-py_start image of `slot` (LK_IMG_UND, LK_IMG_DEF or LK_IMG_NXT), out: host
+ * [rows][cols] floats of that level.  Needs no sectors and no other slot; allowed in every mode; changes no engine state.
+ * LK_ERROR_BAD_DOMAIN with a message: a null output, a bad order, a slot that is not set, a side below 8. */
+int lk_spline_coefficients(lk_engine *e, int slot, int order, float *out);
+/* The pass's sampler at n points xy [n][2] (level-py_start pixels of the image of `slot`): out4 [n][4] = W, Wx, Wy, ok with
+ * ok = 1, or four zeros where the sampler's window leaves the image.  Otherwise as lk_spline_coefficients. */
+int lk_spline_sample(lk_engine *e, int slot, int order, const float *xy, int n, float *out4);
+/* the kernel's weight function on the host: w6 and g6 take the order + 1 weights and derivative weights at the fraction t,
+ * zeros behind them.  LK_ERROR_BAD_DOMAIN for a null pointer, an order that is not 0, 3 or 5, or a t that is not finite. */
+int lk_spline_weights(int order, float t, float *w6, float *g6);
+
 /* ---- field map: dense displacement and strain maps on a regular grid of nodes ---------------- */
 /* lk_field_map gives the full-field picture a DIC user looks at first: u, v, the gradients, the strain tensor and its
  * principal values on a regular grid of nodes - every pixel, or every stride-th - drawn in the reference image or over the

@@ -235,6 +235,28 @@ def run_znssd():
     return out
 
 
+def run_spline():
+    import correlation_amd as ca
+    out = {}
+    for scene in ("mix", "grid"):
+        for model, name in ((ca.FM_UVUXUYVXVY, "affine"), (ca.FM_UV, "uv"), (ca.FM_UVQ, "uvq"), (ca.FM_U, "u")):
+            e, rec = solved(scene, model, ca.IM_BICUBIC)
+            g = np.zeros((e.n_sectors, 6), np.float32)
+            g[:, :2] = TRUTH[:2]
+            for order in (3, 5):
+                for seeds, kw in (("records", dict(records=rec)), ("guesses", dict(guesses=g))):
+                    refined, info, sums = e.refine_spline(order=order, return_sums=True, **kw)
+                    tag = "spline%d_%s_%s_%s" % (order, scene, name, seeds)
+                    out.update(fields(tag + ".records", refined))
+                    out.update(fields(tag, info))
+                    out[tag + ".sums"] = sums
+            if model == ca.FM_U:
+                for order in (3, 5):
+                    out["spline%d_%s_coefficients" % (order, scene)] = e.spline_coefficients(ca.IMG_DEF, order)
+            e.close()
+    return out
+
+
 def run_quadratic():
     import correlation_amd as ca
     out = {}
@@ -363,7 +385,8 @@ VARIANTS += [("outlier_g%d_cap%s" % (g, cap), {"LK_OUTLIER_GROUP": str(g), "LK_O
 VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (16, 64)]
 VARIANTS += [("field_walk%d" % w, {"LK_FIELD_WALK": str(w)}, run_field) for w in (0, 1)]
 VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
-             ("pattern", {}, run_pattern), ("znssd", {}, run_znssd), ("quadratic", {}, run_quadratic)]
+             ("pattern", {}, run_pattern), ("znssd", {}, run_znssd), ("quadratic", {}, run_quadratic),
+             ("spline", {}, run_spline)]
 VARIANTS += SOLVES
 
 
