@@ -206,6 +206,25 @@ class LkSplineConfig(C.Structure):
 
 assert C.sizeof(LkSplineConfig) == 32
 
+# weighted refinement (include/lk_engine.h: lk_refine_weighted); statuses ZN_*, sums ZN_SUMS
+LOG2E = 1.4426950408889634   # log2(e): inv = float32(LOG2E / (2 sigma_L^2)) is the window's scale
+
+
+class LkWeightedConfig(C.Structure):
+    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float),
+                ("lambda0", C.c_float), ("sigma", C.c_float), ("min_fraction", C.c_float), ("mask_rows", C.c_int),
+                ("mask_cols", C.c_int), ("reserved", C.c_int * 3)]
+
+
+# struct lk_weighted as a numpy record: ZNSSD_DTYPE's first 48 bytes, then the weights'
+WEIGHTED_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "iterations", "evaluations")] +
+                          [(k, np.float32) for k in ("zncc", "gain", "offset", "znssd", "zncc_seed", "shift", "lambda",
+                                                     "last_step")] +
+                          [("n_valid", np.int32)] +
+                          [(k, np.float32) for k in ("weight_sum", "n_eff", "centroid_dx", "centroid_dy")] +
+                          [("reserved", np.int32, (3,))])
+assert WEIGHTED_DTYPE.itemsize == 80 and C.sizeof(LkWeightedConfig) == 48
+
 # speckle quality (include/lk_engine.h: lk_pattern_quality, lk_suggest_subset)
 PATTERN_OK, PATTERN_TOO_FEW, PATTERN_FLAT, PATTERN_APERTURE, PATTERN_SATURATED = range(5)
 SUBSET_OK, SUBSET_NONE, SUBSET_BAD_POINT = range(3)
@@ -349,6 +368,9 @@ SYMBOLS = {
     "lk_spline_sample": (C.c_int, [_P, C.c_int, C.c_int, _F, C.c_int, _F]),
     "lk_spline_weights": (C.c_int, [C.c_int, C.c_float, _F, _F]),
     "lk_quadratic_step_from_sums": (C.c_int, [C.c_int, _P, C.c_float, _P, _P, _P, _P]),
+    "lk_refine_weighted": (C.c_int, [_P, C.POINTER(LkWeightedConfig), _P, _P, _F, _P, _P, _P]),
+    "lk_weight_window": (C.c_int, [C.c_float, C.c_float, C.c_float, _F]),
+    "lk_weighted_step_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_double, _P, C.c_float, _P, _P, _P, _P]),
     "lk_field_map": (C.c_int, [_P, C.POINTER(LkFieldMapConfig), _P, _P, _P, _P]),
     "lk_field_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_double, _P, C.c_int, _F, _I]),
     "lk_pattern_quality": (C.c_int, [_P, C.POINTER(LkPatternConfig), _P, _P, _P]),
@@ -581,6 +603,34 @@ def spline_weights(order, t):
         raise ValueError(f"lk_spline_weights: order {order} is not 3 or 5, or t is not finite")
     n = (int(order) or 5) + 1
     return w[:n], g[:n]
+
+
+def weight_window(inv, dx, dy):
+    """lk_weight_window (host, the kernel's function): the float32 window 2^-(r2 inv) at the offset (dx, dy), inv =
+    float32(LOG2E / (2 sigma^2))."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    w = np.zeros(1, np.float32)
+    if _compose_lib.lk_weight_window(float(inv), float(dx), float(dy), fptr(w)) != 0:
+        raise ValueError(f"lk_weight_window: inv {inv} is negative or not finite, or the offset is not finite")
+    return w[0]
+
+
+def weighted_step_from_sums(model, n_valid, N, sums, lam):
+    """lk_weighted_step_from_sums (host, the kernel's function): (status, delta [6], crit, gain, offset) of one sector of
+    n_valid samples of total weight N whose weighted sums, in the model's layout, are `sums`, at the damping `lam`."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.zeros(ZN_SUMS, np.float64)
+    flat = np.asarray(sums, np.float64).reshape(-1)
+    s[:len(flat)] = flat
+    delta, crit, go, status = np.zeros(6, np.float64), C.c_double(), np.zeros(2, np.float64), C.c_int32(-1)
+    if _compose_lib.lk_weighted_step_from_sums(int(model), int(n_valid), float(N), s.ctypes.data_as(_P), float(lam),
+                                               delta.ctypes.data_as(_P), C.byref(crit), go.ctypes.data_as(_P), C.byref(status)) != 0:
+        raise ValueError(f"lk_weighted_step_from_sums: bad model {model}, n_valid < 0, or a bad N or lambda")
+    return status.value, delta, crit.value, float(go[0]), float(go[1])
 
 
 def pattern_from_sums(n, sums9, mig_sum, noise_sigma=1.0, max_saturated=1.0):

@@ -378,6 +378,16 @@ struct LkSplineArgs {
   const float *coef;        // [zn.ev.drows][zn.ev.dcols]
 };
 
+// Weighted refinement (lk_weighted.hip, include/lk_engine.h: lk_refine_weighted): the ZNSSD pass's arguments (zn.out is not
+// used), the mask over the undeformed level image and the window.
+struct LkWeightedArgs {
+  LkZnssdArgs zn;
+  const uint8_t *mask;      // [zn.ev.urows][zn.ev.ucols], nonzero = use, or null: every pixel
+  struct lk_weighted *out;  // [S]
+  float inv;                // log2(e) / (2 sigma_L^2), or 0: no window
+  float min_fraction;
+};
+
 // Second-order refinement (lk_quadratic.hip, include/lk_engine.h: lk_refine_quadratic): the ZNSSD pass's loop on twelve
 // parameters; the engine's model only says how a seed is read and a record written.
 struct LkQuadraticArgs {

@@ -140,6 +140,10 @@ hipError_t lk_launch_spline_sample(int order, const float *coef, int rows, int c
 // as lk_launch_znssd, sampling a.coef
 hipError_t lk_launch_spline(const LkSplineArgs &a, int model, int order, int group, hipStream_t st);
 
+// ---- lk_weighted.hip: the weighted refinement (lk_refine_weighted)
+// as lk_launch_znssd, every sample under a.mask and the window of a.inv; the info goes to a.out
+hipError_t lk_launch_weighted(const LkWeightedArgs &a, int model, int interp, int group, hipStream_t st);
+
 // ---- lk_quadratic.hip: the second-order refinement (lk_refine_quadratic)
 // as lk_launch_znssd; the engine's model travels in a.model (the kernel has no model template)
 hipError_t lk_launch_quadratic(const LkQuadraticArgs &a, int interp, int group, hipStream_t st);

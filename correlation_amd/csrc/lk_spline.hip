@@ -225,7 +225,7 @@ template <int ORDER> struct ZnSplineSampler {
 
 template <int MODEL, int ORDER, int GROUP>
 __global__ void __launch_bounds__(GROUP <= 64 ? 256 : GROUP) lk_spline_kernel(LkSplineArgs a) {
-  lk_znssd_sector<MODEL, GROUP>(a.zn, ZnSplineSampler<ORDER>{(gptr<float>)a.coef});
+  lk_znssd_sector<MODEL, GROUP>(a.zn, ZnSplineSampler<ORDER>{(gptr<float>)a.coef}, LkZnUnitWeight{});
 }
 
 template <class F> hipError_t dispatch_order(int order, F &&f) {

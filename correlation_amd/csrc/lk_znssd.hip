@@ -15,7 +15,7 @@ template <int INTERP> struct ZnImageSampler {
 
 template <int MODEL, int INTERP, int GROUP>
 __global__ void __launch_bounds__(GROUP <= 64 ? 256 : GROUP) lk_znssd_kernel(LkZnssdArgs a) {
-  lk_znssd_sector<MODEL, GROUP>(a, ZnImageSampler<INTERP>{});
+  lk_znssd_sector<MODEL, GROUP>(a, ZnImageSampler<INTERP>{}, LkZnUnitWeight{});
 }
 
 } // namespace

@@ -24,13 +24,14 @@ struct LkZnCriterion {
   double crit, gain, offset, zncc;
 };
 
-// The criterion of n samples with these sums: 0, or the status that refuses them (LK_ZN_TOO_FEW, LK_ZN_FLAT - all four
-// numbers 0 - or LK_ZN_NEGATIVE, all four numbers filled).
-template <int P> __host__ __device__ inline int lk_znssd_criterion(int n, const double *sums, LkZnCriterion *out) {
+// The criterion of n samples of total weight N with these sums: 0, or the status that refuses them (LK_ZN_TOO_FEW, LK_ZN_FLAT
+// - all four numbers 0 - or LK_ZN_NEGATIVE, all four numbers filled).  n counts the samples that take part (the too-few
+// test); N stands where the unweighted formulas have (double)n: the sum of the weights (lk_refine_weighted, DESIGN.md
+// section 26).
+template <int P> __host__ __device__ inline int lk_znssd_criterion(int n, double N, const double *sums, LkZnCriterion *out) {
   out->crit = out->gain = out->offset = out->zncc = 0.0;
   if (n < P + 2)
     return LK_ZN_TOO_FEW;
-  const double N = (double)n;
   const double Sf = sums[0], Sg = sums[1], Sff = sums[2], Sgg = sums[3], Sfg = sums[4];
   const double qf = N * Sff, qg = N * Sgg;
   const double vf = qf - Sf * Sf, vg = qg - Sg * Sg, c = N * Sfg - Sf * Sg;
@@ -45,6 +46,10 @@ template <int P> __host__ __device__ inline int lk_znssd_criterion(int n, const 
   out->crit = rest > 0.0 ? rest : 0.0;
   return c > 0.0 ? 0 : LK_ZN_NEGATIVE;
 }
+// unit weights: N = n
+template <int P> __host__ __device__ inline int lk_znssd_criterion(int n, const double *sums, LkZnCriterion *out) {
+  return lk_znssd_criterion<P>(n, (double)n, sums, out);
+}
 
 // The criterion, and the Gauss-Newton step of ZNSSD with gain and offset eliminated, damped by lambda:
 //   A_kl = gain^2 (SHH_kl - SH_k SH_l / N) / N,  b_k = gain ((SHf_k - SH_k Sf / N) - gain (SHg_k - SH_k Sg / N)) / N,
@@ -52,16 +57,17 @@ template <int P> __host__ __device__ inline int lk_znssd_criterion(int n, const 
 // A is scaled to C = A_kl / sqrt(A_kk A_ll) - a diagonal of 1 + lambda - and factored as L D L^T without pivoting; a diagonal
 // entry of A that is not positive, or a pivot of C that is not above kLkUncMinPivot, gives LK_ZN_SINGULAR (delta zeros, the
 // criterion filled).  Returns 0 or the refusing status.  Fully unrolled: every index is a compile-time constant on the device.
+// n and N as for the criterion.
 template <int P>
-__host__ __device__ inline int lk_znssd_step(int n, const double *sums, double lambda, double *delta, LkZnCriterion *cr) {
+__host__ __device__ inline int lk_znssd_step(int n, double N, const double *sums, double lambda, double *delta, LkZnCriterion *cr) {
   using Y = LkZnLayout<P>;
 #pragma unroll
   for (int k = 0; k < P; ++k)
     delta[k] = 0.0;
-  const int refused = lk_znssd_criterion<P>(n, sums, cr);
+  const int refused = lk_znssd_criterion<P>(n, N, sums, cr);
   if (refused != 0)
     return refused;
-  const double N = (double)n, gain = cr->gain, Sf = sums[0], Sg = sums[1];
+  const double gain = cr->gain, Sf = sums[0], Sg = sums[1];
   const double gg = gain * gain;
   double A[P][P], b[P], root[P];
   {
@@ -131,6 +137,11 @@ __host__ __device__ inline int lk_znssd_step(int n, const double *sums, double l
     delta[i] = y[i] / root[i];
   return 0;
 }
+// unit weights: N = n
+template <int P>
+__host__ __device__ inline int lk_znssd_step(int n, const double *sums, double lambda, double *delta, LkZnCriterion *cr) {
+  return lk_znssd_step<P>(n, (double)n, sums, lambda, delta, cr);
+}
 
 // the weight of parameter k of a model with P parameters in the convergence test: 1 for the translations, the half-width of
 // a square subset of n samples for the gradient terms and the rotation (never below 1)
@@ -142,16 +153,20 @@ __host__ __device__ inline double lk_znssd_weight(int k, int P, int n) {
 }
 
 // Returns -1 for an unknown model (outputs untouched), else the status of lk_znssd_step; delta: 6 doubles, zeros behind P.
-inline int lk_znssd_step_from_sums_impl(int model, int n, const double *sums, double lambda, double *delta6, LkZnCriterion *cr) {
+inline int lk_znssd_step_from_sums_impl(int model, int n, double N, const double *sums, double lambda, double *delta6,
+                                        LkZnCriterion *cr) {
   if (model != LK_FM_U && model != LK_FM_UV && model != LK_FM_UVQ && model != LK_FM_UVUXUYVXVY)
     return -1;
   for (int k = 0; k < 6; ++k)
     delta6[k] = 0.0;
   switch (model) {
-  case LK_FM_U: return lk_znssd_step<1>(n, sums, lambda, delta6, cr);
-  case LK_FM_UV: return lk_znssd_step<2>(n, sums, lambda, delta6, cr);
-  case LK_FM_UVQ: return lk_znssd_step<3>(n, sums, lambda, delta6, cr);
-  case LK_FM_UVUXUYVXVY: return lk_znssd_step<6>(n, sums, lambda, delta6, cr);
+  case LK_FM_U: return lk_znssd_step<1>(n, N, sums, lambda, delta6, cr);
+  case LK_FM_UV: return lk_znssd_step<2>(n, N, sums, lambda, delta6, cr);
+  case LK_FM_UVQ: return lk_znssd_step<3>(n, N, sums, lambda, delta6, cr);
+  case LK_FM_UVUXUYVXVY: return lk_znssd_step<6>(n, N, sums, lambda, delta6, cr);
   default: return -1;
   }
+}
+inline int lk_znssd_step_from_sums_impl(int model, int n, const double *sums, double lambda, double *delta6, LkZnCriterion *cr) {
+  return lk_znssd_step_from_sums_impl(model, n, (double)n, sums, lambda, delta6, cr);
 }

@@ -1,6 +1,7 @@
 // lk_znssd_loop.hpp - the loop of the ZNSSD refinement, one body for the passes that differ in how the deformed image is
-// sampled: lk_znssd.hip (the engine's interpolator, lk_refine_znssd) and lk_spline.hip (a B-spline of
-// the prefiltered image, lk_refine_spline; section 25).  Device only.
+// sampled or in how its samples are weighted: lk_znssd.hip (the engine's interpolator, lk_refine_znssd; DESIGN.md section
+// 23), lk_spline.hip (a B-spline of the prefiltered image, lk_refine_spline; section 25) and lk_weighted.hip (the engine's
+// interpolator under a Gaussian window and a pixel mask, lk_refine_weighted; section 26).  Device only.
 //
 // One lane group refines one sector from its seed to the end, at the finest level the solve reaches: a 16-lane DPP row, a
 // wavefront or a 512-thread workgroup, chosen from the sector's level-0 sample count alone (lk_bw_group).  An evaluation is
@@ -65,11 +66,30 @@ __device__ __forceinline__ int zn_error_code(int status) {
   }
 }
 
+// The weight policy of the passes that give every sample the weight 1 (lk_znssd.hip, lk_spline.hip): nothing of a weight is
+// compiled into their kernels.  A policy with kWeighted = true (lk_weighted.hip) has
+//   float of(const SectorLevel &c, f32x2 q) const        the weight of sample q, >= 0; the same float wherever it is asked for
+//   bool too_few(int n_valid, int n) const               its own rule on top of n_valid < P + 2
+//   void store(int s, const lk_znssd &o, const LkZnWeightSums &w, int level) const      the info record in place of a.out[s]
+struct LkZnUnitWeight {
+  static constexpr bool kWeighted = false;
+};
+// what the prologue of a weighted sector leaves: the samples with w > 0, sum w, sum w^2, sum w dx, sum w dy (level-L pixels
+// about the committed centre)
+struct LkZnWeightSums {
+  int n_valid;
+  double sw, sww, swx, swy;
+};
+
 // The body of a kernel of THREADS = 256 (GROUP <= 64) or GROUP threads.  sample(c, xd, yd, g, gx, gy): the deformed image
-// and its gradient at a level-L position of the sector c, false where the sampler's window leaves the image.
-template <int MODEL, int GROUP, class SAMPLER> __device__ __forceinline__ void lk_znssd_sector(const LkZnssdArgs &a, const SAMPLER &sample) {
+// and its gradient at a level-L position of the sector c, false where the sampler's window leaves the image.  weight: the
+// policy above; with weights a sample of weight 0 is skipped before anything of it is read, every other term of the sums is
+// formed as without weights and multiplied by (double)w before it is added, and N = sum w stands for (double)n.
+template <int MODEL, int GROUP, class SAMPLER, class WEIGHT>
+__device__ __forceinline__ void lk_znssd_sector(const LkZnssdArgs &a, const SAMPLER &sample, const WEIGHT &weight) {
   constexpr int THREADS = GROUP <= 64 ? 256 : GROUP;
   constexpr int P = n_params(MODEL);
+  constexpr bool WEIGHTED = WEIGHT::kWeighted;
   using Y = LkZnLayout<P>;
   constexpr int NS = Y::N; // the sums and the flagged count
   __shared__ double lds[(GROUP > 64 ? GROUP / kWave : 1) * kZnLdsStride];
@@ -121,6 +141,50 @@ template <int MODEL, int GROUP, class SAMPLER> __device__ __forceinline__ void l
   best.crit = best.gain = best.offset = best.zncc = 0.0;
   float zncc_seed = 0.f;
   bool go = good;
+  // with weights, the prologue: one pass over the samples' weights alone, one reduction in the fixed order
+  [[maybe_unused]] LkZnWeightSums ws{0, 0.0, 0.0, 0.0, 0.0};
+  if constexpr (WEIGHTED) {
+    if (good) { // (uniform over the group, as everything the reduction leaves)
+      double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int k = lane; k < n; k += GROUP) {
+        const f32x2 q = sector_sample(c, k);
+        const float w = weight.of(c, q);
+        if (w > 0.f) {
+          const double wd = (double)w;
+          t[0] += 1.0;
+          t[1] += wd;
+          t[2] += wd * wd;
+          t[3] += wd * (double)(q.x - c.cx);
+          t[4] += wd * (double)(q.y - c.cy);
+        }
+      }
+      zn_reduce<GROUP>(t, lds);
+      if constexpr (GROUP > 64)
+        __syncthreads(); // (the first evaluation's reduction writes the slots these sums were read from)
+      ws.n_valid = (int)t[0];
+      ws.sw = t[1];
+      ws.sww = t[2];
+      ws.swx = t[3];
+      ws.swy = t[4];
+      if (ws.n_valid < P + 2 || weight.too_few(ws.n_valid, n)) { // nothing of the images is read
+        status = LK_ZN_TOO_FEW;
+        go = false;
+      }
+    }
+  }
+  // criterion and step of `sums`: n samples of weight 1, or the n_valid samples of total weight sum w
+  auto criterion = [&](const double *sums, LkZnCriterion *out) {
+    if constexpr (WEIGHTED)
+      return lk_znssd_criterion<P>(ws.n_valid, ws.sw, sums, out);
+    else
+      return lk_znssd_criterion<P>(n, sums, out);
+  };
+  auto step = [&](const double *sums, double lam, double *delta, LkZnCriterion *out) {
+    if constexpr (WEIGHTED)
+      return lk_znssd_step<P>(ws.n_valid, ws.sw, sums, lam, delta, out);
+    else
+      return lk_znssd_step<P>(n, sums, lam, delta, out);
+  };
   while (go) {
     double v[NS];
 #pragma unroll
@@ -128,6 +192,20 @@ template <int MODEL, int GROUP, class SAMPLER> __device__ __forceinline__ void l
       v[i] = 0.0;
     for (int k = lane; k < n; k += GROUP) {
       const f32x2 q = sector_sample(c, k);
+      [[maybe_unused]] double wd = 1.0;
+      if constexpr (WEIGHTED) {
+        const float w = weight.of(c, q);
+        if (!(w > 0.f))
+          continue; // not part of the sector: never sampled, never flagged
+        wd = (double)w;
+      }
+      // term, or with weights term times w (a rounded product), added to acc
+      auto add = [&](double &acc, double term) {
+        if constexpr (WEIGHTED)
+          acc += term * wd;
+        else
+          acc += term;
+      };
       float xd, yd, dx = 0.f, dy = 0.f;
       Warp<MODEL>::apply(q.x, q.y, c.cx, c.cy, p_try, xd, yd, dx, dy);
       const float f = sector_und_node(c, q);
@@ -143,20 +221,20 @@ template <int MODEL, int GROUP, class SAMPLER> __device__ __forceinline__ void l
       for (int i = 0; i < P; ++i)
         Hd[i] = (double)H[i];
       const double fd = (double)f, gd = (double)g;
-      v[0] += fd;
-      v[1] += gd;
-      v[2] += fd * fd; // (no contraction: a rounded product, then a rounded sum)
-      v[3] += gd * gd;
-      v[4] += fd * gd;
+      add(v[0], fd);
+      add(v[1], gd);
+      add(v[2], fd * fd); // (no contraction: a rounded product, then a rounded sum)
+      add(v[3], gd * gd);
+      add(v[4], fd * gd);
       int idx = 0;
 #pragma unroll
       for (int p1 = 0; p1 < P; ++p1) {
-        v[Y::H + p1] += Hd[p1];
-        v[Y::HF + p1] += Hd[p1] * fd;
-        v[Y::HG + p1] += Hd[p1] * gd;
+        add(v[Y::H + p1], Hd[p1]);
+        add(v[Y::HF + p1], Hd[p1] * fd);
+        add(v[Y::HG + p1], Hd[p1] * gd);
 #pragma unroll
         for (int p2 = p1; p2 < P; ++p2)
-          v[Y::HH + idx] += Hd[p1] * Hd[p2], ++idx;
+          add(v[Y::HH + idx], Hd[p1] * Hd[p2]), ++idx;
       }
     }
     zn_reduce<GROUP>(v, lds);
@@ -165,7 +243,7 @@ template <int MODEL, int GROUP, class SAMPLER> __device__ __forceinline__ void l
       LkZnCriterion cr;
       cr.crit = cr.gain = cr.offset = cr.zncc = 0.0;
       const bool flagged = v[Y::FLAGGED] != 0.0;
-      const int refused = flagged ? (int)LK_ZN_OUT_OF_IMAGE : lk_znssd_criterion<P>(n, v, &cr);
+      const int refused = flagged ? (int)LK_ZN_OUT_OF_IMAGE : criterion(v, &cr);
       bool done = false, keep = false;
       if (evals == 1) { // the seed
         keep = !flagged;
@@ -214,7 +292,7 @@ template <int MODEL, int GROUP, class SAMPLER> __device__ __forceinline__ void l
         ++trips;
         double delta[P];
         LkZnCriterion again;
-        if (lk_znssd_step<P>(n, kept, lambda, delta, &again) != 0) { // LK_ZN_SINGULAR: the kept sums passed the criterion
+        if (step(kept, lambda, delta, &again) != 0) { // LK_ZN_SINGULAR: the kept sums passed the criterion
           lambda = 10.0 * lambda;
           if (lambda >= 1e9) {
             status = LK_ZN_STALLED;
@@ -279,7 +357,10 @@ template <int MODEL, int GROUP, class SAMPLER> __device__ __forceinline__ void l
   o.lambda = good ? (float)lambda : 0.f;
   o.last_step = (float)last_step;
   o.reserved[0] = o.reserved[1] = o.reserved[2] = o.reserved[3] = 0;
-  a.out[s] = o;
+  if constexpr (WEIGHTED)
+    weight.store(s, o, ws, level);
+  else
+    a.out[s] = o;
   lk_result r;
   if (!good && !a.guess) {
     r = rec; // a bad seed record passes through
@@ -288,7 +369,12 @@ template <int MODEL, int GROUP, class SAMPLER> __device__ __forceinline__ void l
     for (int i = 0; i < 6; ++i)
       r.resultingParameters[i] = good ? (i < P ? back[i] : 0.f) : seed[i];
     r.chi = 0.f;
-    if (evaluated) { // sum (f - g)^2 / n from the kept sums: the forward evaluation's chi up to its float rounding
+    if constexpr (WEIGHTED) {
+      if (evaluated && evals > 0) { // sum w (f - g)^2 / sum w (a sector the prologue refused has no sums)
+        const double two = 2.0 * kept[4], ssd = (kept[2] - two) + kept[3];
+        r.chi = (float)((ssd > 0.0 ? ssd : 0.0) / ws.sw);
+      }
+    } else if (evaluated) { // sum (f - g)^2 / n from the kept sums: the forward evaluation's chi up to its float rounding
       const double two = 2.0 * kept[4], ssd = (kept[2] - two) + kept[3];
       r.chi = (float)((ssd > 0.0 ? ssd : 0.0) / (double)n);
     }

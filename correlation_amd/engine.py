@@ -614,6 +614,54 @@ class HipCorrelationEngine:
         """lk_spline_weights: the sampler's weights and derivative weights on the host (no engine needed)."""
         return _ffi.spline_weights(order, t)
 
+    # ---- weighted refinement: a pixel mask and a Gaussian window inside the ZNSSD sums ------------------------
+    def refine_weighted(self, records=None, guesses=None, sigma=0.0, mask=None, min_fraction=0.0, def_slot=-1, chi_max=0.0,
+                        max_iters=-1, precision=0.0, lambda0=0.0, return_sums=False):
+        """lk_refine_weighted: refine_znssd with the weight w = mask(node) * window(q - centre) on every sample.  sigma: the
+        standard deviation of the Gaussian window in level-0 pixels (0: no window); mask: [rows][cols] of the level-py_start
+        undeformed image, nonzero = use (None: every pixel); min_fraction: a sector with fewer than min_fraction * n_L
+        samples of positive weight is ZN_TOO_FEW.  The other arguments as refine_znssd.  Returns (records RESULT_DTYPE [S],
+        info WEIGHTED_DTYPE [S]) and, with return_sums, the 45 weighted double sums [S][45].  No engine state changes."""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if m.ndim != 2:
+                raise ValueError("refine_weighted: mask must be [rows][cols]")
+        cfg = _ffi.LkWeightedConfig(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
+                                    float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0), float(sigma),
+                                    float(min_fraction), m.shape[0] if m is not None else 0, m.shape[1] if m is not None else 0)
+        rec = g = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        if guesses is not None:
+            g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
+        out = np.zeros(self.n_sectors, RESULT_DTYPE)
+        info = np.zeros(self.n_sectors, _ffi.WEIGHTED_DTYPE)
+        sums = np.zeros((self.n_sectors, _ffi.ZN_SUMS), np.float64) if return_sums else None
+        self._chk(self.lib.lk_refine_weighted(self._h, C.byref(cfg), m.ctypes.data_as(C.c_void_p) if m is not None else None,
+                                              rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
+                                              _ffi.fptr(g) if g is not None else None, out.ctypes.data_as(C.c_void_p),
+                                              info.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p) if return_sums else None))
+        return (out, info, sums) if return_sums else (out, info)
+
+    def weighted_last(self):
+        """Bench hook: (device ms, the sectors the 16-, 64- and 512-lane groups took) of the last refine_weighted call."""
+        ms, cnt = C.c_float(), (C.c_int * 3)()
+        fn = self.lib.lk_internal_weighted_last
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        self._chk(fn(self._h, C.byref(ms), cnt))
+        return ms.value, tuple(cnt)
+
+    @staticmethod
+    def weight_window(inv, dx, dy):
+        """lk_weight_window: the kernel's window function on the host (no engine needed)."""
+        return _ffi.weight_window(inv, dx, dy)
+
+    @staticmethod
+    def weighted_step_from_sums(model, n_valid, N, sums, lam):
+        """lk_weighted_step_from_sums: the kernel's criterion and step for weighted sums on the host (no engine needed)."""
+        return _ffi.weighted_step_from_sums(model, n_valid, N, sums, lam)
+
     # ---- speckle quality: is the pattern good enough, how large must the subsets be ----------------------
     def pattern_quality(self, slot=_ffi.IMG_UND, grey_low=0, grey_high=255, noise_sigma=1.0, max_saturated=1.0,
                         return_sums=False):

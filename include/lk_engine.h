@@ -1174,6 +1174,84 @@ int lk_spline_sample(lk_engine *e, int slot, int order, const float *xy, int n, 
  * zeros behind them.  LK_ERROR_BAD_DOMAIN for a null pointer, an order that is not 0, 3 or 5, or a t that is not finite. */
 int lk_spline_weights(int order, float t, float *w6, float *g6);
 
+/* ---- weighted refinement: subsets that stop at an edge, a window that weights the centre ------ */
+/* Every other sub-pixel solve of the engine gives all samples of a sector the same weight.  A sector that straddles the
+ * specimen's edge, a hole's rim, an open crack or a highlight then contains pixels that do not move with the material, and
+ * the solve is biased by as much as they disagree; and under a curved displacement the affine model's error grows with the
+ * second moment of the subset.  lk_refine_weighted is lk_refine_znssd with a weight per sample inside the ZNSSD sums: a
+ * pixel mask over the undeformed image times a Gaussian window about the committed centre, in a kernel of its own
+ * (csrc/lk_weighted.hip).  What is not said here is as for lk_refine_znssd: seeds, level, walk, lane
+ * groups, warp, the engine's interpolator, loop, statuses (LK_ZN_*), the record layout, refusals, modes.
+ *   weight    of the sample q of a sector with the committed centre (cx, cy) at level L = py_start: w = m g.
+ *             m = 1 without a mask, or where the mask byte at the sample's undeformed node - the node f is read at,
+ *             ((int)(x + 0.5f), (int)(y + 0.5f)) - is nonzero; else 0.  g = 1 for sigma == 0, else the window below at
+ *             (q.x - cx, q.y - cy) with sigma_L = sigma 2^-L.  Rectangles and sample lists alike.
+ *   window    lk_weight_window (one function for the kernel and the host, csrc/lk_weighted.hpp), in float:
+ *             r2 = fma(dy, dy, dx dx), t = r2 inv with inv = (float)(log2(e) / (2 sigma_L^2)) formed once on the host in
+ *             double; the window is 2^-t: k = (int)(t + 0.5f), x = t - k, 2^-x by the Taylor polynomial of degree 7 of
+ *             exp(-x ln 2), every coefficient the float nearest (-ln 2)^j / j!, by Horner's rule with one fused multiply-add
+ *             per power, then ldexpf(.., -k).  t >= 126: 0.  No library exponential: host and device give the same bits.
+ *             Within 1e-6 relative of exp(-r^2 / (2 sigma^2)) in double over the subset the window is made for, |dx|,
+ *             |dy| <= 3 sigma (the float rounding of t alone is a relative 2^-23 t ln 2 of the result).
+ *   prologue  per sector, before the loop, one pass over the weights and one reduction in the fixed order of the sums:
+ *             n_valid = the samples with w > 0, Sw = sum w, Sww = sum w^2, sum w dx, sum w dy (dx, dy in float as above;
+ *             products and sums in double).  N = Sw; n_eff = Sw^2 / Sww; the centroid offset = (sum w d / Sw) 2^L.
+ *             n_valid < P + 2, or n_valid < min_fraction n_L (in double): LK_ZN_TOO_FEW - no pixel of either image is read,
+ *             evaluations = 0, floats and sums 0 (weight_sum, n_eff and the centroid are filled; all 0 for n_valid = 0).
+ *   sums      a sample with w == 0 is skipped before anything of it is read: it is never sampled and never flagged, so a
+ *             mask over the columns whose warped positions leave the deformed image rescues a sector that is
+ *             LK_ZN_OUT_OF_IMAGE as a whole.  Every other term of lk_refine_znssd's 45 sums is formed exactly as there,
+ *             then multiplied by (double)w - a rounded product - then added; the flagged count is not weighted.  sums_out
+ *             is [S][45] in the same layout.  With every w = 1 (sigma == 0 and no mask, or a mask of ones) the sums, and
+ *             with them the records and the first 48 bytes of the info, are lk_refine_znssd's bytes.
+ *   step      lk_weighted_step_from_sums: the arithmetic of lk_znssd_step_from_sums with N = Sw in place of (double)n and
+ *             n_valid in the too-few test.  The weights of the convergence test keep n_L, the full count: the test bounds
+ *             how far any sample of the support moved.
+ *   records   as lk_refine_znssd's, with chi = (Sff - 2 Sfg + Sgg) / Sw of the kept sums; the centre stays the committed
+ *             one and numberOfPoints the level-0 count: the solve reports the affine map at the committed centre, and
+ *             centroid_dx, centroid_dy tell how far the centroid of the data lies from it.
+ *   errors    as lk_refine_znssd, with this function's name in the messages; and a sigma that is negative or not finite
+ *             (or so small that inv is not a finite float); min_fraction outside [0, 1]; mask dimensions that are not
+ *             those of the level-py_start undeformed image; a mask without dimensions, or dimensions without a mask.
+ *   defaults  as lk_refine_znssd.
+ *   scope     as lk_refine_znssd; the engine's interpolator only - the B-spline sampler and the twelve-parameter model with
+ *             weights are follow-ups; no batch solve, backward solve or sequence window gets weights; the mask lives on the
+ *             undeformed configuration only (no mask on the deformed image).  The mask is uploaded by every call: nothing
+ *             is cached that could go stale. */
+typedef struct lk_weighted_config {
+  int def_slot;       /* the words and defaults of lk_znssd_config */
+  float chi_max;
+  int max_iters;
+  float precision;
+  float lambda0;
+  float sigma;        /* Gaussian window, standard deviation in level-0 pixels; 0: no window (w = 1) */
+  float min_fraction; /* in [0, 1]; a sector with n_valid < min_fraction * n_L is LK_ZN_TOO_FEW; 0: the P + 2 rule alone */
+  int mask_rows, mask_cols;   /* of `mask`: the level-py_start undeformed image's; 0, 0 with mask == NULL */
+  int reserved[3];    /* must be 0 */
+} lk_weighted_config;
+struct lk_weighted {  /* 80 bytes, one per sector: struct lk_znssd's first 48 bytes, then the weights' */
+  int32_t n_points, status, iterations, evaluations;   /* status: LK_ZN_*; n_points = n_L */
+  float zncc, gain, offset, znssd;     /* as struct lk_znssd, of the weighted sums */
+  float zncc_seed, shift, lambda, last_step;
+  int32_t n_valid;                     /* samples with w > 0 */
+  float weight_sum, n_eff;             /* Sw; Sw^2 / Sww */
+  float centroid_dx, centroid_dy;      /* centroid of the weights - committed centre, level-0 pixels.  Unit weights: exactly
+                                        * 0 for a rectangle; for a sample list the committed centre is the float32 nearest
+                                        * the samples' mean, so that rounding is left (below one float32 step of the centre) */
+  int32_t reserved[3];
+};
+/* mask: host [mask_rows][mask_cols] bytes, nonzero = use, or NULL.  records, guesses, records_out, sums_out: as
+ * lk_refine_znssd; info_out: [S] or NULL (not both outputs).  Synchronous.  Changes no engine state. */
+int lk_refine_weighted(lk_engine *e, const lk_weighted_config *cfg, const uint8_t *mask, const lk_result *records,
+                       const float *guesses, lk_result *records_out, struct lk_weighted *info_out, double *sums_out);
+/* the kernel's window function on the host: *w = the window at (dx, dy) for inv = log2(e) / (2 sigma^2).
+ * LK_ERROR_BAD_DOMAIN for a null pointer, an inv that is negative or not finite, or an offset that is not finite. */
+int lk_weight_window(float inv, float dx, float dy, float *w);
+/* lk_znssd_step_from_sums for n_valid samples of total weight N (N = n_valid gives its bits).  LK_ERROR_BAD_DOMAIN also for
+ * an N that is negative or not finite. */
+int lk_weighted_step_from_sums(int model, int n_valid, double N, const double *sums, float lambda, double *delta6,
+                               double *crit, double *gain_offset2, int32_t *status);
+
 /* ---- field map: dense displacement and strain maps on a regular grid of nodes ---------------- */
 /* lk_field_map gives the full-field picture a DIC user looks at first: u, v, the gradients, the strain tensor and its
  * principal values on a regular grid of nodes - every pixel, or every stride-th - drawn in the reference image or over the

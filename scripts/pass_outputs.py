@@ -257,6 +257,29 @@ def run_spline():
     return out
 
 
+def run_weighted():
+    import correlation_amd as ca
+    out = {}
+    mask = np.ones((256, 256), np.uint8)
+    mask[:, 100:108] = 0
+    mask[30:34, :] = 0
+    for scene in ("mix", "grid"):
+        for model, interp, name in ((ca.FM_UVUXUYVXVY, ca.IM_BICUBIC, "affine_bicubic"), (ca.FM_UV, ca.IM_BILINEAR, "uv_bilinear"),
+                                    (ca.FM_UVQ, ca.IM_BICUBIC_SEPARABLE, "uvq_separable"), (ca.FM_U, ca.IM_BICUBIC, "u_bicubic")):
+            e, rec = solved(scene, model, interp)
+            g = np.zeros((e.n_sectors, 6), np.float32)
+            g[:, :2] = TRUTH[:2]
+            for seeds, kw in (("unit", dict(records=rec)), ("window", dict(guesses=g, sigma=3.0)), ("mask", dict(guesses=g, mask=mask)),
+                              ("both", dict(records=rec, sigma=3.0, mask=mask, min_fraction=0.5))):
+                refined, info, sums = e.refine_weighted(return_sums=True, **kw)
+                tag = "weighted_%s_%s_%s" % (scene, name, seeds)
+                out.update(fields(tag + ".records", refined))
+                out.update(fields(tag, info))
+                out[tag + ".sums"] = sums
+            e.close()
+    return out
+
+
 def run_quadratic():
     import correlation_amd as ca
     out = {}
@@ -386,7 +409,7 @@ VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (
 VARIANTS += [("field_walk%d" % w, {"LK_FIELD_WALK": str(w)}, run_field) for w in (0, 1)]
 VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
              ("pattern", {}, run_pattern), ("znssd", {}, run_znssd), ("quadratic", {}, run_quadratic),
-             ("spline", {}, run_spline)]
+             ("spline", {}, run_spline), ("weighted", {}, run_weighted)]
 VARIANTS += SOLVES
 
 
