@@ -30,6 +30,7 @@ from ._ffi import (ZN_BAD_SEED, ZN_CONVERGED, ZN_FLAT, ZN_MAX_ITERS, ZN_NEGATIVE
 from ._ffi import QD_PARAMS, QD_SUMS, QUADRATIC_DTYPE, quadratic_step_from_sums  # noqa: F401
 from ._ffi import spline_weights  # noqa: F401
 from ._ffi import WEIGHTED_DTYPE, weight_window, weighted_step_from_sums  # noqa: F401
+from ._ffi import COMPOSED_DTYPE, composed_step_from_sums  # noqa: F401
 from ._ffi import (PATTERN_APERTURE, PATTERN_DTYPE, PATTERN_FLAT, PATTERN_MAX_HALF, PATTERN_OK, PATTERN_SATURATED,  # noqa: F401
                    PATTERN_SUMS, PATTERN_TOO_FEW, SUBSET_BAD_POINT, SUBSET_DTYPE, SUBSET_NONE, SUBSET_OK, pattern_from_sums)
 from ._ffi import (FIELD_ALL, FIELD_BISQUARE, FIELD_CHANNELS, FIELD_DEFORMED, FIELD_DEGENERATE, FIELD_E1, FIELD_E2,  # noqa: F401

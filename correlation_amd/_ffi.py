@@ -225,6 +225,24 @@ WEIGHTED_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "iterat
                           [("reserved", np.int32, (3,))])
 assert WEIGHTED_DTYPE.itemsize == 80 and C.sizeof(LkWeightedConfig) == 48
 
+
+# composed refinement (include/lk_engine.h: lk_refine_composed); statuses ZN_*, sums ZN_SUMS (order 1) or QD_SUMS (order 2)
+class LkComposedConfig(C.Structure):
+    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float),
+                ("lambda0", C.c_float), ("order", C.c_int), ("sampler", C.c_int), ("sigma", C.c_float),
+                ("min_fraction", C.c_float), ("mask_rows", C.c_int), ("mask_cols", C.c_int), ("reserved", C.c_int * 5)]
+
+
+# struct lk_composed as a numpy record: QUADRATIC_DTYPE up to bend, then WEIGHTED_DTYPE's words of the weights
+COMPOSED_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "iterations", "evaluations")] +
+                          [("p", np.float32, (12,))] +
+                          [(k, np.float32) for k in ("zncc", "gain", "offset", "znssd", "zncc_seed", "shift", "lambda",
+                                                     "last_step", "bend")] +
+                          [("n_valid", np.int32)] +
+                          [(k, np.float32) for k in ("weight_sum", "n_eff", "centroid_dx", "centroid_dy")] +
+                          [("reserved", np.int32, (2,))])
+assert COMPOSED_DTYPE.itemsize == 128 and C.sizeof(LkComposedConfig) == 64
+
 # speckle quality (include/lk_engine.h: lk_pattern_quality, lk_suggest_subset)
 PATTERN_OK, PATTERN_TOO_FEW, PATTERN_FLAT, PATTERN_APERTURE, PATTERN_SATURATED = range(5)
 SUBSET_OK, SUBSET_NONE, SUBSET_BAD_POINT = range(3)
@@ -371,6 +389,8 @@ SYMBOLS = {
     "lk_refine_weighted": (C.c_int, [_P, C.POINTER(LkWeightedConfig), _P, _P, _F, _P, _P, _P]),
     "lk_weight_window": (C.c_int, [C.c_float, C.c_float, C.c_float, _F]),
     "lk_weighted_step_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_double, _P, C.c_float, _P, _P, _P, _P]),
+    "lk_refine_composed": (C.c_int, [_P, C.POINTER(LkComposedConfig), _P, _P, _F, _F, _P, _P, _P]),
+    "lk_composed_step_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, _P, C.c_float, _P, _P, _P, _P]),
     "lk_field_map": (C.c_int, [_P, C.POINTER(LkFieldMapConfig), _P, _P, _P, _P]),
     "lk_field_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_double, _P, C.c_int, _F, _I]),
     "lk_pattern_quality": (C.c_int, [_P, C.POINTER(LkPatternConfig), _P, _P, _P]),
@@ -630,6 +650,23 @@ def weighted_step_from_sums(model, n_valid, N, sums, lam):
     if _compose_lib.lk_weighted_step_from_sums(int(model), int(n_valid), float(N), s.ctypes.data_as(_P), float(lam),
                                                delta.ctypes.data_as(_P), C.byref(crit), go.ctypes.data_as(_P), C.byref(status)) != 0:
         raise ValueError(f"lk_weighted_step_from_sums: bad model {model}, n_valid < 0, or a bad N or lambda")
+    return status.value, delta, crit.value, float(go[0]), float(go[1])
+
+
+def composed_step_from_sums(order, model, n_valid, N, sums, lam):
+    """lk_composed_step_from_sums (host, the kernels' function): (status, delta [12], crit, gain, offset) of one sector of
+    n_valid samples of total weight N whose weighted sums are `sums` - the model's layout, ZN_SUMS or fewer, with order 1
+    (delta: zeros behind P); QD_SUMS with order 2, where the model plays no part - at the damping `lam`."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.zeros(QD_SUMS, np.float64)
+    flat = np.asarray(sums, np.float64).reshape(-1)
+    s[:len(flat)] = flat
+    delta, crit, go, status = np.zeros(QD_PARAMS, np.float64), C.c_double(), np.zeros(2, np.float64), C.c_int32(-1)
+    if _compose_lib.lk_composed_step_from_sums(int(order), int(model), int(n_valid), float(N), s.ctypes.data_as(_P), float(lam),
+                                               delta.ctypes.data_as(_P), C.byref(crit), go.ctypes.data_as(_P), C.byref(status)) != 0:
+        raise ValueError(f"lk_composed_step_from_sums: bad order {order} or model {model}, n_valid < 0, or a bad N or lambda")
     return status.value, delta, crit.value, float(go[0]), float(go[1])
 
 

@@ -402,6 +402,23 @@ struct LkQuadraticArgs {
   float chi_max, precision, lambda0;
 };
 
+// Composed refinement (lk_composed.hip, include/lk_engine.h: lk_refine_composed).  Order 1: the weighted pass's arguments -
+// wt.out takes the info, widened to struct lk_composed afterwards - and the coefficient image of a spline sampler.
+struct LkComposedFirstArgs {
+  LkWeightedArgs wt;
+  const float *coef;        // [wt.zn.ev.drows][wt.zn.ev.dcols]
+};
+// Order 2: the second-order pass's arguments (qd.out is not used), the coefficient image of a spline sampler or null, the
+// mask and the window as LkWeightedArgs.
+struct LkComposedSecondArgs {
+  LkQuadraticArgs qd;
+  const float *coef;        // [qd.ev.drows][qd.ev.dcols] or null: the engine's interpolator
+  const uint8_t *mask;      // [qd.ev.urows][qd.ev.ucols], nonzero = use, or null: every pixel
+  struct lk_composed *out;  // [S]
+  float inv;                // log2(e) / (2 sigma_L^2), or 0: no window
+  float min_fraction;
+};
+
 // Residual map (lk_residual.hip, include/lk_engine.h: lk_residual_map): what a pixel needs of a sector, 48 bytes.
 struct LkMapSector {
   float cx0, cy0; // level-0 centre; cx0 = NaN for a sector that is not good (it then fails the distance test by itself)

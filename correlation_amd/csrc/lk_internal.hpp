@@ -87,7 +87,7 @@ struct LkPassSlot {
   virtual ~LkPassSlot() = default;
 };
 enum LkPass { LK_PASS_RESEED, LK_PASS_STRAIN, LK_PASS_UNCERTAINTY, LK_PASS_OUTLIER, LK_PASS_TRACK, LK_PASS_RESIDUAL, LK_PASS_PATTERN,
-              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COUNT };
+              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_COUNT };
 LkPassSlot **lk_internal_pass_slot(lk_engine *e, int which);
 
 // What a post-processing pass reads of the engine (lk_strain_field, lk_parameter_uncertainty, lk_flag_outliers,
@@ -156,4 +156,6 @@ int lk_internal_quadratic_last(lk_engine *e, float *device_ms, int *count3);
 int lk_internal_spline_last(lk_engine *e, float *device_ms, int *count3, float *build_ms);
 // lk_refine_weighted: as lk_internal_znssd_last
 int lk_internal_weighted_last(lk_engine *e, float *device_ms, int *count3);
+// lk_refine_composed: as lk_internal_weighted_last; the time covers the coefficient image of a spline sampler
+int lk_internal_composed_last(lk_engine *e, float *device_ms, int *count3);
 }

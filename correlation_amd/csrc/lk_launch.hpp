@@ -148,6 +148,15 @@ hipError_t lk_launch_weighted(const LkWeightedArgs &a, int model, int interp, in
 // as lk_launch_znssd; the engine's model travels in a.model (the kernel has no model template)
 hipError_t lk_launch_quadratic(const LkQuadraticArgs &a, int interp, int group, hipStream_t st);
 
+// ---- lk_composed.hip: the composed refinement (lk_refine_composed)
+// order 1 under a spline sampler (spline: 3 or 5); under the engine's interpolator the call launches lk_launch_weighted
+hipError_t lk_launch_composed_first(const LkComposedFirstArgs &a, int model, int spline, int group, hipStream_t st);
+// order 2; spline: 3 or 5, or 0: the interpolator `interp`
+hipError_t lk_launch_composed_second(const LkComposedSecondArgs &a, int interp, int spline, int group, hipStream_t st);
+// a thread per sector: the info of a first-order call and its records -> struct lk_composed (n_par: the engine model's P)
+hipError_t lk_launch_composed_info(const struct lk_weighted *in, const lk_result *rec, int n_par, int n, struct lk_composed *out,
+                                   hipStream_t st);
+
 // ---- lk_pattern.hip: speckle quality (lk_pattern_quality, lk_suggest_subset)
 // group: 16, 64 or 512 lanes per sector (lk_bw_group of the level-0 sample count); a.ev.order lists that group's sectors
 hipError_t lk_launch_pattern(const LkPatternArgs &a, int group, hipStream_t st);

@@ -55,16 +55,19 @@ constexpr int kLkQdWork = 5 * kLkQdParams + kLkQdTri;
 // scaling to a diagonal of 1 + lambda, unpivoted L D L^T and pivot rule - on the twelve parameters, whose SH, SHH, SHf, SHg
 // are expanded from the 88 sums on the way.  Loops over `work` (kLkQdWork doubles) instead of lk_znssd_step's unrolled
 // register arrays: twice 144 doubles do not fit into a lane's registers.  delta: 12 doubles, zeros unless 0 is returned.
-__host__ __device__ inline int lk_quadratic_step(int n, const double *sums, double lambda, double *delta, LkZnCriterion *cr, double *work) {
+// n and N as for lk_znssd_criterion: the samples that take part, and their total weight where the unweighted formulas have
+// (double)n (lk_refine_composed).
+__host__ __device__ inline int lk_quadratic_step(int n, double N, const double *sums, double lambda, double *delta, LkZnCriterion *cr,
+                                                 double *work) {
   constexpr int P = kLkQdParams;
   using Y = LkQdLayout;
 #pragma unroll 1
   for (int k = 0; k < P; ++k)
     delta[k] = 0.0;
-  const int refused = lk_znssd_criterion<P>(n, sums, cr);
+  const int refused = lk_znssd_criterion<P>(n, N, sums, cr);
   if (refused != 0)
     return refused;
-  const double N = (double)n, gain = cr->gain, Sf = sums[0], Sg = sums[1];
+  const double gain = cr->gain, Sf = sums[0], Sg = sums[1];
   const double gg = gain * gain;
   double *SH = work, *b = SH + P, *root = b + P, *D = root + P, *y = D + P, *C = y + P; // C(i, j), j <= i, at i (i + 1) / 2 + j
   bool singular = false;
@@ -153,6 +156,10 @@ __host__ __device__ inline int lk_quadratic_step(int n, const double *sums, doub
   for (int i = 0; i < P; ++i)
     delta[i] = y[i] / root[i];
   return 0;
+}
+// unit weights: N = n
+__host__ __device__ inline int lk_quadratic_step(int n, const double *sums, double lambda, double *delta, LkZnCriterion *cr, double *work) {
+  return lk_quadratic_step(n, (double)n, sums, lambda, delta, cr, work);
 }
 
 // the weight of parameter k in the convergence test, with h = max(1, sqrt(n) / 2), the half-width of a square subset of n

@@ -10,9 +10,10 @@
 // recursion state in registers from tile to tile - forward for the causal sweep, backward for the anticausal one - and the
 // wavefront stores the tile as it loaded it.  The tile's row stride is 65 dwords, so the lanes of the filter step (bank
 // (65 r + k) mod 32) and of the load step (consecutive dwords) meet no bank twice.
-// The sampler evaluates the spline and its gradient separably, like LK_IM_BICUBIC_SEPARABLE.  The pass kernel is
-// lk_znssd_loop.hpp with that sampler.
+// The sampler (spline_sample and ZnSplineSampler, lk_sector_policies.hpp, where lk_composed.hip finds them too) evaluates
+// the spline and its gradient separably, like LK_IM_BICUBIC_SEPARABLE.  The pass kernel is lk_znssd_loop.hpp with that sampler.
 #include "lk_launch.hpp"
+#include "lk_sector_policies.hpp" // spline_sample, ZnSplineSampler
 #include "lk_spline.hpp"
 #include "lk_znssd_loop.hpp"
 
@@ -171,42 +172,6 @@ template <int ORDER> __global__ void __launch_bounds__(64) lk_spline_cols_kernel
   }
 }
 
-// The spline of the coefficients and its gradient at (xd, yd); false where the window of ORDER + 1 nodes a side is not
-// inside the image by the bicubic's rule (order 3) or one pixel further in (order 5).  Per image row a value and an
-// x-derivative, each a chain of fused multiply-adds from the left; the rows are folded into W, Wx, Wy as they arrive.
-template <int ORDER>
-__device__ __forceinline__ bool spline_sample(gptr<float> coef, int rows, int cols, float xd, float yd, float &W, float &Wx, float &Wy) {
-  constexpr int NT = ORDER + 1, L = ORDER / 2;
-  if (!(xd > (float)L && yd > (float)L && xd < (float)cols - (float)(L + 1) && yd < (float)rows - (float)(L + 1)))
-    return false;
-  const int ix = (int)xd, iy = (int)yd;
-  const float tx = xd - (float)ix, ty = yd - (float)iy;
-  float wx[NT], gx[NT], wy[NT], gy[NT];
-  lk_spline_weights<ORDER>(tx, wx, gx);
-  lk_spline_weights<ORDER>(ty, wy, gy);
-  gptr<float> base = coef + (size_t)(iy - L) * (size_t)cols + (size_t)(ix - L);
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    gptr<float> r = base + (size_t)j * (size_t)cols;
-    float v = wx[0] * r[0], d = gx[0] * r[0];
-#pragma unroll
-    for (int i = 1; i < NT; ++i) {
-      v = __builtin_fmaf(wx[i], r[i], v);
-      d = __builtin_fmaf(gx[i], r[i], d);
-    }
-    if (j == 0) {
-      W = wy[0] * v;
-      Wx = wy[0] * d;
-      Wy = gy[0] * v;
-    } else {
-      W = __builtin_fmaf(wy[j], v, W);
-      Wx = __builtin_fmaf(wy[j], d, Wx);
-      Wy = __builtin_fmaf(gy[j], v, Wy);
-    }
-  }
-  return true;
-}
-
 template <int ORDER> __global__ void lk_spline_sample_kernel(const float *coef, int rows, int cols, const float2 *pts, int n, float4 *out) {
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (k >= n)
@@ -215,13 +180,6 @@ template <int ORDER> __global__ void lk_spline_sample_kernel(const float *coef, 
   const bool ok = spline_sample<ORDER>((gptr<float>)coef, rows, cols, pts[k].x, pts[k].y, W, Wx, Wy);
   out[k] = ok ? make_float4(W, Wx, Wy, 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
-
-template <int ORDER> struct ZnSplineSampler {
-  gptr<float> coef; // [drows][dcols] of the sector's deformed level image
-  __device__ __forceinline__ bool operator()(const SectorLevel &c, float xd, float yd, float &g, float &gx, float &gy) const {
-    return spline_sample<ORDER>(coef, c.drows, c.dcols, xd, yd, g, gx, gy);
-  }
-};
 
 template <int MODEL, int ORDER, int GROUP>
 __global__ void __launch_bounds__(GROUP <= 64 ? 256 : GROUP) lk_spline_kernel(LkSplineArgs a) {

@@ -662,6 +662,53 @@ class HipCorrelationEngine:
         """lk_weighted_step_from_sums: the kernel's criterion and step for weighted sums on the host (no engine needed)."""
         return _ffi.weighted_step_from_sums(model, n_valid, N, sums, lam)
 
+    # ---- composed refinement: model order, sampler and weights chosen independently ---------------------------
+    def refine_composed(self, records=None, guesses=None, second=None, order=2, sampler=0, sigma=0.0, mask=None, min_fraction=0.0,
+                        def_slot=-1, chi_max=0.0, max_iters=-1, precision=0.0, lambda0=0.0, return_sums=False):
+        """lk_refine_composed: order 1 (the engine's model, refine_znssd's parameters) or 2 (refine_quadratic's twelve),
+        sampler 0 (the engine's interpolator), 3 or 5 (refine_spline's cubic or quintic B-spline), and refine_weighted's
+        sigma, mask and min_fraction, each chosen independently.  second: [S][6] second-order seeds, order 2 only.  Returns
+        (records RESULT_DTYPE [S], info COMPOSED_DTYPE [S]) and, with return_sums, the weighted double sums [S][45] (order 1)
+        or [S][88] (order 2).  No engine state changes."""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if m.ndim != 2:
+                raise ValueError("refine_composed: mask must be [rows][cols]")
+        cfg = _ffi.LkComposedConfig(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
+                                    float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0), int(order),
+                                    int(sampler), float(sigma), float(min_fraction), m.shape[0] if m is not None else 0,
+                                    m.shape[1] if m is not None else 0)
+        rec = g = g2 = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
+        if guesses is not None:
+            g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
+        if second is not None:
+            g2 = np.ascontiguousarray(second, np.float32).reshape(self.n_sectors, 6)
+        out = np.zeros(self.n_sectors, RESULT_DTYPE)
+        info = np.zeros(self.n_sectors, _ffi.COMPOSED_DTYPE)
+        sums = np.zeros((self.n_sectors, _ffi.QD_SUMS if int(order) == 2 else _ffi.ZN_SUMS), np.float64) if return_sums else None
+        self._chk(self.lib.lk_refine_composed(self._h, C.byref(cfg), m.ctypes.data_as(C.c_void_p) if m is not None else None,
+                                              rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
+                                              _ffi.fptr(g) if g is not None else None, _ffi.fptr(g2) if g2 is not None else None,
+                                              out.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p),
+                                              sums.ctypes.data_as(C.c_void_p) if return_sums else None))
+        return (out, info, sums) if return_sums else (out, info)
+
+    def composed_last(self):
+        """Bench hook: (device ms, the sectors the 16-, 64- and 512-lane groups took) of the last refine_composed call."""
+        ms, cnt = C.c_float(), (C.c_int * 3)()
+        fn = self.lib.lk_internal_composed_last
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        self._chk(fn(self._h, C.byref(ms), cnt))
+        return ms.value, tuple(cnt)
+
+    @staticmethod
+    def composed_step_from_sums(order, model, n_valid, N, sums, lam):
+        """lk_composed_step_from_sums: the kernels' criterion and step of either order on the host (no engine needed)."""
+        return _ffi.composed_step_from_sums(order, model, n_valid, N, sums, lam)
+
     # ---- speckle quality: is the pattern good enough, how large must the subsets be ----------------------
     def pattern_quality(self, slot=_ffi.IMG_UND, grey_low=0, grey_high=255, noise_sigma=1.0, max_saturated=1.0,
                         return_sums=False):

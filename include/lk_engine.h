@@ -1149,8 +1149,8 @@ int lk_quadratic_step_from_sums(int n, const double *sums88, float lambda, doubl
  *   errors    as lk_refine_znssd, with this function's name in the messages; and an order that is not 0, 3 or 5; a level
  *             image with a side below 8.
  *   defaults  as lk_refine_znssd; order 0 is 5.
- *   scope     as lk_refine_znssd.  lk_refine_quadratic keeps the engine's interpolator: giving it this sampler is a
- *             follow-up.  The batch solve, the backward solve and the sequence windows keep theirs too. */
+ *   scope     as lk_refine_znssd.  lk_refine_quadratic keeps the engine's interpolator: lk_refine_composed gives it this
+ *             sampler.  The batch solve, the backward solve and the sequence windows keep theirs too. */
 typedef struct lk_spline_config {
   int def_slot;       /* the words and defaults of lk_znssd_config */
   float chi_max;
@@ -1215,7 +1215,7 @@ int lk_spline_weights(int order, float t, float *w6, float *g6);
  *             those of the level-py_start undeformed image; a mask without dimensions, or dimensions without a mask.
  *   defaults  as lk_refine_znssd.
  *   scope     as lk_refine_znssd; the engine's interpolator only - the B-spline sampler and the twelve-parameter model with
- *             weights are follow-ups; no batch solve, backward solve or sequence window gets weights; the mask lives on the
+ *             weights are lk_refine_composed's; no batch solve, backward solve or sequence window gets weights; the mask lives on the
  *             undeformed configuration only (no mask on the deformed image).  The mask is uploaded by every call: nothing
  *             is cached that could go stale. */
 typedef struct lk_weighted_config {
@@ -1251,6 +1251,76 @@ int lk_weight_window(float inv, float dx, float dy, float *w);
  * an N that is negative or not finite. */
 int lk_weighted_step_from_sums(int model, int n_valid, double N, const double *sums, float lambda, double *delta6,
                                double *crit, double *gain_offset2, int32_t *status);
+
+/* ---- composed refinement: model order, sampler and weights chosen independently --------------- */
+/* lk_refine_quadratic, lk_refine_spline and lk_refine_weighted each give lk_refine_znssd one more capability: a model that
+ * bends, a sampler without the bicubic's phase error, weights with a mask.  lk_refine_composed gives them together: next to
+ * a hole a subset needs the mask AND the model that bends, and a strain map without bands needs the spline sampler under
+ * whichever model and weights were chosen.  The kernels are the two shared loop bodies with the samplers and the weight
+ * policy of the four passes (csrc/lk_composed.hip).  Every rule is the one of the pass whose option is
+ * chosen; what is not said here is said there.
+ *   order     1: the engine's model, lk_refine_znssd's parameters, 45 sums (sums_out [S][45]).  2: the twelve parameters
+ *             of lk_refine_quadratic, its warp, its 88 sums in three sweeps (sums_out [S][88]), its step, its convergence
+ *             weights, its record layout.
+ *   sampler   0: the engine's interpolator.  3 / 5: the cubic / quintic B-spline of lk_refine_spline - its prefilter, run by
+ *             every call on the level-py_start deformed image, its sampler, its validity rule.
+ *   weights   lk_refine_weighted's: w = mask(node) window(q - centre), sigma = 0 and mask == NULL give w = 1; its prologue
+ *             (n_valid, Sw, Sww, the centroid), the skip of a sample with w == 0 before anything of it is read - in all
+ *             three sweeps with order 2 -, N = Sw, min_fraction.  The too-few rule is n_valid < P + 2, P = 12 with order 2.
+ *   seeds     lk_refine_quadratic's: records or guesses in the engine model's meaning; `second` [S][6] with order 2 only.
+ *             Level, statuses (LK_ZN_*), the BAD_SEED rules and the record that passes through: as there.
+ *   sums      order 1: lk_refine_weighted's (under a spline sampler lk_refine_spline's g, g_x, g_y).  Order 2: every term of
+ *             the 88 sums is lk_refine_quadratic's term, then multiplied by (double)w - a rounded product - then added; the
+ *             flagged count is not weighted.  Which sweep holds a sum changes no bit of it.
+ *   step      lk_composed_step_from_sums: lk_weighted_step_from_sums (order 1) or the arithmetic of
+ *             lk_quadratic_step_from_sums with N = Sw in place of (double)n and n_valid in the too-few test (order 2).  The
+ *             weights of the convergence test keep n_L.
+ *   records   as the chosen order's, with chi = (Sff - 2 Sfg + Sgg) / Sw of the kept sums.
+ *   info      struct lk_composed: struct lk_quadratic's words up to bend, then struct lk_weighted's n_valid, weight_sum,
+ *             n_eff, centroid_dx, centroid_dy.  Order 1: p[0 .. P - 1] = the engine model's parameters as in the record
+ *             (zeros behind them; all zeros for BAD_SEED and OUT_OF_IMAGE), bend = 0.
+ *   reduces   with unit weights and the matching options the records, the shared info words and the sums are the bytes of
+ *             lk_refine_znssd (1, 0), lk_refine_spline (1, 3 / 5) and lk_refine_quadratic (2, 0); (1, 0) with weights is
+ *             lk_refine_weighted's kernel itself.
+ *   modes     as lk_refine_znssd: every mode, synchronous, nothing of the engine is written; nothing is cached between calls.
+ *   errors    the union of the four passes' refusals with this function's name in the messages, outputs untouched; and an
+ *             order that is not 1 or 2; a sampler that is not 0, 3 or 5; `second` given with order 1.
+ *   defaults  as lk_refine_znssd.
+ *   scope     as lk_refine_znssd; no mask on the deformed image; no sampler or model beyond these. */
+typedef struct lk_composed_config {
+  int def_slot;       /* the words and defaults of lk_znssd_config */
+  float chi_max;
+  int max_iters;
+  float precision;
+  float lambda0;
+  int order;          /* 1: the engine's model; 2: twelve parameters */
+  int sampler;        /* 0: the engine's interpolator; 3 / 5: cubic / quintic B-spline */
+  float sigma;        /* the words of lk_weighted_config */
+  float min_fraction;
+  int mask_rows, mask_cols;
+  int reserved[5];    /* must be 0 */
+} lk_composed_config;
+struct lk_composed {  /* 128 bytes, one per sector: the layout of struct lk_quadratic */
+  int32_t n_points, status, iterations, evaluations;   /* status: LK_ZN_* */
+  float p[12];                         /* level-0 scale; order 1: the engine model's P parameters, zeros behind them */
+  float zncc, gain, offset, znssd;     /* of the weighted sums */
+  float zncc_seed, shift, lambda, last_step;
+  float bend;                          /* as struct lk_quadratic; 0 with order 1 */
+  int32_t n_valid;                     /* as struct lk_weighted */
+  float weight_sum, n_eff;
+  float centroid_dx, centroid_dy;
+  int32_t reserved[2];
+};
+/* mask: as lk_refine_weighted.  records, guesses, second, records_out: as lk_refine_quadratic; info_out: [S] or NULL (not
+ * both outputs).  sums_out: [S][45] (order 1) or [S][88] (order 2) doubles or NULL.  Synchronous.  Changes no engine state. */
+int lk_refine_composed(lk_engine *e, const lk_composed_config *cfg, const uint8_t *mask, const lk_result *records,
+                       const float *guesses, const float *second, lk_result *records_out, struct lk_composed *info_out,
+                       double *sums_out);
+/* criterion and step of either order for n_valid samples of total weight N.  order 1: lk_weighted_step_from_sums of `model`,
+ * delta12 zeros behind P.  order 2: lk_quadratic_step_from_sums with N in place of (double)n (N = n_valid gives its bits);
+ * the model plays no part.  LK_ERROR_BAD_DOMAIN (outputs untouched) as those two, and for an order that is not 1 or 2. */
+int lk_composed_step_from_sums(int order, int model, int n_valid, double N, const double *sums, float lambda,
+                               double *delta12, double *crit, double *gain_offset2, int32_t *status);
 
 /* ---- field map: dense displacement and strain maps on a regular grid of nodes ---------------- */
 /* lk_field_map gives the full-field picture a DIC user looks at first: u, v, the gradients, the strain tensor and its

@@ -301,6 +301,34 @@ def run_quadratic():
     return out
 
 
+def run_composed():
+    import correlation_amd as ca
+    out = {}
+    mask = np.ones((256, 256), np.uint8)
+    mask[:, 100:108] = 0
+    mask[30:34, :] = 0
+    for scene in ("mix", "grid"):
+        for model, interp, name in ((ca.FM_UVUXUYVXVY, ca.IM_BICUBIC, "affine_bicubic"), (ca.FM_UV, ca.IM_BILINEAR, "uv_bilinear"),
+                                    (ca.FM_UVQ, ca.IM_BICUBIC_SEPARABLE, "uvq_separable"), (ca.FM_U, ca.IM_BICUBIC, "u_bicubic")):
+            e, rec = solved(scene, model, interp)
+            g = np.zeros((e.n_sectors, 6), np.float32)
+            g[:, :2] = TRUTH[:2]
+            g2 = np.tile(np.float32([1e-4, -1e-4, 5e-5, -5e-5, 1e-4, -1e-4]), (e.n_sectors, 1))
+            for order in (1, 2):
+                for sampler in (0, 3, 5):
+                    for seeds, kw in (("unit", dict(records=rec)), ("both", dict(guesses=g, sigma=3.0, mask=mask, min_fraction=0.5)),
+                                      ("second", dict(guesses=g, second=g2, mask=mask))):
+                        if seeds == "second" and order == 1:
+                            continue
+                        refined, info, sums = e.refine_composed(order=order, sampler=sampler, return_sums=True, **kw)
+                        tag = "composed%d%d_%s_%s_%s" % (order, sampler, scene, name, seeds)
+                        out.update(fields(tag + ".records", refined))
+                        out.update(fields(tag, info))
+                        out[tag + ".sums"] = sums
+            e.close()
+    return out
+
+
 # ---- the solve's own launch paths (lk_engine_solve.cpp, lk_engine_sequence.cpp): records of the engine itself -----------
 MODES = ("default", "batch_invariant", "reference_order1", "reference_order4", "backward")
 
@@ -409,7 +437,7 @@ VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (
 VARIANTS += [("field_walk%d" % w, {"LK_FIELD_WALK": str(w)}, run_field) for w in (0, 1)]
 VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
              ("pattern", {}, run_pattern), ("znssd", {}, run_znssd), ("quadratic", {}, run_quadratic),
-             ("spline", {}, run_spline), ("weighted", {}, run_weighted)]
+             ("spline", {}, run_spline), ("weighted", {}, run_weighted), ("composed", {}, run_composed)]
 VARIANTS += SOLVES
 
 
