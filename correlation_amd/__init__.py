@@ -12,6 +12,7 @@ from ._ffi import (ERROR_BAD_DOMAIN, ERROR_CORRELATION_MAX_ITERS_REACHED, ERROR_
                    load_library)
 from ._ffi import (GS_NO_CANDIDATE, GS_OK, GS_TEXTURELESS, GS_TOO_FEW, GS_TOO_LARGE, GS_WEAK,  # noqa: F401
                    GUESS_MATCH_DTYPE)
+from ._ffi import ROTATED_MATCH_DTYPE, RS_MAX_ANGLES, rotation_table  # noqa: F401
 from ._ffi import (RESEED_GOOD, RESEED_INFO_DTYPE, RESEED_NO_NEIGHBOUR, RESEED_NOT_IMPROVED, RESEED_PLANNED,  # noqa: F401
                    RESEED_RECOVERED)
 from ._ffi import (STRAIN_DEGENERATE, STRAIN_DTYPE, STRAIN_FILLED, STRAIN_GREEN_LAGRANGE, STRAIN_OK, STRAIN_SMALL,  # noqa: F401

@@ -65,6 +65,28 @@ GUESS_MATCH_DTYPE = np.dtype({"names": [f for f, _ in LkGuessMatch._fields_],
                               "offsets": [getattr(LkGuessMatch, f).offset for f, _ in LkGuessMatch._fields_],
                               "itemsize": C.sizeof(LkGuessMatch)})
 
+# rotation-aware automatic initial guess (include/lk_engine.h: lk_search_rotated)
+RS_MAX_ANGLES = 361
+
+
+class LkRotatedSearch(C.Structure):
+    _fields_ = [("search", LkGuessSearch), ("angle_center", C.c_float), ("angle_step", C.c_float), ("n_half", C.c_int)]
+
+
+class LkRotatedMatch(C.Structure):
+    _fields_ = [("center_x", C.c_int), ("center_y", C.c_int), ("shift_x", C.c_int), ("shift_y", C.c_int),
+                ("n_samples", C.c_int), ("n_valid", C.c_int), ("status", C.c_int), ("angle_index", C.c_int),
+                ("score", C.c_double), ("runner_up", C.c_double), ("angle_runner_up", C.c_double),
+                ("angle", C.c_float), ("angle_refined", C.c_float)]
+
+
+# lk_rotated_match as a numpy record (same layout as LkRotatedMatch)
+ROTATED_MATCH_DTYPE = np.dtype({"names": [f for f, _ in LkRotatedMatch._fields_],
+                                "formats": [np.int32] * 8 + [np.float64] * 3 + [np.float32] * 2,
+                                "offsets": [getattr(LkRotatedMatch, f).offset for f, _ in LkRotatedMatch._fields_],
+                                "itemsize": C.sizeof(LkRotatedMatch)})
+assert ROTATED_MATCH_DTYPE.itemsize == 64
+
 # recovery pass (include/lk_engine.h: lk_reseed_failed)
 RESEED_GOOD, RESEED_RECOVERED, RESEED_NO_NEIGHBOUR, RESEED_NOT_IMPROVED, RESEED_PLANNED = range(5)
 
@@ -362,6 +384,10 @@ SYMBOLS = {
     "lk_get_guesses": (C.c_int, [_P, _F]),
     "lk_search_guesses": (C.c_int, [_P, C.POINTER(LkGuessSearch), _F]),
     "lk_get_guess_search_info": (C.c_int, [_P, _P]),
+    "lk_search_rotated": (C.c_int, [_P, C.POINTER(LkRotatedSearch), _F]),
+    "lk_get_rotated_search_info": (C.c_int, [_P, _P]),
+    "lk_get_rotated_search_profile": (C.c_int, [_P, _P]),
+    "lk_rotation_table": (C.c_int, [C.POINTER(LkRotatedSearch), _F]),
     "lk_reseed_failed": (C.c_int, [_P, C.POINTER(LkReseedConfig), _P, _I]),
     "lk_get_reseed_info": (C.c_int, [_P, _P]),
     "lk_reseed_plan": (C.c_int, [_P, C.POINTER(LkReseedConfig), _P, _F, _P]),
@@ -522,6 +548,19 @@ def compose_inverse(model, p, delta):
         return None
     if rc != 0:
         raise ValueError(f"lk_compose_inverse: bad model {model}")
+    return out
+
+
+def rotation_table(angle_step, n_half, angle_center=0.0):
+    """lk_rotation_table (host, the table the kernels of lk_search_rotated read): float32 [2 n_half + 1][2], {cos, sin} of
+    theta_k = angle_center + k angle_step, k = -n_half .. n_half."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    cfg = LkRotatedSearch(LkGuessSearch(-1, 0, 0, 0.0, -1), float(angle_center), float(angle_step), int(n_half))
+    out = np.zeros((max(2 * int(n_half) + 1, 1), 2), np.float32)
+    if _compose_lib.lk_rotation_table(C.byref(cfg), fptr(out)) != 0:
+        raise ValueError("lk_rotation_table: bad n_half, angle_step or angle_center")
     return out
 
 

@@ -11,14 +11,14 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblk_engine.so")
 SOURCES = ["lk_engine.cpp", "lk_engine_images.cpp", "lk_engine_sectors.cpp", "lk_engine_moves.cpp", "lk_engine_solve.cpp",
            "lk_engine_sequence.cpp", "lk_tracker.cpp", "lk_group.cpp", "lk_image_io.cpp", "lk_kernels.hip", "lk_guess_search.cpp",
-           "lk_guess_search.hip", "lk_backward.hip", "lk_reseed.cpp", "lk_reseed.hip",
+           "lk_guess_search.hip", "lk_rotated_search.cpp", "lk_rotated_search.hip", "lk_backward.hip", "lk_reseed.cpp", "lk_reseed.hip",
            "lk_strain.cpp", "lk_strain.hip", "lk_uncertainty.cpp", "lk_uncertainty.hip",
            "lk_outlier.cpp", "lk_outlier.hip", "lk_track.cpp", "lk_track.hip",
            "lk_residual.cpp", "lk_residual.hip", "lk_pattern.cpp", "lk_pattern.hip",
            "lk_field.cpp", "lk_field.hip", "lk_znssd.cpp", "lk_znssd.hip",
            "lk_quadratic.cpp", "lk_quadratic.hip", "lk_spline.cpp", "lk_spline.hip",
            "lk_weighted.cpp", "lk_weighted.hip", "lk_composed.cpp", "lk_composed.hip"]
-HEADERS = ["lk_engine_state.hpp", "lk_device.hpp", "lk_roi.hpp", "lk_solver_common.hpp", "lk_compose.hpp", "lk_launch.hpp", "lk_neighbours.hpp", "lk_rect_walk.hpp", "lk_sector_eval.hpp", "lk_cell_grid.hpp", "lk_pass.hpp", "lk_strain.hpp", "lk_uncertainty.hpp", "lk_outlier.hpp", "lk_track.hpp", "lk_residual.hpp", "lk_pattern.hpp", "lk_field.hpp", "lk_znssd.hpp", "lk_znssd_loop.hpp", "lk_quadratic.hpp", "lk_quadratic_loop.hpp", "lk_spline.hpp", "lk_weighted.hpp", "lk_sector_policies.hpp", "lk_composed.hpp", os.path.join("..", "..", "include", "lk_engine.h"),
+HEADERS = ["lk_engine_state.hpp", "lk_device.hpp", "lk_roi.hpp", "lk_solver_common.hpp", "lk_compose.hpp", "lk_launch.hpp", "lk_search_common.hpp", "lk_neighbours.hpp", "lk_rect_walk.hpp", "lk_sector_eval.hpp", "lk_cell_grid.hpp", "lk_pass.hpp", "lk_strain.hpp", "lk_uncertainty.hpp", "lk_outlier.hpp", "lk_track.hpp", "lk_residual.hpp", "lk_pattern.hpp", "lk_field.hpp", "lk_znssd.hpp", "lk_znssd_loop.hpp", "lk_quadratic.hpp", "lk_quadratic_loop.hpp", "lk_spline.hpp", "lk_weighted.hpp", "lk_sector_policies.hpp", "lk_composed.hpp", os.path.join("..", "..", "include", "lk_engine.h"),
            os.path.join("..", "..", "include", "lk_tracker.h"), os.path.join("..", "..", "include", "lk_group.h")]
 
 

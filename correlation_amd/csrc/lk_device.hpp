@@ -204,6 +204,24 @@ struct LkGuessSearchArgs {
 constexpr int kLkGsThreads = 256;
 constexpr int kLkGsChunk = 1024; // template samples staged in LDS at a time (uint32 partial sums per chunk are exact)
 
+// Rotation-aware automatic guess (lk_rotated_search.hip): one workgroup per (sector, angle) writes an LkRotAngleRecord, one
+// lane group per sector reduces them to an lk_rotated_match, the guess and the profile.
+struct LkRotAngleRecord { // 32 bytes
+  double best, runner_up; // -2 where there is none
+  int shift_x, shift_y, n_valid, status; // status: LK_GS_* of this angle alone, LK_GS_OK where it has a scored candidate
+};
+struct LkRotatedSearchArgs {
+  LkGuessSearchArgs gs;      // images, lists, guesses, history, level, radius, min_samples, min_score, win_bytes (match unused)
+  const float2 *center;      // [S] the committed level-0 centres
+  const float2 *cos_sin;     // [n_angles] {c_k, s_k}, the table of lk_rotation_table
+  LkRotAngleRecord *angle;   // [S][n_angles]
+  double *profile;           // [S][n_angles] best score per angle, -2 where an angle has none
+  lk_rotated_match *match;   // [S]
+  int n_angles, model;
+  double angle_center, angle_step;
+};
+constexpr int kLkRsReduceThreads = 64; // lanes of the reduce kernel's group
+
 // Backward (inverse-compositional) update (lk_backward.hip, lk_set_update): one lane group per sector for its whole
 // coarse-to-fine solve.  The group is chosen from the sector's level-0 sample count alone (kLkBwGroup*), so that a
 // sector's record does not depend on what else is solved with it.

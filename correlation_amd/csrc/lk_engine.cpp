@@ -260,6 +260,12 @@ int lk_internal_fail(lk_engine *e, int code, const char *what) { return e->fail(
 int lk_internal_hipfail(lk_engine *e, hipError_t err, const char *where) { return e->hipfail(err, where); }
 int *lk_internal_guess_search_count(lk_engine *e) { return &e->gs_count; }
 
+int lk_internal_engine_stream(lk_engine *e, hipStream_t *stream) {
+  HIPCHK(hipSetDevice(e->cfg.device));
+  *stream = e->stream;
+  return LK_ERROR_NONE;
+}
+
 int lk_internal_guess_search_matches(lk_engine *e, lk_guess_match **d_match, hipStream_t *stream) {
   if (!e->d_gs_match.p)
     return e->fail(LK_ERROR_BAD_DOMAIN, "lk_get_guess_search_info: no search yet");
@@ -289,19 +295,20 @@ static int level_images(lk_engine *e, const char *who, int level, int def_slot, 
   return LK_ERROR_NONE;
 }
 
-int lk_internal_guess_search_view(lk_engine *e, int level, int def_slot, LkGuessSearchView *v) {
+int lk_internal_guess_search_view(lk_engine *e, int level, int def_slot, LkGuessSearchView *v, const char *who) {
+  const std::string w(who);
   if (level < 0)
     level = e->cfg.py_stop;
   if (!e->committed)
-    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_search_guesses: sectors are not committed (call lk_commit_sectors)");
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": sectors are not committed (call lk_commit_sectors)");
   if (level < 0 || level > e->cfg.py_stop || level >= LK_MAX_LEVELS || e->h_off[level].size() != (size_t)e->S + 1 ||
       e->h_rect[level].size() != (size_t)e->S)
-    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_search_guesses: the engine builds no sample lists for that level");
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": the engine builds no sample lists for that level");
   HIPCHK(hipSetDevice(e->cfg.device));
   if (int rc = recommit_if_pending(e)) // (as the next solve would)
     return rc;
   const DevImage *u = nullptr, *d = nullptr;
-  if (int rc = level_images(e, "lk_search_guesses", level, def_slot, &u, &d)) // (any negative def_slot: LK_IMG_DEF)
+  if (int rc = level_images(e, who, level, def_slot, &u, &d)) // (any negative def_slot: LK_IMG_DEF)
     return rc;
   HIPCHK(e->d_gs_match.ensure((size_t)std::max(e->S, 1)));
   v->stream = e->stream;
@@ -322,6 +329,7 @@ int lk_internal_guess_search_view(lk_engine *e, int level, int def_slot, LkGuess
   v->d_guess = e->d_guess.p;
   v->d_prev_p = e->d_prev_p.p;
   v->d_match = e->d_gs_match.p;
+  v->center = e->d_center.p;
   return LK_ERROR_NONE;
 }
 

@@ -39,10 +39,14 @@ struct LkGuessSearchView {
   const uint32_t *h_off;    // [S+1]
   float *d_guess, *d_prev_p; // [S][6] engine-held guesses and previous_resulting_parameters
   lk_guess_match *d_match;  // [S]
+  const float2 *center;     // [S] the committed level-0 centres (device; lk_search_rotated)
 };
-int lk_internal_guess_search_view(lk_engine *e, int level, int def_slot, LkGuessSearchView *v);
+// refusals are prefixed with `who`, the function the caller called
+int lk_internal_guess_search_view(lk_engine *e, int level, int def_slot, LkGuessSearchView *v, const char *who = "lk_search_guesses");
 // level -1: py_stop (v->level says which)
 int lk_internal_guess_search_matches(lk_engine *e, lk_guess_match **d_match, hipStream_t *stream);
+// the engine's stream, its device made current (lk_get_rotated_search_info / _profile wait on it)
+int lk_internal_engine_stream(lk_engine *e, hipStream_t *stream);
 int lk_internal_fail(lk_engine *e, int code, const char *what);
 int lk_internal_hipfail(lk_engine *e, hipError_t err, const char *where);
 // the sector count the match buffer holds results for (set by lk_search_guesses; 0: none yet)
@@ -87,7 +91,7 @@ struct LkPassSlot {
   virtual ~LkPassSlot() = default;
 };
 enum LkPass { LK_PASS_RESEED, LK_PASS_STRAIN, LK_PASS_UNCERTAINTY, LK_PASS_OUTLIER, LK_PASS_TRACK, LK_PASS_RESIDUAL, LK_PASS_PATTERN,
-              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_COUNT };
+              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_ROTATED, LK_PASS_COUNT };
 LkPassSlot **lk_internal_pass_slot(lk_engine *e, int which);
 
 // What a post-processing pass reads of the engine (lk_strain_field, lk_parameter_uncertainty, lk_flag_outliers,

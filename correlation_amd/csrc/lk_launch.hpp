@@ -29,6 +29,12 @@ hipError_t lk_launch_guess_search(const LkGuessSearchArgs &a, hipStream_t st);
 // LDS left for the staged window: 64 KB per workgroup minus the scores, the template chunk and the reduction arrays
 int lk_guess_search_window_budget(int radius, int has_v);
 
+// ---- lk_rotated_search.hip: the same search over angle and shift
+// one workgroup per (sector, angle): the per-angle records
+hipError_t lk_launch_rotated_search(const LkRotatedSearchArgs &a, hipStream_t st);
+// one lane group per sector: the winner across angles, the guess, the history, the match and the profile
+hipError_t lk_launch_rotated_reduce(const LkRotatedSearchArgs &a, hipStream_t st);
+
 // ---- lk_kernels.hip: pyramids and the level table
 hipError_t lk_launch_pyramid(const uint8_t *src, int srows, int scols, uint8_t *dst, hipStream_t st);
 hipError_t lk_launch_set_views(const LkLevelView *h_views, LkLevelView *d_views, hipStream_t st);

@@ -32,6 +32,7 @@ class HipCorrelationEngine:
                             py_stop, device)
         self.n_params = _ffi.N_PARAMS[fitting_model]
         self._seq_frames = 0   # frames of the last window this object launched (correlate_sequence_async)
+        self._rs_angles = 1    # angles of the last search_rotated
         self._h = C.c_void_p()
         rc = self.lib.lk_create(C.byref(self.cfg), C.byref(self._h))
         if rc != 0:
@@ -342,6 +343,36 @@ class HipCorrelationEngine:
         out = np.zeros(self.n_sectors, _ffi.GUESS_MATCH_DTYPE)
         self._chk(self.lib.lk_get_guess_search_info(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    # ---- rotation-aware automatic initial guess: the same search over angle and shift ------------
+    def search_rotated(self, radius, angle_step, n_half, angle_center=0.0, level=-1, guesses=None, min_samples=0,
+                       min_score=0.0, def_slot=-1):
+        """search_guesses at every angle angle_center + k angle_step (radians), k = -n_half .. n_half; an OK sector also gets
+        the winning rotation in g[2..5] (affine) or g[2] (FM_UVQ) (include/lk_engine.h: lk_search_rotated).  guesses as for
+        search_guesses."""
+        cfg = _ffi.LkRotatedSearch(_ffi.LkGuessSearch(int(level), int(radius), int(min_samples), float(min_score), int(def_slot)),
+                                   float(angle_center), float(angle_step), int(n_half))
+        g = None if guesses is None else np.array(guesses, np.float32).reshape(self.n_sectors, 6)
+        self._chk(self.lib.lk_search_rotated(self._h, C.byref(cfg), None if g is None else _ffi.fptr(g)))
+        self._rs_angles = 2 * int(n_half) + 1
+        return g
+
+    def rotated_search_info(self):
+        """The matches of the last search_rotated: a ROTATED_MATCH_DTYPE array [S]."""
+        out = np.zeros(self.n_sectors, _ffi.ROTATED_MATCH_DTYPE)
+        self._chk(self.lib.lk_get_rotated_search_info(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def rotated_search_profile(self):
+        """The best score per angle of the last search_rotated: float64 [S][2 n_half + 1], -2 where an angle has none."""
+        out = np.zeros((self.n_sectors, self._rs_angles), np.float64)
+        self._chk(self.lib.lk_get_rotated_search_profile(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    @staticmethod
+    def rotation_table(angle_step, n_half, angle_center=0.0):
+        """lk_rotation_table: the {cos, sin} table search_rotated uploads, float32 [2 n_half + 1][2]."""
+        return _ffi.rotation_table(angle_step, n_half, angle_center)
 
     # ---- recovery pass: failed sectors re-solved from their converged neighbours ---------------
     def reseed_failed(self, radius, chi_max=0.0, min_neighbours=1, max_rounds=8, want_records=True):

@@ -431,6 +431,61 @@ int lk_search_guesses(lk_engine *e, const lk_guess_search *cfg, float *guesses_i
 /* the matches of the last lk_search_guesses, [S] (waits for it) */
 int lk_get_guess_search_info(lk_engine *e, lk_guess_match *out);
 
+/* ---- rotation-aware automatic initial guess: ZNCC search over angle and shift ---------------- */
+/* lk_search_guesses run at every angle theta_k = angle_center + k angle_step, k = -K .. K (K = n_half), for specimens that
+ * rotate between the two frames (LK_FM_UVQ, LK_FM_UVUXUYVXVY; LK_FM_U and LK_FM_UV have no parameter that could carry an
+ * angle and are refused with LK_ERROR_BAD_DOMAIN, as are n_half < 0, 2K+1 > LK_RS_MAX_ANGLES, a step that is not > 0 while
+ * K > 0, a centre or step that is not finite, and whatever lk_search_guesses refuses of `search`).
+ *   template   exactly lk_search_guesses': the sector's level-L samples in the reference's order, rounded (int)(v + 0.5f) and
+ *              clamped to the undeformed image, u8 values of the level-L undeformed image; St, Stt and the checks TOO_LARGE,
+ *              TOO_FEW, TEXTURELESS as there.
+ *   table      lk_rotation_table: theta_k = (double)angle_center + k (double)angle_step, c_k = (float)cos(theta_k),
+ *              s_k = (float)sin(theta_k), built on the host once per call; the kernels call no trigonometric function.
+ *   position   of template sample (x, y) at angle k, every step in float32 and rounded on its own (no fused multiply-add):
+ *              C = (cx0, cy0) 2^-L with (cx0, cy0) the committed level-0 centre (lk_get_sector_info); dx = (float)x - Cx,
+ *              dy = (float)y - Cy; rx = c dx - s dy, ry = s dx + c dy; X = (int)floorf((Cx + rx) + 0.5f), Y likewise.  A
+ *              positive angle is counter-clockwise in image coordinates as Warp<UVUXUYVXVY> sees it.  Candidate (k, i, j)
+ *              reads the level-L deformed pixel (X + c_x + i, Y + c_y + j), nearest neighbour, (c_x, c_y) = lk_search_guesses'
+ *              rounded centre of g[0], g[1].  Several samples may land on one pixel; n stays the template's count.
+ *   validity   every deformed sample of the candidate inside the level-L deformed image (per angle a rectangle of shifts,
+ *              from the rotated bounding box) and n Sdd != Sd^2.  The score is lk_search_guesses' exact expression.
+ *   winner     over (k, i, j): the higher score, then the smaller |k|, then the smaller k, then lk_search_guesses' rule
+ *              (the smaller i^2 + j^2, then the smaller j, then the smaller i).  Statuses are checked in lk_search_guesses'
+ *              order; NO_CANDIDATE: no valid candidate at any angle.
+ *   guess      an OK sector gets g[0], g[1] as lk_search_guesses writes them and, LK_FM_UVUXUYVXVY: g[2] = c - 1.f,
+ *              g[3] = 0.f - s, g[4] = s, g[5] = c - 1.f; LK_FM_UVQ: g[2] = s (the linearised warp's best q), g[3..5] untouched.
+ *              A sector that is not OK keeps its six words, bit for bit.  Engine-held guesses and the sequence history are
+ *              written as lk_search_guesses writes them.
+ *   refined    angle_refined = (float)(theta_k + t angle_step), t = 0.5 (s- - s+) / (s- - 2 s0 + s+) from the best scores of
+ *              the angles k-1, k, k+1 of the winner, clamped to [-0.5, 0.5]; t = 0 unless both neighbours have a score and
+ *              the denominator is negative.  Reported only: the guess uses the table's c_k, s_k.
+ * A sector without a winner reports shift 0, angle_index 0, score and runner-ups -2 and theta_0 as both angles.  With
+ * n_half = 0 and angle_center = 0 the pass equals lk_search_guesses: the same g[0], g[1] and shared match fields, byte for
+ * byte (an affine OK sector gets g[2..5] = +0.0f).  Integer sums, unfused float steps: a sector gets the same bits in any
+ * batch and mode, whatever other sectors or angles are in the call. */
+#define LK_RS_MAX_ANGLES 361
+typedef struct {
+  lk_guess_search search;   /* level, radius, min_samples, min_score, def_slot: lk_search_guesses' meaning */
+  float angle_center;       /* radians, counter-clockwise in image coordinates as Warp<UVUXUYVXVY> sees it */
+  float angle_step;         /* radians, > 0 (ignored when n_half == 0) */
+  int n_half;               /* K: angles theta_k = center + k step, k = -K .. K; 2K+1 <= LK_RS_MAX_ANGLES */
+} lk_rotated_search;
+typedef struct {            /* 64 bytes, one per sector */
+  int center_x, center_y, shift_x, shift_y;    /* as lk_guess_match, at the winning angle */
+  int n_samples, n_valid, status, angle_index; /* n_valid: scored candidates over ALL angles; status: LK_GS_*; k of the winner */
+  double score, runner_up;  /* runner_up: lk_guess_match's rule, inside the winning angle */
+  double angle_runner_up;   /* best per-angle score among angles with |k - k_win| >= 2; -2: none */
+  float angle, angle_refined; /* theta_k_win; the same plus the parabola's offset */
+} lk_rotated_match;
+/* guesses_inout as for lk_search_guesses (NULL: about the engine-held guesses, asynchronous on the engine stream) */
+int lk_search_rotated(lk_engine *e, const lk_rotated_search *cfg, float *guesses_inout);
+/* the matches of the last lk_search_rotated, [S] (waits for it) */
+int lk_get_rotated_search_info(lk_engine *e, lk_rotated_match *out);
+/* its best score per angle, [S][2K+1], -2 where an angle has no score (waits for it) */
+int lk_get_rotated_search_profile(lk_engine *e, double *best_per_angle);
+/* host: {c_k, s_k}, [2K+1][2], the table the kernels read; LK_ERROR_BAD_DOMAIN for a bad n_half, step or centre */
+int lk_rotation_table(const lk_rotated_search *cfg, float *cos_sin_out);
+
 /* ---- recovery pass: re-solve failed sectors from their converged neighbours ------------- */
 /* lk_reseed_failed repairs the engine-held records of the last lk_correlate_all* / lk_wait_results after the fact: a sector
  * that failed is given a guess extrapolated from neighbours that converged and is solved again; what was recovered seeds
