@@ -24,6 +24,8 @@ from ._ffi import (ERROR_OUTLIER, OUTLIER_DEGENERATE, OUTLIER_DTYPE, OUTLIER_FLA
 from ._ffi import (TRACK_BAD_POINT, TRACK_DEGENERATE, TRACK_DTYPE, TRACK_INCREMENTAL, TRACK_LOST, TRACK_OK,  # noqa: F401
                    TRACK_RECORDS_CALLER, TRACK_RECORDS_ENGINE, TRACK_RECORDS_WINDOW, TRACK_TOO_FEW, TRACK_TOTAL,
                    gauges_from_tracks, track_step)
+from ._ffi import (MOTION_AFFINE, MOTION_DEGENERATE, MOTION_DTYPE, MOTION_MIN_SECTORS, MOTION_OK, MOTION_RIGID,  # noqa: F401
+                   MOTION_SIMILARITY, MOTION_TOO_FEW, MOTION_TRANSLATION, motion_apply, motion_from_sums, motion_remove)
 from ._ffi import (MAP_NO_OWNER, PHOTO_BAD_RECORD, PHOTO_FLAT, PHOTO_OK, PHOTO_OUT_OF_IMAGE, PHOTO_SUMS,  # noqa: F401
                    PHOTO_TOO_FEW, PHOTOMETRY_DTYPE, map_owner, photometry_from_sums)
 from ._ffi import (ZN_BAD_SEED, ZN_CONVERGED, ZN_FLAT, ZN_MAX_ITERS, ZN_NEGATIVE, ZN_OUT_OF_IMAGE, ZN_SINGULAR,  # noqa: F401

@@ -162,6 +162,23 @@ TRACK_DTYPE = np.dtype([(k, np.float32) for k in ("x", "y", "u", "v", "ux", "uy"
                        [("neighbours", np.int32), ("status", np.int32)])
 assert TRACK_DTYPE.itemsize == 64
 
+# global motion per frame (include/lk_engine.h: lk_rigid_motion)
+MOTION_TRANSLATION, MOTION_RIGID, MOTION_SIMILARITY, MOTION_AFFINE = range(4)
+MOTION_OK, MOTION_TOO_FEW, MOTION_DEGENERATE = range(3)
+MOTION_MIN_SECTORS = {MOTION_TRANSLATION: 1, MOTION_RIGID: 2, MOTION_SIMILARITY: 2, MOTION_AFFINE: 3}
+
+
+class LkMotionConfig(C.Structure):
+    _fields_ = [("kind", C.c_int), ("source", C.c_int), ("chi_max", C.c_float), ("reject", C.c_float), ("passes", C.c_int),
+                ("min_sectors", C.c_int), ("reserved", C.c_int * 2)]
+
+
+# lk_motion as a numpy record
+MOTION_DTYPE = np.dtype([(k, np.float32) for k in ("cx", "cy", "tx", "ty", "axx", "axy", "ayx", "ayy", "theta", "scale", "rms",
+                                                   "max_residual")] +
+                        [(k, np.int32) for k in ("n_fit", "n_rejected", "status", "passes_run")])
+assert MOTION_DTYPE.itemsize == 64 and C.sizeof(LkMotionConfig) == 32
+
 # photometry and the residual map (include/lk_engine.h: lk_photometry, lk_residual_map)
 PHOTO_OK, PHOTO_BAD_RECORD, PHOTO_OUT_OF_IMAGE, PHOTO_TOO_FEW, PHOTO_FLAT = range(5)
 PHOTO_SUMS = 8   # doubles per sector: sum f, sum g, sum f^2, sum g^2, sum f g, sum V^2, flagged samples, max |V|
@@ -400,6 +417,10 @@ SYMBOLS = {
     "lk_track_points": (C.c_int, [_P, C.POINTER(LkTrackConfig), C.c_int, _F, C.c_int, _P, _P, _P]),
     "lk_track_step": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
     "lk_gauges_from_tracks": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, _F]),
+    "lk_rigid_motion": (C.c_int, [_P, C.POINTER(LkMotionConfig), C.c_int, _P, _P, _P, _P, _P]),
+    "lk_motion_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "lk_motion_apply": (C.c_int, [_P, C.c_int, _F, _F]),
+    "lk_motion_remove": (C.c_int, [C.c_int, _P, C.c_float, C.c_float, _P, _P]),
     "lk_photometry": (C.c_int, [_P, C.POINTER(LkPhotometryConfig), _P, _P, _P]),
     "lk_photometry_from_sums": (C.c_int, [C.c_int, _P, _P]),
     "lk_residual_map": (C.c_int, [_P, C.POINTER(LkResidualMapConfig), _P, _P, _P, _P]),
@@ -788,4 +809,55 @@ def gauges_from_tracks(tracks, pairs):
     if _compose_lib.lk_gauges_from_tracks(t.shape[0], t.shape[1], t.ctypes.data_as(_P), len(ij), ij.ctypes.data_as(_P),
                                           fptr(out)) != 0:
         raise ValueError("lk_gauges_from_tracks: no frames, points or gauges, or a pair index outside the points")
+    return out
+
+
+def motion_from_sums(kind, n, sums11, origin_xy, min_sectors=None):
+    """lk_motion_from_sums (host, the kernel's fit): the fit set's count n and 11 sums relative to origin_xy -> the
+    MOTION_DTYPE record (rms, max_residual, n_rejected and passes_run are 0: the sums do not hold them)."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.ascontiguousarray(sums11, np.float64).reshape(11)
+    o = np.ascontiguousarray(origin_xy, np.float64).reshape(2)
+    out = np.zeros(1, MOTION_DTYPE)
+    if min_sectors is None:
+        min_sectors = MOTION_MIN_SECTORS.get(int(kind), 1)
+    if _compose_lib.lk_motion_from_sums(int(kind), int(min_sectors), int(n), s.ctypes.data_as(_P), o.ctypes.data_as(_P),
+                                        out.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_motion_from_sums: n < 0, an unknown kind or a min_sectors below the kind's minimum")
+    return out[0]
+
+
+def motion_apply(motion, xy):
+    """lk_motion_apply (host): the displacement t + (A - I)(x - c) of one MOTION_DTYPE record at xy [n][2] -> float32 [n][2]."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    m = np.ascontiguousarray(motion, MOTION_DTYPE).reshape(1)
+    p = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    out = np.zeros_like(p)
+    if _compose_lib.lk_motion_apply(m.ctypes.data_as(_P), len(p), fptr(p), fptr(out)) != 0:
+        raise ValueError("lk_motion_apply: no positions")
+    return out
+
+
+def motion_remove(model, motion, centers, records, good=None):
+    """lk_motion_remove (host, the kernel's removal) over one frame: records [S] at centers [S][2] without the MOTION_DTYPE
+    record `motion` -> records [S].  good [S]: the records to rewrite (the caller's good rule); None: all of them."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    m = np.ascontiguousarray(motion, MOTION_DTYPE).reshape(1)
+    c = np.ascontiguousarray(centers, np.float32).reshape(-1, 2)
+    rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(len(c))
+    out = rec.copy()
+    one = np.zeros(1, RESULT_DTYPE)
+    for s in range(len(c)):
+        if good is not None and not good[s]:
+            continue
+        if _compose_lib.lk_motion_remove(int(model), m.ctypes.data_as(_P), float(c[s, 0]), float(c[s, 1]),
+                                         rec[s:s + 1].ctypes.data_as(_P), one.ctypes.data_as(_P)) != 0:
+            raise ValueError("lk_motion_remove: an unknown model, FM_U with an A that is not the identity, or an A without an inverse")
+        out[s] = one[0]
     return out

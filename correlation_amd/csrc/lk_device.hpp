@@ -329,6 +329,26 @@ struct LkTrackArgs {
   double radius;
 };
 
+// Global motion per frame (lk_motion.hip, include/lk_engine.h: lk_rigid_motion): the sums of every frame's fit set in
+// chunks of `chunk` sectors, the fit of lk_motion.hpp, the residuals to it, and the records with the motion taken out.
+struct LkMotionFit;
+constexpr int kLkMotionPartial = 14; // doubles of a chunk: {n, the 11 sums, sectors trimmed, 0}, or {sum r^2, max r^2, 0 ...}
+struct LkMotionArgs {
+  const float4 *pack;      // [F][S] {cx, cy, u, v} of a good sector, cx = NaN for one that is not (lk_pack_prep_kernel)
+  const uint8_t *fit_mask; // [S] or null
+  uint8_t *keep;           // [F][S] 1: the sector is in the fit set of the running pass (sums kernel -> residual kernel)
+  double *partial;         // [F][chunks][kLkMotionPartial]
+  double *sums;            // [F][12] {n, the 11 sums} of the last pass that ran
+  LkMotionFit *fit;        // [F] the running pass's fit in double; the sums kernel of the next pass trims against it
+  lk_motion *out;          // [F]
+  const lk_result *rec;    // [F][S] the removal's input
+  const float2 *center;    // [S]
+  lk_result *rec_out;      // [F][S]
+  int n_frames, n_sectors, chunk, chunks, kind, min_sectors, model, pass;
+  double ox, oy;           // the origin of the sums: the centre of the centres' bounding box
+  double reject;           // (double)cfg->reject; <= 0: no trimming
+};
+
 // Outlier flags (lk_outlier.hip, include/lk_engine.h: lk_flag_outliers): one pass of the (detrended) normalised median test.
 struct LkOutlierArgs {
   LkReseedGrid grid;

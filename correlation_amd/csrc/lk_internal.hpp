@@ -91,7 +91,7 @@ struct LkPassSlot {
   virtual ~LkPassSlot() = default;
 };
 enum LkPass { LK_PASS_RESEED, LK_PASS_STRAIN, LK_PASS_UNCERTAINTY, LK_PASS_OUTLIER, LK_PASS_TRACK, LK_PASS_RESIDUAL, LK_PASS_PATTERN,
-              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_ROTATED, LK_PASS_COUNT };
+              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_ROTATED, LK_PASS_MOTION, LK_PASS_COUNT };
 LkPassSlot **lk_internal_pass_slot(lk_engine *e, int which);
 
 // What a post-processing pass reads of the engine (lk_strain_field, lk_parameter_uncertainty, lk_flag_outliers,
@@ -162,4 +162,7 @@ int lk_internal_spline_last(lk_engine *e, float *device_ms, int *count3, float *
 int lk_internal_weighted_last(lk_engine *e, float *device_ms, int *count3);
 // lk_refine_composed: as lk_internal_weighted_last; the time covers the coefficient image of a spline sampler
 int lk_internal_composed_last(lk_engine *e, float *device_ms, int *count3);
+// lk_rigid_motion: the chunk size and the chunks per frame; the time covers the pack, the passes and the removal (not the
+// bounding box's round trip, which comes before, and not the copies of the records)
+int lk_internal_motion_last(lk_engine *e, float *device_ms, int *chunk, int *chunks);
 }

@@ -175,3 +175,10 @@ hipError_t lk_launch_subset_query(const LkSubsetArgs &a, hipStream_t st);
 // ---- lk_field.hip: dense displacement and strain maps (lk_field_map)
 // one workgroup per tile of kLkMapTileW x kLkMapTileH nodes; weight, frame: LK_FIELD_*; *n_tiles = the tiles launched
 hipError_t lk_launch_field_map(const LkFieldArgs &a, int weight, int frame, int *n_tiles, hipStream_t st);
+
+// ---- lk_motion.hip: the global motion per frame (lk_rigid_motion)
+// pass a.pass of every frame: the sums of the fit set (one workgroup per chunk and frame), the fit, the residual sums, the
+// residual's close - four kernels; a.chunks = the chunks of a.chunk sectors that cover a.n_sectors
+hipError_t lk_launch_motion_pass(const LkMotionArgs &a, hipStream_t st);
+// a thread per (frame, sector): a.rec without the motion a.out[f] -> a.rec_out
+hipError_t lk_launch_motion_remove(const LkMotionArgs &a, hipStream_t st);

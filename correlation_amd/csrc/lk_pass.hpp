@@ -1,5 +1,5 @@
 // lk_pass.hpp - the host plumbing the add-on passes share (lk_reseed.cpp, lk_strain.cpp, lk_uncertainty.cpp, lk_outlier.cpp,
-// lk_track.cpp, lk_residual.cpp, lk_pattern.cpp, lk_field.cpp; the error macro also lk_guess_search.cpp): device buffers that free themselves, the state a
+// lk_track.cpp, lk_residual.cpp, lk_pattern.cpp, lk_field.cpp, lk_motion.cpp; the error macro also lk_guess_search.cpp): device buffers that free themselves, the state a
 // pass keeps on its slot of the engine, the upload of caller records, the bounding box and cell grid over the centres, the
 // order of the sectors by lane group.  Host only: no .hip file includes it; the device half is lk_neighbours.hpp and
 // lk_sector_eval.hpp.  A new pass starts here ("adding a pass").

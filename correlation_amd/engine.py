@@ -888,6 +888,75 @@ class HipCorrelationEngine:
         """lk_gauges_from_tracks: virtual extensometers between tracked points (host, no engine needed)."""
         return _ffi.gauges_from_tracks(tracks, pairs)
 
+    # ---- global motion: the motion of a frame as a whole, and the records without it ---------------------
+    def rigid_motion(self, kind=_ffi.MOTION_RIGID, n_frames=None, records=None, source=None, fit_mask=None, reject=0.0,
+                     passes=1, chi_max=0.0, min_sectors=None, return_records=False, return_sums=False):
+        """lk_rigid_motion: the MOTION_DTYPE array [F]; with return_records and / or return_sums a tuple (motion, the records
+        [F][S] with the motion taken out, float64 [F][12] = the fit set's count and 11 sums), the parts asked for in that
+        order.  source None: TRACK_RECORDS_CALLER when records [F][S] are given, else TRACK_RECORDS_ENGINE (the last batch
+        solve, one frame); TRACK_RECORDS_WINDOW reads the device records of the last waited-for window in place.  fit_mask [S]:
+        the sectors that may enter the fit.  min_sectors None: the kind's minimum.  No engine state changes."""
+        if source is None:
+            source = _ffi.TRACK_RECORDS_CALLER if records is not None else _ffi.TRACK_RECORDS_ENGINE
+        S = self.n_sectors
+        rec = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(-1, S)
+            if n_frames is None:
+                n_frames = rec.shape[0]
+            elif int(n_frames) > rec.shape[0]:
+                raise ValueError("rigid_motion: fewer frames of records than n_frames")
+        elif source == _ffi.TRACK_RECORDS_WINDOW and not n_frames:
+            # (as track_points: the window's own frame count sizes the outputs)
+            n_frames = self._seq_frames
+            if n_frames == 0 and self.lib.lk_get_sequence_results_device(self._h, None, None) == 0:
+                raise ValueError("rigid_motion: a window this object did not launch is held; pass its n_frames")
+        elif n_frames is None:
+            n_frames = 1
+        mask = None
+        if fit_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(fit_mask) != 0, np.uint8).reshape(-1)
+            if len(mask) != S:
+                raise ValueError("rigid_motion: fit_mask must have one entry per sector")
+        if min_sectors is None:
+            min_sectors = _ffi.MOTION_MIN_SECTORS.get(int(kind), 1)
+        cfg = _ffi.LkMotionConfig(int(kind), int(source), float(chi_max), float(reject), int(passes), int(min_sectors))
+        F = max(int(n_frames), 0)
+        out = np.zeros(F, _ffi.MOTION_DTYPE)
+        rec_out = np.zeros((F, S), RESULT_DTYPE) if return_records else None
+        sums = np.zeros((F, 12), np.float64) if return_sums else None
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self.lib.lk_rigid_motion(self._h, C.byref(cfg), int(n_frames), ptr(rec), ptr(mask), ptr(out), ptr(rec_out),
+                                           ptr(sums)))
+        if not return_records and not return_sums:
+            return out
+        return (out,) + ((rec_out,) if return_records else ()) + ((sums,) if return_sums else ())
+
+    def motion_last(self):
+        """Bench hook: (device ms, chunk size, chunks per frame) of the last rigid_motion call."""
+        ms, chunk, chunks = C.c_float(), C.c_int(), C.c_int()
+        fn = self.lib.lk_internal_motion_last
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self._chk(fn(self._h, C.byref(ms), C.byref(chunk), C.byref(chunks)))
+        return ms.value, chunk.value, chunks.value
+
+    @staticmethod
+    def motion_from_sums(kind, n, sums11, origin_xy, min_sectors=None):
+        """lk_motion_from_sums: the kernel's fit on the host (no engine needed)."""
+        return _ffi.motion_from_sums(kind, n, sums11, origin_xy, min_sectors)
+
+    @staticmethod
+    def motion_apply(motion, xy):
+        """lk_motion_apply: the displacement field of a motion at positions (host, no engine needed)."""
+        return _ffi.motion_apply(motion, xy)
+
+    @staticmethod
+    def motion_remove(model, motion, centers, records, good=None):
+        """lk_motion_remove: the kernel's removal on the host (no engine needed)."""
+        return _ffi.motion_remove(model, motion, centers, records, good)
+
     # ---- stand-alone pieces -------------------------------------------------------------
     def evaluate(self, sector, level, p):
         pp = np.zeros(6, np.float32)

@@ -879,6 +879,114 @@ int lk_track_step(int mode, int min_neighbours, int n, const double *sums11, dou
  * pointer, n_frames, n_points or n_gauges < 1, or a pair index outside 0 .. n_points - 1 (out4 untouched). */
 int lk_gauges_from_tracks(int n_frames, int n_points, const lk_track *tracks, int n_gauges, const int32_t *pairs_ij, float *out4);
 
+/* ---- global motion: the motion of a frame as a whole, and the records without it ----------- */
+/* A specimen that slips in its grips, a camera that sags or a re-mounted part puts a translation and a rotation of many
+ * pixels under a deformation of a few hundredths, and LK_STRAIN_SMALL is not invariant under rotation (a rigid rotation by
+ * 2 degrees reads exx = eyy = cos 2 - 1 = -6.1e-4).  lk_rigid_motion fits ONE motion x -> c + t + A (x - c) to the good
+ * sectors of every frame - a translation, a rigid motion, a similarity or an affine map - and, where asked, returns the
+ * records with that motion taken out, for the passes downstream (csrc/lk_motion.hip, csrc/lk_motion.hpp, DESIGN.md section
+ * 29).
+ *   data      of a sector: position x = the engine's committed centre (lk_get_sector_info), the same in every frame of the
+ *             call; displacement u = p[0], v = p[1] (v = 0 for LK_FM_U); x' = x + (u, v).
+ *   good      the shared rule of the recovery pass, the strain field and the tracks (one device function): LK_ERROR_NONE,
+ *             finite parameters (the model's P), finite chi and, if chi_max > 0, chi <= chi_max; once per (frame, sector).
+ *   records   cfg->source, with lk_track_points' rules and refusals: LK_TRACK_RECORDS_CALLER: `records` is host
+ *             [n_frames][S].  _ENGINE: records == NULL and n_frames == 1; the engine-held records of the last finished batch
+ *             solve.  _WINDOW: records == NULL; the device records of the last window that was waited for are read where
+ *             lk_get_sequence_results_device shows them, without a host copy; n_frames is 0 or that window's frame count.
+ *   fit set   of a frame, pass 0: the good sectors with fit_mask[s] != 0 (all good sectors when fit_mask is NULL) - the mask
+ *             selects a datum region, a grip or a static background.  Pass k > 0 (cfg->passes > 1): the same sectors minus
+ *             those whose residual r_j to pass k - 1's fit exceeds the threshold, r_j > (double)reject * rms_{k-1}, compared
+ *             in double before anything is rounded to float; the trimming is not cumulative (a sector that pass 1 left out
+ *             is back in pass 2 if pass 1's fit brings it under its threshold).  A frame whose pass is not LK_MOTION_OK runs
+ *             no further pass.
+ *   sums      the count n and the eleven sums Sx, Sy, Sxx, Sxy, Syy, Su, Sxu, Syu, Sv, Sxv, Syv of lk_strain_field's `fit`
+ *             paragraph over the fit set, in double, with x, y relative to the origin o = the centre of the bounding box of
+ *             all centres, o = ((double)min + (double)max) / 2 per axis of the float centres.  Each product and each sum is
+ *             rounded to double (no fused multiply-add).  sums_out, if not NULL, receives {n, the eleven sums} of every
+ *             frame's last pass, [n_frames][12] doubles.
+ *   fit       one function for the kernel and the host (csrc/lk_motion.hpp, lk_motion_from_sums), from the centred moments
+ *             of lk_strain_field: Cxx = Sxx - Sx Sx / n, Cxy, Cyy, Cxu = Sxu - Sx Su / n, Cyu, Cxv, Cyv alike.
+ *               c = o + (Sx, Sy) / n  (the centroid of the fit set),  t = (Su, Sv) / n  (its displacement)
+ *               TRANSLATION  A = I
+ *               RIGID        num = Cxv - Cyu,  den = Cxx + Cxu + Cyy + Cyv,  h = sqrt(num^2 + den^2),
+ *                            A = [[den, -num], [num, den]] / h  (2-D Procrustes: the rotation nearest the scatter)
+ *               SIMILARITY   A = [[den, -num], [num, den]] / (Cxx + Cyy)
+ *               AFFINE       A = I + g,  g = the plane gradients ux, uy, vx, vy of lk_strain_field's `fit` paragraph
+ *             Nothing but + - * / sqrt on the way to c, t, A, scale and rms: the host and the device give the same bytes.
+ *             theta = atan2(ayx - axy, axx + ayy) alone uses atan2 and is informational; scale = sqrt(|det A|).  Each
+ *             output is rounded to float once.
+ *   status    checked in this order: TOO_FEW  n < min_sectors;  DEGENERATE  RIGID and SIMILARITY: Cxx + Cyy == 0 or
+ *             h == 0; AFFINE: lk_strain_field's rule, Cxx Cyy == 0 or D <= 1e-6 Cxx Cyy, or det A == 0 (a map that folds
+ *             the plane onto a line cannot be taken out again); TRANSLATION is never degenerate.  For a frame that is not
+ *             OK every float field is 0, n_fit = n, and its records_out are the input records unchanged.
+ *   residual  a second reduction over the fit set, in double and with the fit before its rounding to float:
+ *             r_j = |x'_j - (c + t + A (x_j - c))|,  rms = sqrt(sum r_j^2 / n),  max_residual = max r_j.
+ *   removal   records_out, if not NULL, receives [n_frames][S] records: every good record of a frame whose motion is OK,
+ *             inside the fit set or not, is lk_motion_remove of it - with the 64-byte motion as stored, in double, each
+ *             output rounded to float once:
+ *               x'' = c + A^-1 (x' - c - t),  (u'', v'') = x'' - x,  A^-1 the closed-form inverse of the 2 x 2 matrix.
+ *             This un-rotates the deformed positions; it does not subtract the displacement field t + (A - I)(x - c), which
+ *             differs from it at large rotations.  The local deformation gradient becomes F'' = A^-1 F:
+ *             LK_FM_UVUXUYVXVY  F = [[1 + p2, p3], [p4, 1 + p5]], p2 .. p5 rewritten;  LK_FM_UVQ  F = [[1, -q], [q, 1]],
+ *             q'' = (F''yx - F''xy) / 2;  LK_FM_UV  u and v alone;  LK_FM_U  u alone, and only LK_MOTION_TRANSLATION is
+ *             accepted.  chi, the counts, the error code and undCenterX/Y are copied.  Records that are not good are copied
+ *             unchanged.
+ *   order     fixed: the sectors of a frame are cut into chunks of a constant size by ascending index (2048; the tuning
+ *             hook LK_MOTION_CHUNK=64 makes a small domain span several); within a chunk sector chunk * size + i goes to
+ *             lane i mod 256 of one workgroup, every lane adds what it is dealt in ascending order, and the lanes are
+ *             joined by a fixed butterfly within a wavefront and by ascending wavefront; the chunks are added by ascending
+ *             chunk index.  A frame's motion, sums and output records are the same bytes alone, inside a longer call, from
+ *             any source and on every run.  A float64 restatement reproduces them up to the order of the double sums.
+ *   modes     allowed in every mode, reference-order mode included: the call writes nothing of the engine's - records,
+ *             guesses, last parameters, counters and lk_get_reseed_info stay byte for byte - and a rebuild of the sample
+ *             lists that waits for the next solve keeps waiting.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message, `out` untouched: lk_track_points' for the sources (null configuration
+ *             or output; no committed sectors; CALLER without records or with n_frames < 1; ENGINE or WINDOW with records;
+ *             ENGINE with n_frames != 1, before any batch solve or with one in flight; WINDOW with an n_frames that is
+ *             neither 0 nor the window's, before any window or with one in flight; unknown source), and: unknown kind;
+ *             passes outside 1 .. 4; passes > 1 with reject <= 0; min_sectors below the kind's minimum (1, 2, 2, 3);
+ *             non-zero reserved words; reject or chi_max not finite; LK_FM_U with a kind other than TRANSLATION.
+ *   scope     one engine; records_out is a host array.  Not covered: composing the motions of a reference_previous window
+ *             into totals (each frame's motion is that of its own records), device-resident records_out, lk_group,
+ *             lk_tracker, the report CSV and the CudaClass adapter. */
+enum { LK_MOTION_TRANSLATION = 0, LK_MOTION_RIGID = 1, LK_MOTION_SIMILARITY = 2, LK_MOTION_AFFINE = 3 };
+enum { LK_MOTION_OK = 0, LK_MOTION_TOO_FEW = 1, LK_MOTION_DEGENERATE = 2 };
+typedef struct lk_motion_config {
+  int   kind;          /* LK_MOTION_* */
+  int   source;        /* LK_TRACK_RECORDS_CALLER / _ENGINE / _WINDOW, with lk_track_points' rules and refusals */
+  float chi_max;       /* the shared good rule; <= 0: the error code alone decides */
+  float reject;        /* > 0: pass k > 0 leaves out sectors whose residual to pass k-1's fit exceeds reject * rms of pass k-1; <= 0: no trimming */
+  int   passes;        /* 1..4; > 1 requires reject > 0 */
+  int   min_sectors;   /* >= 1 / 2 / 2 / 3 for the four kinds */
+  int   reserved[2];   /* must be 0 */
+} lk_motion_config;
+typedef struct lk_motion {      /* 64 bytes, one per frame, of the last pass */
+  float cx, cy;                 /* centroid of the fit set, level-0 pixels */
+  float tx, ty;                 /* displacement of that centroid */
+  float axx, axy, ayx, ayy;     /* linear part A: I, R, sR or the affine matrix */
+  float theta, scale;           /* atan2(ayx - axy, axx + ayy); sqrt(|det A|) */
+  float rms, max_residual;      /* of |x'_j - (c + t + A (x_j - c))| over the fit set, pixels */
+  int32_t n_fit, n_rejected, status, passes_run;  /* sectors fitted; sectors the last pass trimmed; LK_MOTION_*; passes that ran */
+} lk_motion;
+/* records: host [n_frames][S] or NULL (see `records`); fit_mask: host [S] or NULL; out: [n_frames] (source WINDOW with
+ * n_frames = 0: the window's frame count); records_out: host [n_frames][S] or NULL; sums_out: [n_frames][12] doubles or NULL.
+ * Synchronous.  Changes no engine state. */
+int lk_rigid_motion(lk_engine *e, const lk_motion_config *cfg, int n_frames, const lk_result *records,
+                    const uint8_t *fit_mask, lk_motion *out, lk_result *records_out, double *sums_out);
+/* the kernel's own fit compiled for the host (csrc/lk_motion.hpp): the count n and the eleven sums of the `sums` paragraph
+ * relative to origin_xy = {ox, oy} -> the record.  rms, max_residual, n_rejected and passes_run, which the sums do not hold,
+ * are 0.  LK_ERROR_BAD_DOMAIN for a null pointer, n < 0, an unknown kind or a min_sectors below the kind's minimum. */
+int lk_motion_from_sums(int kind, int min_sectors, int n, const double *sums11, const double *origin_xy, lk_motion *out);
+/* the displacement field of a motion at n positions, host, in double: d(x) = t + (A - I)(x - c) from the motion's float
+ * fields, uv_out[2 i ..] rounded to float once; zeros for a motion that is not OK.  LK_ERROR_BAD_DOMAIN for a null pointer
+ * or n < 1. */
+int lk_motion_apply(const lk_motion *m, int n, const float *xy, float *uv_out);
+/* the kernel's own removal of one record compiled for the host (the `removal` paragraph): `in` at the centre (cx, cy) ->
+ * `out`.  The caller applies the good rule; a motion that is not OK copies the record.  LK_ERROR_BAD_DOMAIN for a null
+ * pointer, an unknown model, LK_FM_U with an A that is not the identity, or an A without an inverse (out untouched). */
+int lk_motion_remove(int model, const lk_motion *m, float cx, float cy, const lk_result *in, lk_result *out);
+
 /* ---- photometry and the back-warped residual map: the grey values once more ---------------- */
 /* chi is a plain sum of squared grey-level differences: a frame that is 20 % darker gives every sector a large chi although
  * the match is perfect.  lk_photometry evaluates every good sector once at its record's parameters and reports the

@@ -122,6 +122,26 @@ def run_track():
     return out
 
 
+def run_motion():
+    import correlation_amd as ca
+    e, rec = solved("grid", ca.FM_UVUXUYVXVY, ca.IM_BICUBIC)
+    frames = np.stack([rec.copy() for _ in range(3)])
+    for f in range(3):   # frame f: f + 1 times the solved field
+        frames["p"][f] *= np.float32(f + 1)
+    frames["error_code"][1][60:64] = 3
+    frames["p"][2][[88, 301], 0] += 5.0   # two sectors for the second pass to trim
+    mask = np.arange(e.n_sectors) % 24 < 6
+    out = {}
+    for kind, name in enumerate(("translation", "rigid", "similarity", "affine")):
+        for tag, kw in (("", {}), ("_masked", dict(fit_mask=mask)), ("_trimmed", dict(reject=3.0, passes=2)),
+                        ("_too_few", dict(min_sectors=e.n_sectors + 1))):
+            m, removed, sums = e.rigid_motion(kind, records=frames, return_records=True, return_sums=True, **kw)
+            out.update(fields("motion_" + name + tag, m))
+            out.update(fields("motion_" + name + tag + ".records", removed))
+            out["motion_" + name + tag + ".sums"] = sums
+    return out
+
+
 def run_plan():
     import correlation_amd as ca
     out = {}
@@ -435,6 +455,7 @@ VARIANTS += [("outlier_g%d_cap%s" % (g, cap), {"LK_OUTLIER_GROUP": str(g), "LK_O
              for g in (16, 64) for cap in ("0", "100000")]
 VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (16, 64)]
 VARIANTS += [("field_walk%d" % w, {"LK_FIELD_WALK": str(w)}, run_field) for w in (0, 1)]
+VARIANTS += [("motion_chunk%d" % c, {"LK_MOTION_CHUNK": str(c)}, run_motion) for c in (64, 2048)]
 VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
              ("pattern", {}, run_pattern), ("znssd", {}, run_znssd), ("quadratic", {}, run_quadratic),
              ("spline", {}, run_spline), ("weighted", {}, run_weighted), ("composed", {}, run_composed)]
