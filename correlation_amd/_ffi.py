@@ -42,6 +42,17 @@ class LkStats(C.Structure):
                 ("pyramid_ms", C.c_float), ("window_safe_reruns", C.c_uint64)]
 
 
+# launch report (include/lk_engine.h: lk_get_launch_report)
+(LAUNCH_MAIN, LAUNCH_STARVED, LAUNCH_FINISHER, LAUNCH_SAFE_PASS, LAUNCH_EVAL) = range(5)
+FLAVOUR_FAST, FLAVOUR_SAFE, FLAVOUR_REFERENCE = range(3)
+LAUNCH_REPORT_CAPACITY = 64
+
+
+class LkLaunchRecord(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("model", "interp", "group", "threads", "flavour", "seq", "role", "sectors", "team_w",
+                                       "persistent", "grid", "reserved")]
+
+
 # automatic initial guess (include/lk_engine.h: lk_search_guesses)
 GS_OK, GS_TEXTURELESS, GS_NO_CANDIDATE, GS_TOO_FEW, GS_TOO_LARGE, GS_WEAK = range(6)
 GS_MAX_RADIUS = 32
@@ -452,6 +463,8 @@ SYMBOLS = {
     "lk_reduce_compare": (C.c_int, [_P, C.c_int, C.c_int, _F, _F]),
     "lk_get_stats": (C.c_int, [_P, C.POINTER(LkStats)]),
     "lk_get_sector_stats": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "lk_get_launch_report": (C.c_int, [_P, C.POINTER(LkLaunchRecord), C.c_int, _I, _I]),
+    "lk_get_sector_groups": (C.c_int, [_P, _I, _I]),
     # include/lk_tracker.h
     "lk_tracker_create": (C.c_int, [_P, C.POINTER(_P)]),
     "lk_tracker_destroy": (None, [_P]),

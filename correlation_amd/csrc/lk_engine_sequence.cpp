@@ -242,7 +242,7 @@ static int launch_window(lk_engine *e) {
       }
       a.safe = flavour != 0;
       const int group = seq_group_of_class(e, c, nc);
-      HIPCHK(lk_launch_solve_seq(a, e->cfg.fitting_model, e->cfg.interpolation, group, flavour, st));
+      HIPCHK(lk_launch_solve_seq(a, e->cfg.fitting_model, e->cfg.interpolation, group, flavour, st, e->launch_report_slot()));
       if (int rc = fork.join(c, st))
         return rc;
       if (flavour == 0)
@@ -261,7 +261,7 @@ static int launch_window(lk_engine *e) {
         sp.a.seq_flags = e->d_seq_flags.p + 2;
         sp.a.seq_gate = e->d_seq_flags.p + 1;
         sp.a.safe = 1;
-        HIPCHK(lk_launch_solve_seq(sp.a, e->cfg.fitting_model, e->cfg.interpolation, sp.group, 1, e->stream));
+        HIPCHK(lk_launch_solve_seq(sp.a, e->cfg.fitting_model, e->cfg.interpolation, sp.group, 1, e->stream, e->launch_report_slot()));
       }
     }
     // reference-order mode: the stale iteration counts, in the order the reference solves - frame by frame, sector by

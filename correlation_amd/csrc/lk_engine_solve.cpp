@@ -89,13 +89,13 @@ static int launch_starved(lk_engine *e, LkSolveArgs &a, int c, int first, hipStr
   a.finish_count = e->d_finish_count.p + c;
   if (a.eval_cap > 0)
     HIPCHK(hipMemsetAsync(a.finish_count, 0, sizeof(uint32_t), st));
-  HIPCHK(lk_launch_solve(a, e->cfg.fitting_model, e->cfg.interpolation, 1, st));
+  HIPCHK(lk_launch_solve(a, e->cfg.fitting_model, e->cfg.interpolation, 1, st, e->launch_report_slot()));
   if (a.eval_cap > 0) {
     LkSolveArgs f = a;
     f.finisher = 1;
     f.safe = 1;
     f.align = 0; // one trip per evaluation whatever the level: rows take the next parked sector as they finish
-    HIPCHK(lk_launch_solve(f, e->cfg.fitting_model, e->cfg.interpolation, 16, st));
+    HIPCHK(lk_launch_solve(f, e->cfg.fitting_model, e->cfg.interpolation, 16, st, e->launch_report_slot()));
   }
   a.eval_cap = 0;
   return LK_ERROR_NONE;
@@ -112,7 +112,7 @@ static int launch_groups(lk_engine *e, LkSolveArgs &a, int group, int c, int fir
     a.ill_list = e->d_ill_list.p + first;
     a.ill_count = e->d_ill_count.p + c; // (rewound by the SAFE pass itself)
   }
-  HIPCHK(lk_launch_solve(a, e->cfg.fitting_model, e->cfg.interpolation, group, st));
+  HIPCHK(lk_launch_solve(a, e->cfg.fitting_model, e->cfg.interpolation, group, st, e->launch_report_slot()));
   if (with_ill_pass) {
     LkSolveArgs r = a;
     r.resume = 1;
@@ -124,7 +124,7 @@ static int launch_groups(lk_engine *e, LkSolveArgs &a, int group, int c, int fir
     r.team_w = 0;
     r.handoff = nullptr;
     r.queue = a.queue + 3;
-    HIPCHK(lk_launch_solve(r, e->cfg.fitting_model, e->cfg.interpolation, 16, st));
+    HIPCHK(lk_launch_solve(r, e->cfg.fitting_model, e->cfg.interpolation, 16, st, e->launch_report_slot()));
   }
   return LK_ERROR_NONE;
 }
@@ -199,8 +199,9 @@ int ClassFork::join(int c, hipStream_t st) {
 }
 
 // What brackets every solve: the timing events on the engine's stream and, behind it, what lk_get_stats needs to know
-// about the counters - how many frames they cover and which update wrote them.
+// about the counters - how many frames they cover and which update wrote them.  The launch report starts over with it.
 int solve_begin(lk_engine *e) {
+  e->launch_report_begin(); // (lk_get_launch_report describes the call that starts here)
   if (e->timing)
     HIPCHK(hipEventRecord(e->ev_s0, e->stream));
   return LK_ERROR_NONE;
@@ -221,6 +222,11 @@ int solve_end(lk_engine *e, int stats_frames, int stats_update) {
 // per sector then shortens every sector's chain, beyond that the wavefronts' throughput wins.
 int reference_group_of_class(int c, int n) {
   return c == 0 ? 16 : (c >= kTeamClass - 1 || (c == kTeamClass - 2 && n <= 256)) ? 512 : 64;
+}
+// number_of_threads = T > 1 on the `n` sectors of one of the two big classes: the team width T the batch asks for (0: none)
+static int reference_team_of_class(const lk_engine *e, int c, int n) {
+  const int T = e->reference_order;
+  return c >= kTeamClass - 1 && T > 1 && T <= kLkMaxTeam && (long long)n * T <= 256 && !e->batch_invariant ? T : 0;
 }
 // ... and a single sector (lk_correlate, lk_evaluate).  NOT the batch rule, and not to be merged with it: a lone sector
 // never gets a workgroup or a team, whatever its class.
@@ -373,9 +379,7 @@ int launch_all(lk_engine *e, const float *d_guess, lk_result *d_result, const Lk
       a.reference_order = e->reference_order;
       // number_of_threads = T > 1 on the big classes: a TEAM of T workgroups per sector, one thread chunk of the reference
       // each (the launch falls back to one workgroup per sector when T x sectors are not all resident at once)
-      if (c >= kTeamClass - 1 && e->reference_order > 1 && e->reference_order <= kLkMaxTeam && (long long)n * e->reference_order <= 256 &&
-          !e->batch_invariant) {
-        const int T = e->reference_order;
+      if (const int T = reference_team_of_class(e, c, n)) {
         HIPCHK(e->d_team_partials.ensure((size_t)n * 2 * (size_t)T * 32));
         HIPCHK(e->d_team_arrivals.ensure(2 * (size_t)n));
         a.team_w = T;
@@ -386,7 +390,7 @@ int launch_all(lk_engine *e, const float *d_guess, lk_result *d_result, const Lk
         if (int rc = team_turn.take(e, st))
           return rc;
       }
-      HIPCHK(lk_launch_solve(a, e->cfg.fitting_model, e->cfg.interpolation, reference_group_of_class(c, n), st));
+      HIPCHK(lk_launch_solve(a, e->cfg.fitting_model, e->cfg.interpolation, reference_group_of_class(c, n), st, e->launch_report_slot()));
     } else {
       if (e->team_share_permille > 0 && (c == kTeamClass || c == kTeamClass - 1))
         a.slots_permille = c == kTeamClass ? e->team_share_permille : 1000 - e->team_share_permille;
@@ -560,7 +564,8 @@ int lk_correlate(lk_engine *e, int sector, float *guess_inout, lk_result *out) {
       a.reference_order = e->reference_order;
       if ((rc = solve_begin(e)))
         return rc;
-      HIPCHK(lk_launch_solve(a, e->cfg.fitting_model, e->cfg.interpolation, reference_group_of_sector(e, sector), e->stream));
+      HIPCHK(lk_launch_solve(a, e->cfg.fitting_model, e->cfg.interpolation, reference_group_of_sector(e, sector), e->stream,
+                             e->launch_report_slot()));
       if ((rc = stale_iterations(e, e->d_result.p + sector, 1)))
         return rc;
     } else {
@@ -590,6 +595,34 @@ int lk_correlate(lk_engine *e, int sector, float *guess_inout, lk_result *out) {
   HIPCHK(hipStreamSynchronize(e->stream));
   for (int i = 0; i < e->P; ++i)
     guess_inout[i] = out->resultingParameters[i]; // cuda_class.cu:289-290
+  return LK_ERROR_NONE;
+}
+
+int lk_get_launch_report(lk_engine *e, lk_launch_record *out, int capacity, int *n_out, int *overflow) {
+  if (!e || !n_out || (out && capacity < 0))
+    return LK_ERROR_BAD_DOMAIN;
+  const int kept = std::min(e->launch_report_n, (int)LK_LAUNCH_REPORT_CAPACITY);
+  *n_out = kept;
+  if (overflow)
+    *overflow = e->launch_report_n > LK_LAUNCH_REPORT_CAPACITY ? 1 : 0;
+  if (out)
+    std::memcpy(out, e->launch_report, (size_t)std::min(kept, capacity) * sizeof(lk_launch_record));
+  return LK_ERROR_NONE;
+}
+
+int lk_get_sector_groups(lk_engine *e, int *groups, int *team_w) {
+  if (!e || !groups)
+    return LK_ERROR_BAD_DOMAIN;
+  if (!e->committed)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_get_sector_groups: sectors are not committed");
+  if (e->recommit_pending || e->classes_dirty) // (read-only: the pending work belongs to the next solve, not to a query)
+    return e->fail(LK_ERROR_BAD_DOMAIN, "lk_get_sector_groups: sectors were appended or moved since the last batch solve; the classes are stale");
+  for (int s = 0; s < e->S; ++s) {
+    const int c = e->h_class[(size_t)s], n = e->class_begin[c + 1] - e->class_begin[c];
+    groups[s] = e->reference_order > 0 ? reference_group_of_class(c, n) : kGroupOfClass[c];
+    if (team_w)
+      team_w[s] = e->reference_order > 0 ? (groups[s] == 512 ? reference_team_of_class(e, c, n) : 0) : c == kTeamClass ? e->team_w : 0;
+  }
   return LK_ERROR_NONE;
 }
 
@@ -658,7 +691,8 @@ int lk_evaluate(lk_engine *e, int sector, int level, const float *p, float *A36,
   a.out = e->d_scratch.p;
   a.ref_threads = e->reference_order;
   const int group = e->reference_order > 0 ? reference_group_of_sector(e, sector) : kGroupOfClass[e->h_class[(size_t)sector]];
-  HIPCHK(lk_launch_eval(a, e->cfg.fitting_model, e->cfg.interpolation, group, e->stream));
+  e->launch_report_begin();
+  HIPCHK(lk_launch_eval(a, e->cfg.fitting_model, e->cfg.interpolation, group, e->stream, e->launch_report_slot()));
   return evaluation_out(e, A36, b6, chi, error);
 }
 

@@ -306,6 +306,15 @@ struct lk_engine {
   int records_S = 0;        // sectors the engine-held records of a batch solve cover (0: no solve since the commit)
   int window_S = 0;         // sectors the device records of the last window cover (0: no window since the commit; lk_track_points)
   LkPassSlot *pass[LK_PASS_COUNT] = {}; // what the add-on passes keep between their calls (lk_pass.hpp), deleted by lk_destroy
+  // lk_get_launch_report: the launches of the most recent solving call, in the order the host issued them.  Fixed capacity:
+  // a launch past it is counted and not kept (its record goes to the spare slot at the end).
+  lk_launch_record launch_report[LK_LAUNCH_REPORT_CAPACITY + 1] = {};
+  int launch_report_n = 0; // launches of the call so far (may exceed the capacity)
+  void launch_report_begin() { launch_report_n = 0; }
+  lk_launch_record *launch_report_slot() {
+    const int i = launch_report_n++;
+    return &launch_report[i < LK_LAUNCH_REPORT_CAPACITY ? i : LK_LAUNCH_REPORT_CAPACITY];
+  }
 
   int fail(int code, const std::string &what) {
     err = what;

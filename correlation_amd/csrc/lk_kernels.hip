@@ -3588,8 +3588,29 @@ template <class K> static int resident_workgroups(K kernel, int threads) {
 // for that launch's end (measured on config 3: 0.61 ms with 96 + 160 workgroups, 0.98 with 108 + 147).
 static int split_slots(int all, int team_permille) { return (int)((long long)all * team_permille / 1000) & ~7; }
 
+// What lk_get_launch_report tells about a launch: the instance and what the launcher decided, stored where it is decided
+// (a null `rep` costs the test alone; the engine hands in a slot of its fixed array).
+static inline void report_launch(lk_launch_record *rep, int model, int interp, int group, int threads, int flavour, int seq,
+                                 const LkSolveArgs &b, int grid) {
+  if (!rep)
+    return;
+  rep->model = model;
+  rep->interp = interp;
+  rep->group = group;
+  rep->threads = threads;
+  rep->flavour = flavour;
+  rep->seq = seq;
+  rep->role = group == 1 ? LK_LAUNCH_STARVED : b.finisher ? LK_LAUNCH_FINISHER : (b.resume || b.seq_gate) ? LK_LAUNCH_SAFE_PASS : LK_LAUNCH_MAIN;
+  rep->sectors = b.n_sectors;
+  rep->team_w = b.team_w;
+  rep->persistent = b.persistent;
+  rep->grid = grid;
+  rep->reserved = 0;
+}
+
 template <int MODEL, int INTERP, int GROUP, int THREADS, bool SAFE, bool REF = false>
-static hipError_t launch_solve_gs(const LkSolveArgs &a, hipStream_t st) {
+static hipError_t launch_solve_gs(const LkSolveArgs &a, hipStream_t st, lk_launch_record *rep) {
+  constexpr int kFlavour = REF ? LK_FLAVOUR_REFERENCE : SAFE ? LK_FLAVOUR_SAFE : LK_FLAVOUR_FAST;
   static std::atomic<int> resident_cache{0}; // per template instance (one device type per process); engines launch from several threads
   int resident = resident_cache.load(std::memory_order_relaxed);
   if (resident == 0) {
@@ -3616,6 +3637,7 @@ static hipError_t launch_solve_gs(const LkSolveArgs &a, hipStream_t st) {
     b.persistent = 1;
     b.chunk = 0;
     const int grid = want < 128 ? want : 128;
+    report_launch(rep, MODEL, INTERP, GROUP, THREADS, kFlavour, 0, b, grid);
     hipLaunchKernelGGL((lk_solve_kernel<MODEL, INTERP, GROUP, THREADS, SAFE>), dim3((unsigned)grid), dim3(THREADS), 0,
                        st, b);
     return hipGetLastError();
@@ -3628,6 +3650,7 @@ static hipError_t launch_solve_gs(const LkSolveArgs &a, hipStream_t st) {
     hipError_t qe = hipMemsetAsync(a.queue, 0, sizeof(uint32_t), st);
     if (qe != hipSuccess)
       return qe;
+    report_launch(rep, MODEL, INTERP, GROUP, THREADS, kFlavour, 0, b, want < resident ? want : resident);
     hipLaunchKernelGGL((lk_solve_kernel<MODEL, INTERP, GROUP, THREADS, SAFE>),
                        dim3((unsigned)(want < resident ? want : resident)), dim3(THREADS), 0, st, b);
     return hipGetLastError();
@@ -3647,6 +3670,7 @@ static hipError_t launch_solve_gs(const LkSolveArgs &a, hipStream_t st) {
         return te;
       b.persistent = 0;
       b.chunk = 0;
+      report_launch(rep, MODEL, INTERP, GROUP, THREADS, kFlavour, 0, b, a.n_sectors * b.team_w);
       hipLaunchKernelGGL((lk_solve_kernel<MODEL, INTERP, GROUP, THREADS, SAFE, REF>),
                          dim3((unsigned)(a.n_sectors * b.team_w)), dim3(THREADS), 0, st, b);
       return hipGetLastError();
@@ -3669,6 +3693,7 @@ static hipError_t launch_solve_gs(const LkSolveArgs &a, hipStream_t st) {
       return qe;
   }
   dim3 grid((unsigned)(b.persistent ? grid_persistent : 8 * b.chunk));
+  report_launch(rep, MODEL, INTERP, GROUP, THREADS, kFlavour, 0, b, (int)grid.x);
   hipLaunchKernelGGL((lk_solve_kernel<MODEL, INTERP, GROUP, THREADS, SAFE, REF>), grid, dim3(THREADS), 0, st, b);
   return hipGetLastError();
 }
@@ -3678,51 +3703,51 @@ static hipError_t launch_solve_gs(const LkSolveArgs &a, hipStream_t st) {
 // flavour zeroes the step of a parameter whose pivot is bad.  Starved levels never get here:
 // the GROUP == 1 kernel solves them first.
 template <int MODEL, int INTERP, int GROUP, int THREADS>
-static hipError_t launch_solve_g(const LkSolveArgs &a, hipStream_t st) {
+static hipError_t launch_solve_g(const LkSolveArgs &a, hipStream_t st, lk_launch_record *rep) {
   if constexpr ((THREADS == kWave && (GROUP == 16 || GROUP == kWave)) || (THREADS == 512 && GROUP == 512)) {
     if (a.reference_order > 0) // the reference-order instances
-      return launch_solve_gs<MODEL, INTERP, GROUP, THREADS, true, true>(a, st);
+      return launch_solve_gs<MODEL, INTERP, GROUP, THREADS, true, true>(a, st, rep);
   }
-  return a.safe ? launch_solve_gs<MODEL, INTERP, GROUP, THREADS, true>(a, st)
-                : launch_solve_gs<MODEL, INTERP, GROUP, THREADS, false>(a, st);
+  return a.safe ? launch_solve_gs<MODEL, INTERP, GROUP, THREADS, true>(a, st, rep)
+                : launch_solve_gs<MODEL, INTERP, GROUP, THREADS, false>(a, st, rep);
 }
 
 template <int MODEL, int INTERP>
-static hipError_t launch_solve_mi(const LkSolveArgs &a, int group, hipStream_t st) {
+static hipError_t launch_solve_mi(const LkSolveArgs &a, int group, hipStream_t st, lk_launch_record *rep) {
   switch (group) {
-  case 1: return launch_solve_gs<MODEL, INTERP, 1, 64, false>(a, st); // starved levels, one lane per sector
-  case 16: return launch_solve_g<MODEL, INTERP, 16, 64>(a, st);
-  case 32: return launch_solve_g<MODEL, INTERP, 32, 64>(a, st);
-  case 64: return launch_solve_g<MODEL, INTERP, 64, 64>(a, st);
-  case 256: return launch_solve_g<MODEL, INTERP, 256, 256>(a, st);
-  default: return launch_solve_g<MODEL, INTERP, 512, 512>(a, st);
+  case 1: return launch_solve_gs<MODEL, INTERP, 1, 64, false>(a, st, rep); // starved levels, one lane per sector
+  case 16: return launch_solve_g<MODEL, INTERP, 16, 64>(a, st, rep);
+  case 32: return launch_solve_g<MODEL, INTERP, 32, 64>(a, st, rep);
+  case 64: return launch_solve_g<MODEL, INTERP, 64, 64>(a, st, rep);
+  case 256: return launch_solve_g<MODEL, INTERP, 256, 256>(a, st, rep);
+  default: return launch_solve_g<MODEL, INTERP, 512, 512>(a, st, rep);
   }
 }
 
 // LK_TUNE_ONLY_AFFINE_BICUBIC (kernel tuning builds, scripts/tune_build.sh): instantiate the solve
 // kernel for the affine model with the reference bicubic only - a 15 s build instead of 90 s
 template <int MODEL>
-static hipError_t launch_solve_m(const LkSolveArgs &a, int interp, int group, hipStream_t st) {
+static hipError_t launch_solve_m(const LkSolveArgs &a, int interp, int group, hipStream_t st, lk_launch_record *rep) {
   switch (interp) {
 #ifndef LK_TUNE_ONLY_AFFINE_BICUBIC
-  case LK_IM_NEAREST: return launch_solve_mi<MODEL, LK_IM_NEAREST>(a, group, st);
-  case LK_IM_BILINEAR: return launch_solve_mi<MODEL, LK_IM_BILINEAR>(a, group, st);
-  case LK_IM_BICUBIC_SEPARABLE: return launch_solve_mi<MODEL, LK_IM_BICUBIC_SEPARABLE>(a, group, st);
+  case LK_IM_NEAREST: return launch_solve_mi<MODEL, LK_IM_NEAREST>(a, group, st, rep);
+  case LK_IM_BILINEAR: return launch_solve_mi<MODEL, LK_IM_BILINEAR>(a, group, st, rep);
+  case LK_IM_BICUBIC_SEPARABLE: return launch_solve_mi<MODEL, LK_IM_BICUBIC_SEPARABLE>(a, group, st, rep);
 #endif
-  default: return launch_solve_mi<MODEL, LK_IM_BICUBIC>(a, group, st);
+  default: return launch_solve_mi<MODEL, LK_IM_BICUBIC>(a, group, st, rep);
   }
 }
 
-hipError_t lk_launch_solve(const LkSolveArgs &a, int model, int interp, int group, hipStream_t st) {
+hipError_t lk_launch_solve(const LkSolveArgs &a, int model, int interp, int group, hipStream_t st, lk_launch_record *rep) {
   if (a.n_sectors <= 0)
     return hipSuccess;
   switch (model) {
 #ifndef LK_TUNE_ONLY_AFFINE_BICUBIC
-  case LK_FM_U: return launch_solve_m<LK_FM_U>(a, interp, group, st);
-  case LK_FM_UV: return launch_solve_m<LK_FM_UV>(a, interp, group, st);
-  case LK_FM_UVQ: return launch_solve_m<LK_FM_UVQ>(a, interp, group, st);
+  case LK_FM_U: return launch_solve_m<LK_FM_U>(a, interp, group, st, rep);
+  case LK_FM_UV: return launch_solve_m<LK_FM_UV>(a, interp, group, st, rep);
+  case LK_FM_UVQ: return launch_solve_m<LK_FM_UVQ>(a, interp, group, st, rep);
 #endif
-  default: return launch_solve_m<LK_FM_UVUXUYVXVY>(a, interp, group, st);
+  default: return launch_solve_m<LK_FM_UVUXUYVXVY>(a, interp, group, st, rep);
   }
 }
 
@@ -3731,7 +3756,7 @@ hipError_t lk_launch_solve(const LkSolveArgs &a, int model, int interp, int grou
 // wavefronts than are resident (more would not hurt - a wavefront that is not running holds no ticket - but would queue
 // behind the grid for nothing).
 template <int MODEL, int INTERP, int GROUP, bool SAFE, bool REF>
-static hipError_t launch_solve_seq_gs(const LkSolveArgs &a, hipStream_t st) {
+static hipError_t launch_solve_seq_gs(const LkSolveArgs &a, hipStream_t st, lk_launch_record *rep) {
   static std::atomic<int> resident_cache{0};
   int resident = resident_cache.load(std::memory_order_relaxed);
   if (resident == 0) {
@@ -3776,6 +3801,7 @@ static hipError_t launch_solve_seq_gs(const LkSolveArgs &a, hipStream_t st) {
   hipError_t qe = hipMemsetAsync(a.queue, 0, sizeof(uint32_t), st);
   if (qe != hipSuccess)
     return qe;
+  report_launch(rep, MODEL, INTERP, GROUP, kWave, REF ? LK_FLAVOUR_REFERENCE : SAFE ? LK_FLAVOUR_SAFE : LK_FLAVOUR_FAST, 1, b, grid);
   hipLaunchKernelGGL((lk_solve_kernel<MODEL, INTERP, GROUP, kWave, SAFE, REF, true>), dim3((unsigned)grid), dim3(kWave), 0, st, b);
   return hipGetLastError();
 }
@@ -3784,84 +3810,92 @@ static hipError_t launch_solve_seq_gs(const LkSolveArgs &a, hipStream_t st) {
 // (the QR inside the kernel; 16-lane rows: starved levels with the finisher's arithmetic), 2 reference order
 // (a.reference_order = T)
 template <int MODEL, int INTERP>
-static hipError_t launch_solve_seq_mi(const LkSolveArgs &a, int group, int flavour, hipStream_t st) {
+static hipError_t launch_solve_seq_mi(const LkSolveArgs &a, int group, int flavour, hipStream_t st, lk_launch_record *rep) {
   if (flavour == 2) {
     switch (group) {
-    case 16: return launch_solve_seq_gs<MODEL, INTERP, 16, true, true>(a, st);
-    case 64: return launch_solve_seq_gs<MODEL, INTERP, 64, true, true>(a, st);
+    case 16: return launch_solve_seq_gs<MODEL, INTERP, 16, true, true>(a, st, rep);
+    case 64: return launch_solve_seq_gs<MODEL, INTERP, 64, true, true>(a, st, rep);
     default: return hipErrorInvalidValue;
     }
   }
   if (flavour == 1) {
     switch (group) {
-    case 16: return launch_solve_seq_gs<MODEL, INTERP, 16, true, false>(a, st);
-    case 32: return launch_solve_seq_gs<MODEL, INTERP, 32, true, false>(a, st);
-    case 64: return launch_solve_seq_gs<MODEL, INTERP, 64, true, false>(a, st);
+    case 16: return launch_solve_seq_gs<MODEL, INTERP, 16, true, false>(a, st, rep);
+    case 32: return launch_solve_seq_gs<MODEL, INTERP, 32, true, false>(a, st, rep);
+    case 64: return launch_solve_seq_gs<MODEL, INTERP, 64, true, false>(a, st, rep);
     default: return hipErrorInvalidValue;
     }
   }
   switch (group) {
-  case 16: return launch_solve_seq_gs<MODEL, INTERP, 16, false, false>(a, st);
-  case 32: return launch_solve_seq_gs<MODEL, INTERP, 32, false, false>(a, st);
-  case 64: return launch_solve_seq_gs<MODEL, INTERP, 64, false, false>(a, st);
+  case 16: return launch_solve_seq_gs<MODEL, INTERP, 16, false, false>(a, st, rep);
+  case 32: return launch_solve_seq_gs<MODEL, INTERP, 32, false, false>(a, st, rep);
+  case 64: return launch_solve_seq_gs<MODEL, INTERP, 64, false, false>(a, st, rep);
   default: return hipErrorInvalidValue;
   }
 }
 
 template <int MODEL>
-static hipError_t launch_solve_seq_m(const LkSolveArgs &a, int interp, int group, int flavour, hipStream_t st) {
+static hipError_t launch_solve_seq_m(const LkSolveArgs &a, int interp, int group, int flavour, hipStream_t st, lk_launch_record *rep) {
   switch (interp) {
 #ifndef LK_TUNE_ONLY_AFFINE_BICUBIC
-  case LK_IM_NEAREST: return launch_solve_seq_mi<MODEL, LK_IM_NEAREST>(a, group, flavour, st);
-  case LK_IM_BILINEAR: return launch_solve_seq_mi<MODEL, LK_IM_BILINEAR>(a, group, flavour, st);
-  case LK_IM_BICUBIC_SEPARABLE: return launch_solve_seq_mi<MODEL, LK_IM_BICUBIC_SEPARABLE>(a, group, flavour, st);
+  case LK_IM_NEAREST: return launch_solve_seq_mi<MODEL, LK_IM_NEAREST>(a, group, flavour, st, rep);
+  case LK_IM_BILINEAR: return launch_solve_seq_mi<MODEL, LK_IM_BILINEAR>(a, group, flavour, st, rep);
+  case LK_IM_BICUBIC_SEPARABLE: return launch_solve_seq_mi<MODEL, LK_IM_BICUBIC_SEPARABLE>(a, group, flavour, st, rep);
 #endif
-  default: return launch_solve_seq_mi<MODEL, LK_IM_BICUBIC>(a, group, flavour, st);
+  default: return launch_solve_seq_mi<MODEL, LK_IM_BICUBIC>(a, group, flavour, st, rep);
   }
 }
 
-hipError_t lk_launch_solve_seq(const LkSolveArgs &a, int model, int interp, int group, int flavour, hipStream_t st) {
+hipError_t lk_launch_solve_seq(const LkSolveArgs &a, int model, int interp, int group, int flavour, hipStream_t st,
+                               lk_launch_record *rep) {
   if (a.n_sectors <= 0 || a.seq_frames <= 0)
     return hipSuccess;
   if ((long long)a.n_sectors * a.seq_frames >= (1ll << 31) - (1ll << 20)) // (tickets are ints; the grid draws a few past the end)
     return hipErrorInvalidValue;
   switch (model) {
 #ifndef LK_TUNE_ONLY_AFFINE_BICUBIC
-  case LK_FM_U: return launch_solve_seq_m<LK_FM_U>(a, interp, group, flavour, st);
-  case LK_FM_UV: return launch_solve_seq_m<LK_FM_UV>(a, interp, group, flavour, st);
-  case LK_FM_UVQ: return launch_solve_seq_m<LK_FM_UVQ>(a, interp, group, flavour, st);
+  case LK_FM_U: return launch_solve_seq_m<LK_FM_U>(a, interp, group, flavour, st, rep);
+  case LK_FM_UV: return launch_solve_seq_m<LK_FM_UV>(a, interp, group, flavour, st, rep);
+  case LK_FM_UVQ: return launch_solve_seq_m<LK_FM_UVQ>(a, interp, group, flavour, st, rep);
 #endif
-  default: return launch_solve_seq_m<LK_FM_UVUXUYVXVY>(a, interp, group, flavour, st);
+  default: return launch_solve_seq_m<LK_FM_UVUXUYVXVY>(a, interp, group, flavour, st, rep);
   }
 }
 
-template <int MODEL, int GROUP>
-static hipError_t launch_eval_mg(const LkEvalArgs &a, int interp, hipStream_t st) {
-  switch (interp) {
-  case LK_IM_NEAREST: hipLaunchKernelGGL((lk_eval_kernel<MODEL, LK_IM_NEAREST, GROUP>), dim3(1), dim3(256), 0, st, a); break;
-  case LK_IM_BILINEAR: hipLaunchKernelGGL((lk_eval_kernel<MODEL, LK_IM_BILINEAR, GROUP>), dim3(1), dim3(256), 0, st, a); break;
-  case LK_IM_BICUBIC_SEPARABLE: hipLaunchKernelGGL((lk_eval_kernel<MODEL, LK_IM_BICUBIC_SEPARABLE, GROUP>), dim3(1), dim3(256), 0, st, a); break;
-  default: hipLaunchKernelGGL((lk_eval_kernel<MODEL, LK_IM_BICUBIC, GROUP>), dim3(1), dim3(256), 0, st, a); break;
-  }
+template <int MODEL, int INTERP, int GROUP>
+static hipError_t launch_eval_mgi(const LkEvalArgs &a, hipStream_t st, lk_launch_record *rep) {
+  if (rep) // (one workgroup of 256 threads evaluates one sector; a.ref_threads > 0: the sums in the reference's order)
+    *rep = lk_launch_record{MODEL, INTERP, GROUP, 256, a.ref_threads > 0 ? LK_FLAVOUR_REFERENCE : LK_FLAVOUR_FAST, 0, LK_LAUNCH_EVAL, 1, 0, 0, 1, 0};
+  hipLaunchKernelGGL((lk_eval_kernel<MODEL, INTERP, GROUP>), dim3(1), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
-template <int MODEL>
-static hipError_t launch_eval_m(const LkEvalArgs &a, int interp, int group, hipStream_t st) {
-  switch (group) {
-  case 16: return launch_eval_mg<MODEL, 16>(a, interp, st);
-  case 32: return launch_eval_mg<MODEL, 32>(a, interp, st);
-  case 64: return launch_eval_mg<MODEL, 64>(a, interp, st);
-  default: return launch_eval_mg<MODEL, 256>(a, interp, st);
+template <int MODEL, int GROUP>
+static hipError_t launch_eval_mg(const LkEvalArgs &a, int interp, hipStream_t st, lk_launch_record *rep) {
+  switch (interp) {
+  case LK_IM_NEAREST: return launch_eval_mgi<MODEL, LK_IM_NEAREST, GROUP>(a, st, rep);
+  case LK_IM_BILINEAR: return launch_eval_mgi<MODEL, LK_IM_BILINEAR, GROUP>(a, st, rep);
+  case LK_IM_BICUBIC_SEPARABLE: return launch_eval_mgi<MODEL, LK_IM_BICUBIC_SEPARABLE, GROUP>(a, st, rep);
+  default: return launch_eval_mgi<MODEL, LK_IM_BICUBIC, GROUP>(a, st, rep);
   }
 }
 
-hipError_t lk_launch_eval(const LkEvalArgs &a, int model, int interp, int group, hipStream_t st) {
+template <int MODEL>
+static hipError_t launch_eval_m(const LkEvalArgs &a, int interp, int group, hipStream_t st, lk_launch_record *rep) {
+  switch (group) {
+  case 16: return launch_eval_mg<MODEL, 16>(a, interp, st, rep);
+  case 32: return launch_eval_mg<MODEL, 32>(a, interp, st, rep);
+  case 64: return launch_eval_mg<MODEL, 64>(a, interp, st, rep);
+  default: return launch_eval_mg<MODEL, 256>(a, interp, st, rep);
+  }
+}
+
+hipError_t lk_launch_eval(const LkEvalArgs &a, int model, int interp, int group, hipStream_t st, lk_launch_record *rep) {
   switch (model) {
-  case LK_FM_U: return launch_eval_m<LK_FM_U>(a, interp, group, st);
-  case LK_FM_UV: return launch_eval_m<LK_FM_UV>(a, interp, group, st);
-  case LK_FM_UVQ: return launch_eval_m<LK_FM_UVQ>(a, interp, group, st);
-  default: return launch_eval_m<LK_FM_UVUXUYVXVY>(a, interp, group, st);
+  case LK_FM_U: return launch_eval_m<LK_FM_U>(a, interp, group, st, rep);
+  case LK_FM_UV: return launch_eval_m<LK_FM_UV>(a, interp, group, st, rep);
+  case LK_FM_UVQ: return launch_eval_m<LK_FM_UVQ>(a, interp, group, st, rep);
+  default: return launch_eval_m<LK_FM_UVUXUYVXVY>(a, interp, group, st, rep);
   }
 }
 

@@ -9,11 +9,14 @@
 #include "lk_device.hpp"
 
 // ---- lk_kernels.hip: the forward solve and the known-answer entry points
-hipError_t lk_launch_solve(const LkSolveArgs &a, int model, int interp, int group, hipStream_t st);
+// rep (these three launchers): where to note the instance launched and what the launcher decided for it (lk_get_launch_report);
+// nullptr: nowhere
+hipError_t lk_launch_solve(const LkSolveArgs &a, int model, int interp, int group, hipStream_t st, lk_launch_record *rep = nullptr);
 // flavour: 0 fast (root-free Cholesky; a bad pivot raises the gate of the SAFE pass behind it), 1 SAFE (the QR inside the
 // kernel), 2 reference order (a.reference_order = T)
-hipError_t lk_launch_solve_seq(const LkSolveArgs &a, int model, int interp, int group, int flavour, hipStream_t st);
-hipError_t lk_launch_eval(const LkEvalArgs &a, int model, int interp, int group, hipStream_t st);
+hipError_t lk_launch_solve_seq(const LkSolveArgs &a, int model, int interp, int group, int flavour, hipStream_t st,
+                               lk_launch_record *rep = nullptr);
+hipError_t lk_launch_eval(const LkEvalArgs &a, int model, int interp, int group, hipStream_t st, lk_launch_record *rep = nullptr);
 hipError_t lk_launch_solve_only(int n, const float *d_in, float *d_out, hipStream_t st);
 hipError_t lk_launch_step_compare(int n, const float *d_in, float *d_out, hipStream_t st);
 hipError_t lk_launch_reduce_compare(int n, int wide, const float *d_in, float *d_out, hipStream_t st);

@@ -1019,3 +1019,22 @@ class HipCorrelationEngine:
         out = np.zeros((self.n_sectors, 4), np.uint32)
         self._chk(self.lib.lk_get_sector_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
+
+    def launch_report(self):
+        """The kernel launches of the most recent solving call (correlate, correlate_all*, a sequence window, evaluate) in
+        launch order: a list of dicts with the fields of lk_launch_record (include/lk_engine.h) but `reserved`.  Raises if
+        the call made more launches than the engine keeps."""
+        rec = (_ffi.LkLaunchRecord * _ffi.LAUNCH_REPORT_CAPACITY)()
+        n, over = C.c_int(), C.c_int()
+        self._chk(self.lib.lk_get_launch_report(self._h, rec, _ffi.LAUNCH_REPORT_CAPACITY, C.byref(n), C.byref(over)))
+        if over.value:
+            raise RuntimeError(f"launch report overflow: more than {_ffi.LAUNCH_REPORT_CAPACITY} launches in one call")
+        return [{k: getattr(rec[i], k) for k, _ in _ffi.LkLaunchRecord._fields_ if k != "reserved"} for i in range(n.value)]
+
+    def sector_groups(self):
+        """(groups, team_w), int32 [S] each: lanes per sector of the next one-pair batch solve and, for a sector of the team
+        class (512 lanes), the workgroups per sector the engine asks for (lk_get_sector_groups)."""
+        groups, team = np.zeros(self.n_sectors, np.int32), np.zeros(self.n_sectors, np.int32)
+        self._chk(self.lib.lk_get_sector_groups(self._h, groups.ctypes.data_as(C.POINTER(C.c_int)),
+                                                team.ctypes.data_as(C.POINTER(C.c_int))))
+        return groups, team

@@ -1722,6 +1722,46 @@ int lk_get_stats(lk_engine *e, lk_stats *out);
  * out[s] = {evaluations, sample evaluations, point iterations, ill-conditioned solves} */
 int lk_get_sector_stats(lk_engine *e, uint32_t *out_4_per_sector);
 
+/* Which instance of the solve / evaluation kernel a launch ran, as the host decided it (no device word is read). */
+typedef enum {
+  LK_LAUNCH_MAIN = 0,      /* the lane-group launch of a size class (or of one sector, or of a window) */
+  LK_LAUNCH_STARVED = 1,   /* the one-lane kernel of the starved levels, in front of the main launch */
+  LK_LAUNCH_FINISHER = 2,  /* the 16-lane finisher of the sectors the one-lane kernel parked */
+  LK_LAUNCH_SAFE_PASS = 3, /* the SAFE pass behind a fast launch: 16-lane rows for one pair, the window again for a window */
+  LK_LAUNCH_EVAL = 4       /* the evaluation kernel (lk_evaluate) */
+} lk_launch_role;
+typedef enum { LK_FLAVOUR_FAST = 0, LK_FLAVOUR_SAFE = 1, LK_FLAVOUR_REFERENCE = 2 } lk_launch_flavour;
+#define LK_LAUNCH_REPORT_CAPACITY 64 /* six classes x four launches, a window's SAFE pass per class, and room to spare */
+typedef struct {
+  int model;      /* lk_fitting_model of the instance */
+  int interp;     /* lk_interpolation of the instance */
+  int group;      /* lanes per sector: 1, 16, 32, 64, 256, 512 */
+  int threads;    /* threads per workgroup */
+  int flavour;    /* lk_launch_flavour */
+  int seq;        /* 1: a frame-pipelined (SEQ) instance */
+  int role;       /* lk_launch_role */
+  int sectors;    /* sectors given to the launch */
+  int team_w;     /* workgroups per sector after the launcher's clamp to what is resident (0: no team) */
+  int persistent; /* 1: the workgroups draw sectors from the queue */
+  int grid;       /* workgroups launched */
+  int reserved;
+} lk_launch_record;
+/* The launches of the engine's most recent solving call - lk_correlate, lk_correlate_all*, lk_correlate_sequence_async
+ * (its SAFE re-run included; a window that runs as the one-pair loop reports its last frame) and lk_evaluate - in the order
+ * the host issued them.  out: room for `capacity` records, or NULL to ask for the count alone.  *n_out = records the call
+ * made (at most LK_LAUNCH_REPORT_CAPACITY are kept); *overflow = 1 if it made more than are kept.  Host state only:
+ * no device call, no synchronisation. */
+int lk_get_launch_report(lk_engine *e, lk_launch_record *out, int capacity, int *n_out, int *overflow);
+/* Lanes per sector of the next one-pair batch solve (lk_correlate_all*), registration order: groups[s] is the lane group of
+ * sector s's size class after promotions and the LK_FORCE_* hooks, or - in reference-order mode - of the batch rule there
+ * (a 16-lane row, a wavefront, or a 512-thread workgroup for the big classes).  team_w[s] (may be NULL) is the number of
+ * workgroups per sector the engine asks for, before the launcher's clamp to what is resident, and 0 for a sector that gets
+ * no team: outside reference-order mode the team class reports 512 lanes and its width (1 under LK_FORCE_TEAM=1: one
+ * workgroup); in reference-order mode with T > 1 threads a 512-lane sector of either big class reports T where the batch
+ * launches a team of T workgroups, else 0.  Read-only, host state only: no device call, nothing is rebuilt - while a
+ * rebuild is pending (sectors appended or moved since the last batch solve) the call fails with LK_ERROR_BAD_DOMAIN. */
+int lk_get_sector_groups(lk_engine *e, int *groups, int *team_w);
+
 #ifdef __cplusplus
 }
 #endif

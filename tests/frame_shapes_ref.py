@@ -129,8 +129,8 @@ def size_class(n0):
 
 
 def lane_groups(counts, mode="default", force_group=0, force_team=0):
-    """The lane group the host is EXPECTED to pick per sector - a restatement for the tests' printed lines, not read from
-    the engine (which has no binding for it): keep it in step with the host's thresholds.
+    """The lane group the host is EXPECTED to pick per sector - a restatement that assert_lane_groups holds against the
+    engine's own answer (sector_groups()) wherever it is printed: keep it in step with the host's thresholds.
     Lanes per sector for a batch of level-0 sample counts (classify_sectors of lk_engine_sectors.cpp and
     reference_group_of_sector of lk_engine_solve.cpp, one pair in flight): in "reference_order" a 16-lane row or a
     wavefront; in "batch_invariant" the size class alone; in "default" mode the batch's promotions and the two
@@ -157,3 +157,20 @@ def lane_groups(counts, mode="default", force_group=0, force_team=0):
         cls = [TEAM_CLASS if c == TEAM_CLASS - 1 else c for c in cls]
     return [f"team of {force_team} x 512" if c == TEAM_CLASS and force_team >= 1 else
             "team x 512" if c == TEAM_CLASS else str(GROUP_OF_CLASS[c]) for c in cls]
+
+
+def assert_lane_groups(e, expected, counts=None):
+    """lane_groups' strings against sector_groups() of the committed engine `e`: the lanes per sector, and for a team the
+    width the engine asks for.  A team whose width the batch decides ("team x 512") needs `counts`, the level-0 sample
+    counts: classify_sectors asks for ceil(largest team sector / 4096) workgroups, at least 2 and at most 256."""
+    groups, team = e.sector_groups()
+    assert len(expected) == len(groups)
+    n0_max = max([n for n, want in zip(counts or [], expected) if want == "team x 512"], default=0)
+    for s, want in enumerate(expected):
+        if want.startswith("team of "):
+            assert (groups[s], team[s]) == (512, int(want.split()[2])), (s, want, groups[s], team[s])
+        elif want == "team x 512":
+            assert counts is not None, "a batch-sized team needs the sample counts"
+            assert (groups[s], team[s]) == (512, min(max(-(-n0_max // 4096), 2), 256)), (s, want, groups[s], team[s], n0_max)
+        else:
+            assert (groups[s], team[s]) == (int(want), 0), (s, want, groups[s], team[s])

@@ -158,7 +158,9 @@ def test_grid_records_are_the_oracles_bytes(oracle, orientation, which, model, i
         got = e.correlate_all(ZERO)
         REFORDER.assert_same_bytes(got, want, f"{orientation} {which} model {model} interp {interp} T={threads}")
         if threads == 1:
-            print("expected sample loops:", sorted(set(fs.lane_groups([len(x) for x in g.lists], "reference_order"))), "lanes per sector")
+            expected = fs.lane_groups([len(x) for x in g.lists], "reference_order")
+            fs.assert_lane_groups(e, expected, [len(x) for x in g.lists])
+            print("sample loops:", sorted(set(expected)), "lanes per sector")
             one, _ = e.correlate(g.far_valid, np.zeros(ca.N_PARAMS[model], np.float32))
             REFORDER.assert_same_bytes(one, want[g.far_valid], "single-sector entry point")
         e.close()
@@ -172,7 +174,9 @@ def test_grid_default_mode_within_the_yardsticks(oracle, orientation, which, mod
     g = fs.grid(oracle, orientation)
     e = grid_engine(oracle, orientation, which, model, interp)
     got = e.correlate_all(ZERO)
-    print("expected sample loops:", sorted(set(fs.lane_groups([len(x) for x in g.lists]))), "lanes per sector")
+    expected = fs.lane_groups([len(x) for x in g.lists])
+    fs.assert_lane_groups(e, expected, [len(x) for x in g.lists])
+    print("sample loops:", sorted(set(expected)), "lanes per sector")
     PARITY.compare_results(got, yardsticks(oracle, orientation, which, model, interp),
                            f"{orientation} {which} model {model} interp {interp}")
     e.close()
@@ -187,7 +191,9 @@ def test_batch_invariant_sectors_alone_and_in_the_batch(oracle, orientation, whi
     g = fs.grid(oracle, orientation)
     e = grid_engine(oracle, orientation, which, mode="batch_invariant")
     full = e.correlate_all(ZERO)
-    print("expected sample loops:", sorted(set(fs.lane_groups([len(x) for x in g.lists], "batch_invariant"))), "lanes per sector")
+    expected = fs.lane_groups([len(x) for x in g.lists], "batch_invariant")
+    fs.assert_lane_groups(e, expected, [len(x) for x in g.lists])
+    print("sample loops:", sorted(set(expected)), "lanes per sector")
     PARITY.compare_results(full, yardsticks(oracle, orientation, which, ca.FM_UVUXUYVXVY, ca.IM_BICUBIC), "batch invariant")
     chosen = [0, len(g) - 1, g.far_valid, g.interior]
     assert g.edge[len(g) - 1] and not g.edge[[0, g.far_valid, g.interior]].any()
@@ -221,7 +227,9 @@ def test_grid_as_implicit_rectangles(oracle, orientation, which):
         assert len(e.level_xy(0, g.far_valid)) == 0 and np.array_equal(e.getUndXY0ToCPU(g.far_valid), g.lists[g.far_valid])
         assert np.array_equal(np.float32([e.sector_info(s)[1:3] for s in range(len(g))]), g.rect_centers)
         got = e.correlate_all(ZERO)
-        print(f"{mode}: expected sample loops", sorted(set(fs.lane_groups([len(x) for x in g.lists], mode.split(":")[0]))), "lanes per sector")
+        expected = fs.lane_groups([len(x) for x in g.lists], mode.split(":")[0])
+        fs.assert_lane_groups(e, expected, [len(x) for x in g.lists])
+        print(f"{mode}: sample loops", sorted(set(expected)), "lanes per sector")
         if mode.startswith("reference_order"):
             REFORDER.assert_same_bytes(got, want, f"{orientation} {which} implicit rectangles")
         else:
@@ -309,11 +317,12 @@ def test_wavefront_workgroup_and_team_sample_loops(oracle, orientation, which, m
         if mode != "default":     # (default mode: lanes without work join a neighbour's sector, the sums depend on the batch)
             one, _ = e.correlate(1, ZERO)
             assert one.tobytes() == got[1].tobytes()
+        groups = fs.lane_groups(counts, mode.split(":")[0], env.get("LK_FORCE_GROUP", 0), env.get("LK_FORCE_TEAM", 0))
+        fs.assert_lane_groups(e, groups, counts)
         e.close()
         for k in env:
             monkeypatch.delenv(k)
-        groups = fs.lane_groups(counts, mode.split(":")[0], env.get("LK_FORCE_GROUP", 0), env.get("LK_FORCE_TEAM", 0))
-        print(f"{mode} {env}: expected lanes per sector {groups}")
+        print(f"{mode} {env}: lanes per sector {groups}")
         return got
 
     for threads in (1, 20):

@@ -72,6 +72,7 @@ for name, rects in cases.items():
         out[key + "listed"] = np.int32([[len(e.level_xy(l, s)) for l in range(3)] for s in range(S)])
         out[key + "records"] = e.correlate_all(np.zeros(6, np.float32))
         out[key + "stats"] = e.sector_stats()
+        out[key + "groups"] = e.sector_groups()[0]
         sums = np.zeros((S, 3, 44), np.float32)
         for s in range(S):
             for l in range(3):
@@ -107,10 +108,14 @@ def solved(request, tmp_path_factory):
 
 
 def test_the_forced_groups_are_three_different_groups(tmp_path_factory):
-    """The engine has no query for the lane group of a sector.  What shows it: a group of another width adds the same
-    products in another order, so the sums and chi of 19 x 19 samples round differently.  Were LK_FORCE_GROUP ignored, the
-    three runs would be the classifier's group three times, bit for bit."""
+    """The three children report 16, 32 and 64 lanes for every sector (sector_groups()).  And what shows it in the results: a
+    group of another width adds the same products in another order, so the sums and chi of 19 x 19 samples round
+    differently.  Were LK_FORCE_GROUP ignored, the three runs would be the classifier's group three times, bit for bit."""
     runs = {g: run_child(g, tmp_path_factory) for g in ("16", "32", "64")}
+    for g, d in runs.items():   # the engine's own word (lk_get_sector_groups): every sector of every case in the forced group
+        for c in CASES:
+            for domain in ("rect", "list"):
+                assert (d[f"{c}_{domain}_groups"] == int(g)).all(), (g, c, domain, d[f"{c}_{domain}_groups"])
     bits = {g: b"".join(d[c + "_rect_" + k].tobytes() for c in CASES for k in ("sums", "records")) for g, d in runs.items()}
     assert bits["16"] != bits["32"] and bits["32"] != bits["64"] and bits["16"] != bits["64"]
     for c in CASES:   # and per case at level 0, where a lane of every group has several samples
