@@ -38,6 +38,8 @@ from ._ffi import WEIGHTED_DTYPE, weight_window, weighted_step_from_sums  # noqa
 from ._ffi import COMPOSED_DTYPE, composed_step_from_sums  # noqa: F401
 from ._ffi import (PATTERN_APERTURE, PATTERN_DTYPE, PATTERN_FLAT, PATTERN_MAX_HALF, PATTERN_OK, PATTERN_SATURATED,  # noqa: F401
                    PATTERN_SUMS, PATTERN_TOO_FEW, SUBSET_BAD_POINT, SUBSET_DTYPE, SUBSET_NONE, SUBSET_OK, pattern_from_sums)
+from ._ffi import (NOISE_BINS, NOISE_DTYPE, NOISE_IMAGES, NOISE_MAX_FRAMES, NOISE_NO_MODEL, NOISE_OK, NOISE_RING,  # noqa: F401
+                   NOISE_SUMS, NOISE_TOO_FEW, SECTOR_NOISE_DTYPE, noise_from_bins, noise_from_sums)
 from ._ffi import (FIELD_ALL, FIELD_BISQUARE, FIELD_CHANNELS, FIELD_DEFORMED, FIELD_DEGENERATE, FIELD_E1, FIELD_E2,  # noqa: F401
                    FIELD_EXX, FIELD_EXY, FIELD_EYY, FIELD_MISFIT, FIELD_OK, FIELD_REFERENCE, FIELD_THETA, FIELD_TOO_FEW, FIELD_U,
                    FIELD_UNIFORM, FIELD_UX, FIELD_UY, FIELD_V, FIELD_VX, FIELD_VY, FIELD_X0, FIELD_Y0, field_from_sums)

@@ -321,6 +321,29 @@ SUBSET_DTYPE = np.dtype([(k, np.int32) for k in ("half", "status", "n_pixels", "
 assert PATTERN_DTYPE.itemsize == 64 and SUBSET_DTYPE.itemsize == 32
 assert C.sizeof(LkPatternConfig) == 32 and C.sizeof(LkSubsetConfig) == 32
 
+# camera noise (include/lk_engine.h: lk_camera_noise, lk_sector_noise)
+NOISE_IMAGES, NOISE_RING = 0, 1
+NOISE_OK, NOISE_TOO_FEW, NOISE_NO_MODEL = range(3)
+NOISE_MAX_FRAMES = 16
+NOISE_BINS = 256       # int64 pairs {count, sum q}
+NOISE_SUMS = 3         # int64 per sector: n, sum q, sum s1
+
+
+class LkNoiseConfig(C.Structure):
+    _fields_ = [("source", C.c_int32), ("n_frames", C.c_int32), ("slots", C.c_int32 * 3), ("first", C.c_int32),
+                ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("grey_low", C.c_int32), ("grey_high", C.c_int32), ("min_count", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+# struct lk_noise and struct lk_sector_noise as numpy records
+NOISE_DTYPE = np.dtype([("n_pixels", np.int64)] + [(k, np.float64) for k in ("var", "var_detrended", "a", "b")] +
+                       [(k, np.int32) for k in ("status", "n_frames", "bins_used")] +
+                       [(k, np.float32) for k in ("sigma", "sigma_detrended", "flicker", "mean", "sigma_at_mean", "fit_rms")] +
+                       [("reserved", np.int32, (5,))])
+SECTOR_NOISE_DTYPE = np.dtype([("n", np.int32), ("status", np.int32), ("sigma", np.float32), ("mean", np.float32),
+                               ("var", np.float64), ("reserved", np.int32, (2,))])
+assert NOISE_DTYPE.itemsize == 96 and SECTOR_NOISE_DTYPE.itemsize == 32 and C.sizeof(LkNoiseConfig) == 64
+
 # field map (include/lk_engine.h: lk_field_map)
 FIELD_OK, FIELD_TOO_FEW, FIELD_DEGENERATE = range(3)
 FIELD_UNIFORM, FIELD_BISQUARE = 0, 1
@@ -454,6 +477,10 @@ SYMBOLS = {
     "lk_pattern_quality": (C.c_int, [_P, C.POINTER(LkPatternConfig), _P, _P, _P]),
     "lk_pattern_from_sums": (C.c_int, [C.c_int, _P, C.c_double, C.c_float, C.c_float, _P]),
     "lk_suggest_subset": (C.c_int, [_P, C.POINTER(LkSubsetConfig), C.c_int, _F, _P, _P]),
+    "lk_camera_noise": (C.c_int, [_P, C.POINTER(LkNoiseConfig), _P, _P, _P, _P]),
+    "lk_sector_noise": (C.c_int, [_P, C.POINTER(LkNoiseConfig), _P, _P]),
+    "lk_noise_from_bins": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "lk_noise_from_sums": (C.c_int, [C.c_int, _P, _P]),
     "lk_evaluate": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_evaluate_backward": (C.c_int, [_P, C.c_int, C.c_int, _F, _F, _F, _F, _I]),
     "lk_compose_inverse": (C.c_int, [C.c_int, _F, _F, _F]),
@@ -755,6 +782,34 @@ def pattern_from_sums(n, sums9, mig_sum, noise_sigma=1.0, max_saturated=1.0):
     if _compose_lib.lk_pattern_from_sums(int(n), s.ctypes.data_as(_P), float(mig_sum), float(noise_sigma), float(max_saturated),
                                          out.ctypes.data_as(_P)) != 0:
         raise ValueError("lk_pattern_from_sums: n < 0, or a noise_sigma or max_saturated that is not finite")
+    return out[0]
+
+
+def noise_from_bins(n_frames, bins, frame_sums, grey_low=0, grey_high=255, min_count=2):
+    """lk_noise_from_bins (host, no engine): the NOISE_DTYPE record of the tables of K = n_frames static frames - bins
+    [256][2] int64 {count, sum q} and frame_sums [K] int64."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    b = np.ascontiguousarray(bins, np.int64).reshape(NOISE_BINS, 2)
+    f = np.ascontiguousarray(frame_sums, np.int64).reshape(-1)
+    out = np.zeros(1, NOISE_DTYPE)
+    if len(f) != int(n_frames) or _compose_lib.lk_noise_from_bins(int(n_frames), b.ctypes.data_as(_P), f.ctypes.data_as(_P), int(grey_low),
+                                                                  int(grey_high), int(min_count), out.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_noise_from_bins: n_frames outside 2 .. 16, a negative table entry, greys outside 0 .. 255 or "
+                         "min_count < 2")
+    return out[0]
+
+
+def noise_from_sums(n_frames, sums3):
+    """lk_noise_from_sums (host, no engine): the SECTOR_NOISE_DTYPE record of one sector's sums {n, sum q, sum s1}."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.ascontiguousarray(sums3, np.int64).reshape(NOISE_SUMS)
+    out = np.zeros(1, SECTOR_NOISE_DTYPE)
+    if _compose_lib.lk_noise_from_sums(int(n_frames), s.ctypes.data_as(_P), out.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_noise_from_sums: n_frames outside 2 .. 16 or a negative sum")
     return out[0]
 
 

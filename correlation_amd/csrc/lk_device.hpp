@@ -532,3 +532,20 @@ struct LkSubsetArgs {
   uint32_t threshold;       // T = ceil(4 sssig_min)
   float noise_sigma;
 };
+
+// Camera noise (lk_noise.hip, include/lk_engine.h: lk_camera_noise, lk_sector_noise; the arithmetic is lk_noise.hpp).
+// The K frames are level-L images of one geometry, each its own allocation (16-byte aligned), pitch == cols.
+struct LkNoiseFrameArgs {
+  const uint8_t *frame[LK_NOISE_MAX_FRAMES]; // the first n_frames are read
+  const uint8_t *mask;         // [rows][cols] (16-byte aligned), nonzero = use, or null: every pixel
+  int n_frames, rows, cols;
+  int x0, y0, w, h;            // the region, inside the frame
+  unsigned long long *bins;    // [256][2] {count, sum q}, zeroed before the launch
+  unsigned long long *frame_sums; // [n_frames], zeroed before the launch
+};
+struct LkNoiseSectorArgs {
+  LkSectorEvalArgs ev;         // und = def = frame[0] with the frames' dimensions; rec is not read
+  const uint8_t *frame[LK_NOISE_MAX_FRAMES];
+  long long *sums;             // [S][3] n, sum q, sum s1
+  int n_frames, n_sectors, level;
+};

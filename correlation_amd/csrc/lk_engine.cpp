@@ -499,6 +499,64 @@ int lk_internal_image_view(lk_engine *e, const char *who, int slot, int need_sec
   return LK_ERROR_NONE;
 }
 
+int lk_internal_frames_view(lk_engine *e, const char *who, int ring, int n_frames, const int *slots, int first, int need_sectors,
+                            LkFramesView *v) {
+  const std::string w(who);
+  if (n_frames < 2 || n_frames > (ring ? LK_NOISE_MAX_FRAMES : 3))
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + (ring ? ": n_frames must be 2 .. LK_NOISE_MAX_FRAMES ring slots" : ": n_frames must be 2 or 3 image slots"));
+  if (!ring) {
+    for (int i = 0; i < n_frames; ++i) {
+      if (slots[i] != LK_IMG_UND && slots[i] != LK_IMG_DEF && slots[i] != LK_IMG_NXT)
+        return e->fail(LK_ERROR_BAD_DOMAIN, w + ": unknown slot (LK_IMG_UND, LK_IMG_DEF or LK_IMG_NXT)");
+      for (int j = 0; j < i; ++j)
+        if (slots[j] == slots[i])
+          return e->fail(LK_ERROR_BAD_DOMAIN, w + ": an image slot is listed twice");
+    }
+  }
+  if (need_sectors && (!e->committed || e->S <= 0))
+    return e->fail(LK_ERROR_BAD_DOMAIN, w + ": no committed sectors (call lk_commit_sectors)");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  *v = LkFramesView{};
+  const int level = e->cfg.py_start;
+  if (need_sectors)
+    if (int rc = recommit_if_pending(e)) // (as the next solve would)
+      return rc;
+  {
+    // (the next-frame slot and the ring are filled on their own stream, under this lock)
+    std::lock_guard<std::mutex> lock(e->nxt_mu);
+    if (ring && (first < 0 || first > (int)e->ring.size() - n_frames))
+      return e->fail(LK_ERROR_BAD_DOMAIN, w + ": unknown ring slot (lk_sequence_reserve)");
+    for (int i = 0; i < n_frames; ++i) {
+      const DevImage &im = ring ? e->ring[(size_t)(first + i)] : e->img[slots[i]];
+      if (!im.valid || !im.lvl[level])
+        return e->fail(LK_ERROR_BAD_DOMAIN, w + (ring ? ": a ring slot is empty (lk_sequence_set_frame)" : ": the image of a slot is not set (lk_set_image)"));
+      if (i > 0 && ((im.rows >> level) != v->rows || (im.cols >> level) != v->cols))
+        return e->fail(LK_ERROR_BAD_DOMAIN, w + ": the frames must have the same dimensions");
+      // the engine's stream must see the finished pyramid
+      if (ring)
+        HIPCHK(hipStreamWaitEvent(e->stream, e->ring_ready[(size_t)(first + i)], 0));
+      else if (slots[i] == LK_IMG_NXT && e->nxt_pending)
+        HIPCHK(hipStreamWaitEvent(e->stream, e->nxt_done, 0));
+      v->frame[i] = im.lvl[level];
+      v->rows = im.rows >> level;
+      v->cols = im.cols >> level;
+    }
+  }
+  v->level = level;
+  v->n_frames = n_frames;
+  v->stream = e->stream;
+  if (need_sectors) {
+    v->S = e->S;
+    v->xy = e->d_xy[level].p;
+    v->off = e->d_off[level].p;
+    v->rect = e->d_rect[level].p;
+    v->h_rect0 = e->h_rect[0].data();
+    v->h_off0 = e->h_off[0].data();
+    v->center = e->d_center.p;
+  }
+  return LK_ERROR_NONE;
+}
+
 int lk_get_stats(lk_engine *e, lk_stats *out) {
   if (!e || !out)
     return LK_ERROR_BAD_DOMAIN;

@@ -91,7 +91,7 @@ struct LkPassSlot {
   virtual ~LkPassSlot() = default;
 };
 enum LkPass { LK_PASS_RESEED, LK_PASS_STRAIN, LK_PASS_UNCERTAINTY, LK_PASS_OUTLIER, LK_PASS_TRACK, LK_PASS_RESIDUAL, LK_PASS_PATTERN,
-              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_ROTATED, LK_PASS_MOTION, LK_PASS_COUNT };
+              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_ROTATED, LK_PASS_MOTION, LK_PASS_NOISE, LK_PASS_COUNT };
 LkPassSlot **lk_internal_pass_slot(lk_engine *e, int which);
 
 // What a post-processing pass reads of the engine (lk_strain_field, lk_parameter_uncertainty, lk_flag_outliers,
@@ -129,6 +129,27 @@ int lk_internal_pass_view(lk_engine *e, const char *who, unsigned need, int def_
 // level-L lists, a pending rebuild of them finished first as for LK_VIEW_IMAGES; without it the call needs no sectors and
 // the view has S = 0 and no lists.  Allowed in every mode; every refusal is prefixed with `who`.
 int lk_internal_image_view(lk_engine *e, const char *who, int slot, int need_sectors, LkPassView *v);
+// What a pass reads that looks at K frames of one scene (lk_camera_noise, lk_sector_noise): the level-L pyramids, L =
+// py_start, of the image slots slots[0 .. n_frames - 1] (ring == 0: 2 or 3 distinct slots of LK_IMG_UND / _DEF / _NXT, under
+// lk_internal_image_view's checks and its wait for LK_IMG_NXT) or of the ring slots first .. first + n_frames - 1 (ring != 0:
+// 2 .. LK_NOISE_MAX_FRAMES, under level_images' range check and its wait for each slot's pyramid), all of one geometry.
+// need_sectors: the committed sectors with the level-L lists, a pending rebuild of them finished first.  Allowed in every
+// mode; every refusal is prefixed with `who`.
+struct LkFramesView {
+  hipStream_t stream;
+  int level, n_frames;
+  const uint8_t *frame[LK_NOISE_MAX_FRAMES];
+  int rows, cols;           // of every frame at level L
+  int S;                    // need_sectors, else 0 and no lists
+  const float2 *xy;
+  const uint32_t *off;
+  const int4 *rect;
+  const int4 *h_rect0;
+  const uint32_t *h_off0;
+  const float2 *center;
+};
+int lk_internal_frames_view(lk_engine *e, const char *who, int ring, int n_frames, const int *slots, int first, int need_sectors,
+                            LkFramesView *v);
 
 // Bench hooks (scripts/*_bench.py; exported, not part of include/*.h): of the last call of a pass, the HIP-event time of its
 // device part - for the passes with a cell grid the bounding box with its round trip, the grid kernels, the prep and the
@@ -165,4 +186,7 @@ int lk_internal_composed_last(lk_engine *e, float *device_ms, int *count3);
 // lk_rigid_motion: the chunk size and the chunks per frame; the time covers the pack, the passes and the removal (not the
 // bounding box's round trip, which comes before, and not the copies of the records)
 int lk_internal_motion_last(lk_engine *e, float *device_ms, int *chunk, int *chunks);
+// lk_camera_noise or lk_sector_noise: the workgroups of the frame kernel (0 after lk_sector_noise); the time covers the
+// clearing of the tables and the kernels, not the upload of a mask or the copies of the results
+int lk_internal_noise_last(lk_engine *e, float *device_ms, int *workgroups);
 }

@@ -175,6 +175,13 @@ hipError_t lk_launch_sat_build(const LkSatArgs &a, hipStream_t st);
 // a thread per point: every candidate's box sums from the four corners, the smallest passing candidate, the record
 hipError_t lk_launch_subset_query(const LkSubsetArgs &a, hipStream_t st);
 
+// ---- lk_noise.hip: camera noise from static frames (lk_camera_noise, lk_sector_noise)
+// one launch over the region: the 256-bin table {count, sum q} and the per-frame sums, added to a.bins and a.frame_sums
+// (zeroed by the caller); *n_blocks = the workgroups launched; hipErrorInvalidValue for a pointer that is not 16-byte aligned
+hipError_t lk_launch_noise_frames(const LkNoiseFrameArgs &a, int *n_blocks, hipStream_t st);
+// group: 16, 64 or 512 lanes per sector; a.ev.order lists that group's sectors
+hipError_t lk_launch_noise_sectors(const LkNoiseSectorArgs &a, int group, hipStream_t st);
+
 // ---- lk_field.hip: dense displacement and strain maps (lk_field_map)
 // one workgroup per tile of kLkMapTileW x kLkMapTileH nodes; weight, frame: LK_FIELD_*; *n_tiles = the tiles launched
 hipError_t lk_launch_field_map(const LkFieldArgs &a, int weight, int frame, int *n_tiles, hipStream_t st);

@@ -787,6 +787,76 @@ class HipCorrelationEngine:
         """lk_pattern_from_sums: the kernel's record arithmetic on the host (no engine needed)."""
         return _ffi.pattern_from_sums(n, sums9, mig_sum, noise_sigma, max_saturated)
 
+    # ---- camera noise: the photon-transfer curve from static frames ---------------------------------------
+    @staticmethod
+    def _noise_config(slots, ring_first, n_frames, region=None, grey_low=0, grey_high=255, min_count=2):
+        cfg = _ffi.LkNoiseConfig()
+        if ring_first is None:
+            s = [int(k) for k in slots]
+            cfg.source, cfg.n_frames = _ffi.NOISE_IMAGES, len(s)
+            for i, k in enumerate(s[:3]):
+                cfg.slots[i] = k
+        else:
+            cfg.source, cfg.n_frames, cfg.first = _ffi.NOISE_RING, int(n_frames), int(ring_first)
+        if region is not None:
+            cfg.x0, cfg.y0, cfg.x1, cfg.y1 = (int(k) for k in region)
+        cfg.grey_low, cfg.grey_high, cfg.min_count = int(grey_low), int(grey_high), int(min_count)
+        return cfg
+
+    def camera_noise(self, slots=(_ffi.IMG_UND, _ffi.IMG_DEF), ring_first=None, n_frames=None, region=None, mask=None,
+                     grey_low=0, grey_high=255, min_count=2, return_tables=False):
+        """lk_camera_noise: the NOISE_DTYPE record (pooled temporal variance, flicker, detrended variance, the line var(g) =
+        a + b g) of K static frames at level py_start - the image slots `slots` (2 or 3 of them) or, with ring_first, the
+        ring slots ring_first .. ring_first + n_frames - 1 - over `region` (x0, y0, x1, y1 inclusive; None: the whole frame)
+        and the nonzero pixels of `mask` ([rows][cols] of that level).  With return_tables also the int64 tables bins
+        [256][2] {count, sum q} and frame_sums [K].  Needs no sectors; no engine state changes."""
+        cfg = self._noise_config(slots, ring_first, n_frames, region, grey_low, grey_high, min_count)
+        m = np.ascontiguousarray(mask, np.uint8) if mask is not None else None
+        if m is not None and ring_first is None:   # (the library cannot see the size of a caller's mask)
+            r, c = C.c_int(), C.c_int()
+            self._chk(self.lib.lk_get_pyramid_level(self._h, cfg.slots[0], self.cfg.py_start, None, C.byref(r), C.byref(c)))
+            assert m.shape == (r.value, c.value), f"mask {m.shape} on level-py_start frames {(r.value, c.value)}"
+        assert m is None or m.ndim == 2
+        out = np.zeros(1, _ffi.NOISE_DTYPE)
+        bins = np.zeros((_ffi.NOISE_BINS, 2), np.int64) if return_tables else None
+        sums = np.zeros(max(cfg.n_frames, 1), np.int64) if return_tables else None
+        self._chk(self.lib.lk_camera_noise(self._h, C.byref(cfg), m.ctypes.data_as(C.c_void_p) if m is not None else None,
+                                           out.ctypes.data_as(C.c_void_p),
+                                           bins.ctypes.data_as(C.c_void_p) if return_tables else None,
+                                           sums.ctypes.data_as(C.c_void_p) if return_tables else None))
+        return (out[0], bins, sums) if return_tables else out[0]
+
+    def sector_noise(self, slots=(_ffi.IMG_UND, _ffi.IMG_DEF), ring_first=None, n_frames=None, return_sums=False):
+        """lk_sector_noise: a SECTOR_NOISE_DTYPE array [S], the temporal noise of the same K frames over every committed
+        sector's own level-py_start samples (those outside the frame are not counted); with return_sums also the int64 sums
+        [S][3] {n, sum q, sum s1}.  No engine state changes."""
+        cfg = self._noise_config(slots, ring_first, n_frames)
+        out = np.zeros(self.n_sectors, _ffi.SECTOR_NOISE_DTYPE)
+        sums = np.zeros((self.n_sectors, _ffi.NOISE_SUMS), np.int64) if return_sums else None
+        self._chk(self.lib.lk_sector_noise(self._h, C.byref(cfg), out.ctypes.data_as(C.c_void_p),
+                                           sums.ctypes.data_as(C.c_void_p) if return_sums else None))
+        return (out, sums) if return_sums else out
+
+    def noise_last(self):
+        """Bench hook: (device ms, workgroups of the frame kernel) of the last camera_noise or sector_noise call (0
+        workgroups after sector_noise)."""
+        ms, wg = C.c_float(), C.c_int()
+        fn = self.lib.lk_internal_noise_last
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        self._chk(fn(self._h, C.byref(ms), C.byref(wg)))
+        return ms.value, wg.value
+
+    @staticmethod
+    def noise_from_bins(n_frames, bins, frame_sums, grey_low=0, grey_high=255, min_count=2):
+        """lk_noise_from_bins: the record of the tables on the host (no engine needed)."""
+        return _ffi.noise_from_bins(n_frames, bins, frame_sums, grey_low, grey_high, min_count)
+
+    @staticmethod
+    def noise_from_sums(n_frames, sums3):
+        """lk_noise_from_sums: a sector's record from its three sums on the host (no engine needed)."""
+        return _ffi.noise_from_sums(n_frames, sums3)
+
     # ---- field map: dense displacement and strain maps on a regular grid of nodes ------------------------
     def field_map(self, radius, window, stride=1, channels=("u", "v"), weight=_ffi.FIELD_UNIFORM, frame=_ffi.FIELD_REFERENCE,
                   iterations=4, records=None, chi_max=0.0, min_neighbours=3, tensor=_ffi.STRAIN_GREEN_LAGRANGE,

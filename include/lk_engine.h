@@ -1682,6 +1682,104 @@ struct lk_subset {                    /* 32 bytes, one per point */
 int lk_suggest_subset(lk_engine *e, const lk_subset_config *cfg, int n_points, const float *points_xy, struct lk_subset *out,
                       uint32_t *sums_out);
 
+/* ---- camera noise: the photon-transfer curve from static frames ---------------------------------- */
+/* lk_pattern_quality and lk_suggest_subset predict a displacement error "for a given camera noise", lk_parameter_uncertainty
+ * reports a residual in which camera noise, misfit and interpolation error are mixed, lk_flag_outliers has a noise floor.
+ * These two calls measure the camera's part on its own, the way an experiment starts: K frames of the unloaded, unmoved
+ * specimen.  The temporal variance of every pixel, binned by the pixel's mean grey level, is the photon-transfer curve
+ * var(g) = a + b g - a: read noise and quantisation, b: the gain of the shot noise.  lk_camera_noise gives the curve and
+ * the pooled figures of a region, lk_sector_noise the noise of every committed sector over its own samples
+ * (csrc/lk_noise.hip, csrc/lk_noise.hpp).
+ *   level     both calls work at L = py_start, the level of lk_pattern_quality: the sigma is the one its noise_sigma means.
+ *   frames    cfg->source = LK_NOISE_IMAGES: the image slots slots[0 .. n_frames - 1] (LK_IMG_UND, LK_IMG_DEF, LK_IMG_NXT,
+ *             distinct; K = n_frames is 2 or 3);  LK_NOISE_RING: the ring slots first .. first + n_frames - 1 (no wrap;
+ *             K = 2 .. LK_NOISE_MAX_FRAMES).  Every frame must be set and all must have the same level-L dimensions.
+ *   integers  the GPU produces integers only, so its outputs are the same bytes on every run, for every grid and every
+ *             decomposition of a region.  Per counted pixel with its K values x_f (u8 taken as integers):
+ *               s1 = sum x_f,  s2 = sum x_f^2,  q = K s2 - s1^2  (= K sum_f (x_f - mean)^2; K = 2: (a - b)^2; < 2^25),
+ *               g = (2 s1 + K) / (2 K) in integer division: the rounded temporal mean, 0 .. 255.
+ *
+ * lk_camera_noise
+ *   pixels    the region x0 .. x1, y0 .. y1 of the level-L frame, inclusive (all four 0: the whole frame), and of those the
+ *             pixels whose mask byte is nonzero (mask: [rows][cols] of the level-L frame, or NULL: all).
+ *   tables    bins[g] = {count, sum q} over the counted pixels of bin g, [256][2] int64;  frame_sums[f] = sum of x_f over
+ *             the counted pixels, [K] int64;  N = sum count.
+ *   record    lk_noise_from_bins (host only) from the tables, in double, each float field rounded once.  The integer
+ *             combinations below are formed exactly (128-bit) before the one division:
+ *               var = SQ / (N K (K - 1)) with SQ = sum_g sum q_g (the pooled temporal variance);  sigma = sqrt(var);
+ *               mean = sum_f frame_sums[f] / (K N);
+ *               o_f = frame_sums[f] / N - mean, the offset of frame f (from the integer K frame_sums[f] - sum frame_sums);
+ *               flicker = sqrt(sum o_f^2 / K);
+ *               var_detrended = (SQ / K - N sum o_f^2) / ((N - 1)(K - 1)), not below 0: the variance left when every
+ *               frame's own offset is taken out - an identity, no second pass over the pixels;
+ *               sigma_detrended = sqrt(var_detrended);
+ *               a, b: the count-weighted least-squares line var_g = a + b g over the bins with count >= min_count and
+ *               grey_low <= g <= grey_high, var_g = sum q_g / (count_g K (K - 1)); bins_used of them; a negative a or b is
+ *               reported as fitted;  fit_rms = sqrt(sum count_g (var_g - a - b g)^2 / sum count_g) over those bins (0 with
+ *               two bins: the line passes through both);
+ *               sigma_at_mean = sqrt(max(a + b mean, 0)).
+ *   status    LK_NOISE_TOO_FEW  N < 2: every field but n_pixels and n_frames is 0;  LK_NOISE_NO_MODEL  fewer than two
+ *             usable bins: a = var, b = 0, fit_rms = 0, the pooled fields valid;  LK_NOISE_OK.
+ *
+ * lk_sector_noise
+ *   samples   the sector's level-L list or implicit rectangle in lk_pattern_quality's walk and lane groups.  A sample's
+ *             pixel is its node ((int)(x + 0.5f), (int)(y + 0.5f)); a sample outside the frame - x + 0.5f or y + 0.5f below
+ *             0 or not below the frame's size, as floats - is skipped and not counted.  The region, the mask, grey_low, grey_high and min_count of the configuration are ignored.
+ *   sums      three int64 per sector: n = the counted samples, sum q, sum s1.
+ *   record    lk_noise_from_sums (host only): var = sum q / (n K (K - 1)), sigma = sqrt(var), mean = sum s1 / (n K);
+ *             LK_NOISE_TOO_FEW for n < 2 (every field but n is 0), else LK_NOISE_OK.
+ *
+ *   modes     both calls are allowed in every mode and change no engine state: records, guesses, counters and the launch
+ *             report stay byte for byte.  lk_sector_noise carries out a pending rebuild of the sample lists first, as
+ *             lk_pattern_quality does.  Both synchronise the engine's stream before they return.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message prefixed by the function's name, outputs untouched: null configuration or
+ *             output; non-zero reserved words; an unknown source; n_frames out of range; unknown or repeated image slots, or
+ *             one not set; unknown or empty ring slots; frames of unequal dimensions; an empty region or one outside the
+ *             frame; grey_low / grey_high outside 0 .. 255; min_count < 2 (these three lk_camera_noise only);
+ *             lk_sector_noise without committed sectors.  The two host functions return LK_ERROR_BAD_DOMAIN for a null
+ *             pointer, n_frames outside 2 .. LK_NOISE_MAX_FRAMES, a negative table entry, and lk_noise_from_bins also for
+ *             greys outside 0 .. 255 or min_count < 2.
+ *   scope     one engine, grey frames.  lk_group, lk_tracker and the CudaClass adapter do not call them. */
+#define LK_NOISE_MAX_FRAMES 16
+enum { LK_NOISE_IMAGES = 0, LK_NOISE_RING = 1 };
+enum { LK_NOISE_OK = 0, LK_NOISE_TOO_FEW = 1, LK_NOISE_NO_MODEL = 2 };
+typedef struct lk_noise_config {        /* 64 bytes */
+  int32_t source;                       /* LK_NOISE_IMAGES or LK_NOISE_RING */
+  int32_t n_frames;                     /* K */
+  int32_t slots[3];                     /* LK_NOISE_IMAGES: the first n_frames are read */
+  int32_t first;                        /* LK_NOISE_RING: the first ring slot */
+  int32_t x0, y0, x1, y1;               /* region in level-L pixels, inclusive; all 0: the whole frame */
+  int32_t grey_low, grey_high;          /* bins outside are left out of the line fit (clipping shrinks their variance) */
+  int32_t min_count;                    /* a bin enters the fit with at least this many pixels; >= 2 */
+  int32_t reserved[3];                  /* must be 0 */
+} lk_noise_config;
+struct lk_noise {                       /* 96 bytes */
+  int64_t n_pixels;                     /* N */
+  double var, var_detrended;            /* squared grey levels */
+  double a, b;                          /* var(g) = a + b g */
+  int32_t status, n_frames, bins_used;
+  float sigma, sigma_detrended, flicker;
+  float mean, sigma_at_mean, fit_rms;
+  int32_t reserved[5];
+};
+struct lk_sector_noise {                /* 32 bytes, one per sector */
+  int32_t n, status;
+  float sigma, mean;
+  double var;
+  int32_t reserved[2];
+};
+/* mask: [rows][cols] of the level-L frame, nonzero = use, or NULL.  bins_out: [256][2] int64 or NULL.  frame_sums_out: [K]
+ * int64 or NULL.  Synchronous.  Changes no engine state; needs no committed sectors. */
+int lk_camera_noise(lk_engine *e, const lk_noise_config *cfg, const uint8_t *mask, struct lk_noise *out, int64_t *bins_out,
+                    int64_t *frame_sums_out);
+/* out: [S].  sums_out: [S][3] int64 {n, sum q, sum s1} or NULL.  Synchronous.  Changes no engine state. */
+int lk_sector_noise(lk_engine *e, const lk_noise_config *cfg, struct lk_sector_noise *out, int64_t *sums_out);
+/* host only, no engine: the record of the tables bins [256][2] and frame_sums [n_frames] */
+int lk_noise_from_bins(int n_frames, const int64_t *bins, const int64_t *frame_sums, int grey_low, int grey_high, int min_count,
+                       struct lk_noise *out);
+/* host only, no engine: the record of one sector's three sums */
+int lk_noise_from_sums(int n_frames, const int64_t *sums3, struct lk_sector_noise *out);
+
 /* ---- stand-alone pieces (known-answer tests, same kernels as the batch path) ------- */
 /* one evaluation of one sector at one level: raw sums A (6x6 row-major, upper valid),
  * b, chi (unscaled), error flag (apply_model_and_interpolate, correlation_class.cpp:131) */

@@ -236,6 +236,22 @@ def run_pattern():
     return out
 
 
+def run_noise():
+    import correlation_amd as ca
+    out = {}
+    for scene in ("mix", "grid"):
+        e, _ = solved(scene, ca.FM_UVUXUYVXVY, ca.IM_BICUBIC)
+        rec, bins, frame_sums = e.camera_noise(grey_low=20, grey_high=235, min_count=5, return_tables=True)
+        out.update(fields("noise_" + scene, np.array([rec])))
+        out["noise_" + scene + ".bins"] = bins
+        out["noise_" + scene + ".frame_sums"] = frame_sums
+        sec, sums = e.sector_noise(return_sums=True)
+        out.update(fields("sector_noise_" + scene, sec))
+        out["sector_noise_" + scene + ".sums"] = sums
+        e.close()
+    return out
+
+
 def run_znssd():
     import correlation_amd as ca
     out = {}
@@ -457,7 +473,7 @@ VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (
 VARIANTS += [("field_walk%d" % w, {"LK_FIELD_WALK": str(w)}, run_field) for w in (0, 1)]
 VARIANTS += [("motion_chunk%d" % c, {"LK_MOTION_CHUNK": str(c)}, run_motion) for c in (64, 2048)]
 VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
-             ("pattern", {}, run_pattern), ("znssd", {}, run_znssd), ("quadratic", {}, run_quadratic),
+             ("pattern", {}, run_pattern), ("noise", {}, run_noise), ("znssd", {}, run_znssd), ("quadratic", {}, run_quadratic),
              ("spline", {}, run_spline), ("weighted", {}, run_weighted), ("composed", {}, run_composed)]
 VARIANTS += SOLVES
 
