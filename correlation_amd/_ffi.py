@@ -216,18 +216,19 @@ assert PHOTOMETRY_DTYPE.itemsize == 64 and C.sizeof(LkPhotometryConfig) == 16 an
 (ZN_CONVERGED, ZN_MAX_ITERS, ZN_STALLED, ZN_BAD_SEED, ZN_OUT_OF_IMAGE, ZN_TOO_FEW, ZN_FLAT, ZN_NEGATIVE,
  ZN_SINGULAR) = range(9)
 ZN_SUMS = 45   # doubles per sector: Sf, Sg, Sff, Sgg, Sfg, SH[P], SHH[P (P + 1) / 2], SHf[P], SHg[P], flagged samples, zeros
+# what the configurations and the info records of the five refinement passes share: the head; the counts, the criterion, the weights
+_REFINE_HEAD = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float), ("lambda0", C.c_float)]
+_ZN_COUNTS = [(k, np.int32) for k in ("n_points", "status", "iterations", "evaluations")]
+_ZN_FLOATS = [(k, np.float32) for k in ("zncc", "gain", "offset", "znssd", "zncc_seed", "shift", "lambda", "last_step")]
+_ZN_WEIGHTS = [("n_valid", np.int32)] + [(k, np.float32) for k in ("weight_sum", "n_eff", "centroid_dx", "centroid_dy")]
 
 
 class LkZnssdConfig(C.Structure):
-    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float),
-                ("lambda0", C.c_float), ("reserved", C.c_int * 3)]
+    _fields_ = _REFINE_HEAD + [("reserved", C.c_int * 3)]
 
 
 # struct lk_znssd as a numpy record
-ZNSSD_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "iterations", "evaluations")] +
-                       [(k, np.float32) for k in ("zncc", "gain", "offset", "znssd", "zncc_seed", "shift", "lambda",
-                                                  "last_step")] +
-                       [("reserved", np.int32, (4,))])
+ZNSSD_DTYPE = np.dtype(_ZN_COUNTS + _ZN_FLOATS + [("reserved", np.int32, (4,))])
 assert ZNSSD_DTYPE.itemsize == 64 and C.sizeof(LkZnssdConfig) == 32
 
 # second-order refinement (include/lk_engine.h: lk_refine_quadratic); the statuses are ZN_*
@@ -236,22 +237,16 @@ QD_PARAMS = 12
 
 
 class LkQuadraticConfig(C.Structure):
-    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float),
-                ("lambda0", C.c_float), ("reserved", C.c_int * 3)]
+    _fields_ = _REFINE_HEAD + [("reserved", C.c_int * 3)]
 
 
 # struct lk_quadratic as a numpy record
-QUADRATIC_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "iterations", "evaluations")] +
-                           [("p", np.float32, (12,))] +
-                           [(k, np.float32) for k in ("zncc", "gain", "offset", "znssd", "zncc_seed", "shift", "lambda",
-                                                      "last_step", "bend")] +
-                           [("reserved", np.int32, (7,))])
+QUADRATIC_DTYPE = np.dtype(_ZN_COUNTS + [("p", np.float32, (12,))] + _ZN_FLOATS + [("bend", np.float32), ("reserved", np.int32, (7,))])
 assert QUADRATIC_DTYPE.itemsize == 128 and C.sizeof(LkQuadraticConfig) == 32
 
 # B-spline refinement (include/lk_engine.h: lk_refine_spline); statuses ZN_*, info ZNSSD_DTYPE, sums ZN_SUMS
 class LkSplineConfig(C.Structure):
-    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float),
-                ("lambda0", C.c_float), ("order", C.c_int), ("reserved", C.c_int * 2)]
+    _fields_ = _REFINE_HEAD + [("order", C.c_int), ("reserved", C.c_int * 2)]
 
 
 assert C.sizeof(LkSplineConfig) == 32
@@ -261,35 +256,23 @@ LOG2E = 1.4426950408889634   # log2(e): inv = float32(LOG2E / (2 sigma_L^2)) is 
 
 
 class LkWeightedConfig(C.Structure):
-    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float),
-                ("lambda0", C.c_float), ("sigma", C.c_float), ("min_fraction", C.c_float), ("mask_rows", C.c_int),
-                ("mask_cols", C.c_int), ("reserved", C.c_int * 3)]
+    _fields_ = _REFINE_HEAD + [("sigma", C.c_float), ("min_fraction", C.c_float), ("mask_rows", C.c_int), ("mask_cols", C.c_int),
+                               ("reserved", C.c_int * 3)]
 
 
 # struct lk_weighted as a numpy record: ZNSSD_DTYPE's first 48 bytes, then the weights'
-WEIGHTED_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "iterations", "evaluations")] +
-                          [(k, np.float32) for k in ("zncc", "gain", "offset", "znssd", "zncc_seed", "shift", "lambda",
-                                                     "last_step")] +
-                          [("n_valid", np.int32)] +
-                          [(k, np.float32) for k in ("weight_sum", "n_eff", "centroid_dx", "centroid_dy")] +
-                          [("reserved", np.int32, (3,))])
+WEIGHTED_DTYPE = np.dtype(_ZN_COUNTS + _ZN_FLOATS + _ZN_WEIGHTS + [("reserved", np.int32, (3,))])
 assert WEIGHTED_DTYPE.itemsize == 80 and C.sizeof(LkWeightedConfig) == 48
 
 
 # composed refinement (include/lk_engine.h: lk_refine_composed); statuses ZN_*, sums ZN_SUMS (order 1) or QD_SUMS (order 2)
 class LkComposedConfig(C.Structure):
-    _fields_ = [("def_slot", C.c_int), ("chi_max", C.c_float), ("max_iters", C.c_int), ("precision", C.c_float),
-                ("lambda0", C.c_float), ("order", C.c_int), ("sampler", C.c_int), ("sigma", C.c_float),
-                ("min_fraction", C.c_float), ("mask_rows", C.c_int), ("mask_cols", C.c_int), ("reserved", C.c_int * 5)]
+    _fields_ = _REFINE_HEAD + [("order", C.c_int), ("sampler", C.c_int), ("sigma", C.c_float), ("min_fraction", C.c_float),
+                               ("mask_rows", C.c_int), ("mask_cols", C.c_int), ("reserved", C.c_int * 5)]
 
 
 # struct lk_composed as a numpy record: QUADRATIC_DTYPE up to bend, then WEIGHTED_DTYPE's words of the weights
-COMPOSED_DTYPE = np.dtype([(k, np.int32) for k in ("n_points", "status", "iterations", "evaluations")] +
-                          [("p", np.float32, (12,))] +
-                          [(k, np.float32) for k in ("zncc", "gain", "offset", "znssd", "zncc_seed", "shift", "lambda",
-                                                     "last_step", "bend")] +
-                          [("n_valid", np.int32)] +
-                          [(k, np.float32) for k in ("weight_sum", "n_eff", "centroid_dx", "centroid_dy")] +
+COMPOSED_DTYPE = np.dtype(_ZN_COUNTS + [("p", np.float32, (12,))] + _ZN_FLOATS + [("bend", np.float32)] + _ZN_WEIGHTS +
                           [("reserved", np.int32, (2,))])
 assert COMPOSED_DTYPE.itemsize == 128 and C.sizeof(LkComposedConfig) == 64
 
@@ -682,34 +665,34 @@ def photometry_from_sums(n, sums8):
     return out[0]
 
 
-def znssd_step_from_sums(model, n, sums, lam):
-    """lk_znssd_step_from_sums (host, the kernel's function): (status, delta [6], crit, gain, offset) of one sector of n
-    samples whose sums, in the model's layout, are `sums` (ZN_SUMS doubles or fewer), at the damping `lam`."""
+def _step_from_sums(name, head, sums, n_sums, lam, n_delta, refused):
+    """What the four *_step_from_sums wrappers share: lib.name(*head, sums, lam, delta, crit, gain_offset, status), `sums` padded
+    with zeros to n_sums doubles; ValueError(name: refused) where the library refuses.  Returns (status, delta, crit, gain, offset)."""
     global _compose_lib
     if _compose_lib is None:
         _compose_lib = load_library()
-    s = np.zeros(ZN_SUMS, np.float64)
+    s = np.zeros(n_sums, np.float64)
     flat = np.asarray(sums, np.float64).reshape(-1)
     s[:len(flat)] = flat
-    delta, crit, go, status = np.zeros(6, np.float64), C.c_double(), np.zeros(2, np.float64), C.c_int32(-1)
-    if _compose_lib.lk_znssd_step_from_sums(int(model), int(n), s.ctypes.data_as(_P), float(lam), delta.ctypes.data_as(_P),
-                                            C.byref(crit), go.ctypes.data_as(_P), C.byref(status)) != 0:
-        raise ValueError(f"lk_znssd_step_from_sums: bad model {model}, n < 0 or a bad lambda")
+    delta, crit, go, status = np.zeros(n_delta, np.float64), C.c_double(), np.zeros(2, np.float64), C.c_int32(-1)
+    if getattr(_compose_lib, name)(*head, s.ctypes.data_as(_P), float(lam), delta.ctypes.data_as(_P), C.byref(crit),
+                                   go.ctypes.data_as(_P), C.byref(status)) != 0:
+        raise ValueError(f"{name}: {refused}")
     return status.value, delta, crit.value, float(go[0]), float(go[1])
+
+
+def znssd_step_from_sums(model, n, sums, lam):
+    """lk_znssd_step_from_sums (host, the kernel's function): (status, delta [6], crit, gain, offset) of one sector of n
+    samples whose sums, in the model's layout, are `sums` (ZN_SUMS doubles or fewer), at the damping `lam`."""
+    return _step_from_sums("lk_znssd_step_from_sums", (int(model), int(n)), sums, ZN_SUMS, lam, 6,
+                           f"bad model {model}, n < 0 or a bad lambda")
 
 
 def quadratic_step_from_sums(n, sums, lam):
     """lk_quadratic_step_from_sums (host, the kernel's function): (status, delta [12], crit, gain, offset) of one sector of n
     samples whose QD_SUMS sums are `sums`, at the damping `lam`."""
-    global _compose_lib
-    if _compose_lib is None:
-        _compose_lib = load_library()
-    s = np.ascontiguousarray(sums, np.float64).reshape(QD_SUMS)
-    delta, crit, go, status = np.zeros(QD_PARAMS, np.float64), C.c_double(), np.zeros(2, np.float64), C.c_int32(-1)
-    if _compose_lib.lk_quadratic_step_from_sums(int(n), s.ctypes.data_as(_P), float(lam), delta.ctypes.data_as(_P), C.byref(crit),
-                                                go.ctypes.data_as(_P), C.byref(status)) != 0:
-        raise ValueError("lk_quadratic_step_from_sums: n < 0 or a bad lambda")
-    return status.value, delta, crit.value, float(go[0]), float(go[1])
+    return _step_from_sums("lk_quadratic_step_from_sums", (int(n),), np.asarray(sums, np.float64).reshape(QD_SUMS), QD_SUMS, lam,
+                           QD_PARAMS, "n < 0 or a bad lambda")
 
 
 def spline_weights(order, t):
@@ -740,34 +723,16 @@ def weight_window(inv, dx, dy):
 def weighted_step_from_sums(model, n_valid, N, sums, lam):
     """lk_weighted_step_from_sums (host, the kernel's function): (status, delta [6], crit, gain, offset) of one sector of
     n_valid samples of total weight N whose weighted sums, in the model's layout, are `sums`, at the damping `lam`."""
-    global _compose_lib
-    if _compose_lib is None:
-        _compose_lib = load_library()
-    s = np.zeros(ZN_SUMS, np.float64)
-    flat = np.asarray(sums, np.float64).reshape(-1)
-    s[:len(flat)] = flat
-    delta, crit, go, status = np.zeros(6, np.float64), C.c_double(), np.zeros(2, np.float64), C.c_int32(-1)
-    if _compose_lib.lk_weighted_step_from_sums(int(model), int(n_valid), float(N), s.ctypes.data_as(_P), float(lam),
-                                               delta.ctypes.data_as(_P), C.byref(crit), go.ctypes.data_as(_P), C.byref(status)) != 0:
-        raise ValueError(f"lk_weighted_step_from_sums: bad model {model}, n_valid < 0, or a bad N or lambda")
-    return status.value, delta, crit.value, float(go[0]), float(go[1])
+    return _step_from_sums("lk_weighted_step_from_sums", (int(model), int(n_valid), float(N)), sums, ZN_SUMS, lam, 6,
+                           f"bad model {model}, n_valid < 0, or a bad N or lambda")
 
 
 def composed_step_from_sums(order, model, n_valid, N, sums, lam):
     """lk_composed_step_from_sums (host, the kernels' function): (status, delta [12], crit, gain, offset) of one sector of
     n_valid samples of total weight N whose weighted sums are `sums` - the model's layout, ZN_SUMS or fewer, with order 1
     (delta: zeros behind P); QD_SUMS with order 2, where the model plays no part - at the damping `lam`."""
-    global _compose_lib
-    if _compose_lib is None:
-        _compose_lib = load_library()
-    s = np.zeros(QD_SUMS, np.float64)
-    flat = np.asarray(sums, np.float64).reshape(-1)
-    s[:len(flat)] = flat
-    delta, crit, go, status = np.zeros(QD_PARAMS, np.float64), C.c_double(), np.zeros(2, np.float64), C.c_int32(-1)
-    if _compose_lib.lk_composed_step_from_sums(int(order), int(model), int(n_valid), float(N), s.ctypes.data_as(_P), float(lam),
-                                               delta.ctypes.data_as(_P), C.byref(crit), go.ctypes.data_as(_P), C.byref(status)) != 0:
-        raise ValueError(f"lk_composed_step_from_sums: bad order {order} or model {model}, n_valid < 0, or a bad N or lambda")
-    return status.value, delta, crit.value, float(go[0]), float(go[1])
+    return _step_from_sums("lk_composed_step_from_sums", (int(order), int(model), int(n_valid), float(N)), sums, QD_SUMS, lam,
+                           QD_PARAMS, f"bad order {order} or model {model}, n_valid < 0, or a bad N or lambda")
 
 
 def pattern_from_sums(n, sums9, mig_sum, noise_sigma=1.0, max_saturated=1.0):

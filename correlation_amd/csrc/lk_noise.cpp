@@ -248,14 +248,11 @@ int lk_sector_noise(lk_engine *e, const lk_noise_config *cfg, struct lk_sector_n
   a.n_frames = v.n_frames;
   a.level = v.level;
   LK_HIPCHK(st->begin(v.stream));
-  const uint32_t *order = st->order.as<uint32_t>();
-  for (int g = 0; g < 3; ++g) {
+  LK_HIPCHK(lk_pass_each_group(st->order.as<uint32_t>(), count, [&](int group, const uint32_t *order, int n_sectors) {
     a.ev.order = order;
-    a.n_sectors = count[g];
-    if (a.n_sectors > 0)
-      LK_HIPCHK(lk_launch_noise_sectors(a, kLkPassGroups[g], v.stream));
-    order += count[g];
-  }
+    a.n_sectors = n_sectors;
+    return lk_launch_noise_sectors(a, group, v.stream);
+  }));
   LK_HIPCHK(st->end(v.stream));
   std::vector<int64_t> sums(n * kLkNoiseSums);
   LK_HIPCHK(hipMemcpyAsync(sums.data(), st->sums.p, sums.size() * sizeof(int64_t), hipMemcpyDeviceToHost, v.stream));

@@ -1,8 +1,9 @@
 // lk_pass.hpp - the host plumbing the add-on passes share (lk_reseed.cpp, lk_strain.cpp, lk_uncertainty.cpp, lk_outlier.cpp,
-// lk_track.cpp, lk_residual.cpp, lk_pattern.cpp, lk_field.cpp, lk_motion.cpp; the error macro also lk_guess_search.cpp): device buffers that free themselves, the state a
-// pass keeps on its slot of the engine, the upload of caller records, the bounding box and cell grid over the centres, the
-// order of the sectors by lane group.  Host only: no .hip file includes it; the device half is lk_neighbours.hpp and
-// lk_sector_eval.hpp.  A new pass starts here ("adding a pass").
+// lk_track.cpp, lk_residual.cpp, lk_pattern.cpp, lk_field.cpp, lk_motion.cpp, lk_noise.cpp and, through lk_refine.hpp, the five
+// refinement passes; the error macro also lk_guess_search.cpp): device buffers that free themselves, the state a pass keeps on
+// its slot of the engine, the upload of caller records, the bounding box and cell grid over the centres, the order of the
+// sectors by lane group and the launch per group.  Host only: no .hip file includes it; the device half is lk_neighbours.hpp
+// and lk_sector_eval.hpp.  A new pass starts here ("adding a pass").
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -110,6 +111,22 @@ template <class T> int lk_pass_last(lk_engine *e, int which, const char *none_ye
   return LK_ERROR_NONE;
 }
 
+// The whole hook of a pass that launches per lane group (T has count[3], lk_pass_order_by_group's): also the sectors each
+// group took; `state`: for what the pass reports besides.
+template <class T> int lk_pass_last_groups(lk_engine *e, int which, const char *none_yet, float *device_ms, int *count3, T **state = nullptr) {
+  if (!e)
+    return LK_ERROR_BAD_DOMAIN;
+  T *st = nullptr;
+  if (int rc = lk_pass_last(e, which, none_yet, device_ms, &st))
+    return rc;
+  if (count3)
+    for (int g = 0; g < 3; ++g)
+      count3[g] = st->count[g];
+  if (state)
+    *state = st;
+  return LK_ERROR_NONE;
+}
+
 // Records the caller passed (`count` of them) go to the device through `rec` and replace *d_rec, the engine's; null: nothing
 // happens.  R: lk_result or const lk_result.
 template <class R>
@@ -135,6 +152,12 @@ inline int lk_pass_grid(lk_engine *e, const char *who, LkPassState *st, const Lk
   return LK_ERROR_NONE;
 }
 
+// a sector's level-0 sample count: the rectangle's, or the length of its explicit list (rectangle width 0)
+inline int lk_pass_count0(const int4 *h_rect0, const uint32_t *h_off0, size_t s) {
+  const int4 r = h_rect0[s];
+  return r.z > 0 ? r.w : (int)(h_off0[s + 1] - h_off0[s]);
+}
+
 // The sectors by lane group, from the level-0 sample count alone, as the backward solve's tables: h_order holds the sectors
 // of kLkPassGroups[0], then [1], then [2]; count[g] says how many each took.
 constexpr int kLkPassGroups[3] = {16, 64, 512};
@@ -143,14 +166,21 @@ inline void lk_pass_order_by_group(const int4 *h_rect0, const uint32_t *h_off0, 
   size_t at = 0;
   for (int g = 0; g < 3; ++g) {
     const size_t begin = at;
-    for (int s = 0; s < S; ++s) {
-      const int4 r = h_rect0[s];
-      const int n0 = r.z > 0 ? r.w : (int)(h_off0[s + 1] - h_off0[s]);
-      if (lk_bw_group(n0) == kLkPassGroups[g])
+    for (int s = 0; s < S; ++s)
+      if (lk_bw_group(lk_pass_count0(h_rect0, h_off0, (size_t)s)) == kLkPassGroups[g])
         h_order[at++] = (uint32_t)s;
-    }
     count[g] = (int)(at - begin);
   }
+}
+
+// A launch per lane group: launch(group, order, n) for every group that took sectors, with the part of d_order
+// (lk_pass_order_by_group's, on the device) that is its own; the first failure ends the walk.
+template <class F> hipError_t lk_pass_each_group(const uint32_t *d_order, const int count[3], F &&launch) {
+  hipError_t err = hipSuccess;
+  for (int g = 0; g < 3 && err == hipSuccess; d_order += count[g++])
+    if (count[g] > 0)
+      err = launch(kLkPassGroups[g], d_order, count[g]);
+  return err;
 }
 
 // What the kernels of lk_sector_eval.hpp read of the view (LK_VIEW_IMAGES), for the records d_rec; the caller sets `order`

@@ -82,14 +82,11 @@ int lk_pattern_quality(lk_engine *e, const lk_pattern_config *cfg, struct lk_pat
   a.noise_sigma = cfg->noise_sigma;
   a.max_saturated = cfg->max_saturated;
   LK_HIPCHK(st->begin(v.stream));
-  const uint32_t *order = st->order.as<uint32_t>();
-  for (int g = 0; g < 3; ++g) {
+  LK_HIPCHK(lk_pass_each_group(st->order.as<uint32_t>(), count, [&](int group, const uint32_t *order, int n_sectors) {
     a.ev.order = order;
-    a.n_sectors = count[g];
-    if (a.n_sectors > 0)
-      LK_HIPCHK(lk_launch_pattern(a, kLkPassGroups[g], v.stream));
-    order += count[g];
-  }
+    a.n_sectors = n_sectors;
+    return lk_launch_pattern(a, group, v.stream);
+  }));
   LK_HIPCHK(st->end(v.stream));
   LK_HIPCHK(hipMemcpyAsync(out, st->out.p, n * sizeof(struct lk_pattern), hipMemcpyDeviceToHost, v.stream));
   if (sums_out)

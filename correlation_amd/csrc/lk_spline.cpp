@@ -5,26 +5,21 @@
 
 #include <cmath>
 #include <string>
-#include <vector>
 
 #include "../../include/lk_engine.h"
 #include "lk_launch.hpp"
-#include "lk_pass.hpp"
+#include "lk_refine.hpp"
 #include "lk_spline.hpp"
 #include "lk_znssd.hpp"
 
 namespace {
 
-struct SplineState : LkPassState {
-  LkDevBytes rec, guess, order, count0, rec_out, out, sums;
+struct SplineState : LkRefineState {
   LkDevBytes coef;        // the coefficient image, rebuilt by every call
   LkDevBytes points, w4;  // lk_spline_sample
-  std::vector<uint32_t> h_order;
-  std::vector<int32_t> h_count0;
-  int count[3] = {0, 0, 0};
   hipEvent_t ev_mid = nullptr; // behind the build of the coefficient image
   hipError_t init() {
-    const hipError_t err = LkPassState::init(false); // (no cell grid: no bounding box to land)
+    const hipError_t err = LkRefineState::init();
     return err != hipSuccess ? err : hipEventCreate(&ev_mid);
   }
   ~SplineState() override {
@@ -34,10 +29,6 @@ struct SplineState : LkPassState {
 };
 
 const char *const kWhere = "hipEventCreate (lk_refine_spline, lk_spline_coefficients, lk_spline_sample)";
-
-constexpr int kSpDefaultIters = 50; // lk_refine_znssd's defaults
-constexpr float kSpDefaultPrecision = 1e-3f;
-constexpr float kSpDefaultLambda = 1e-3f;
 
 // 3 or 5, or 0 for an order the pass does not have
 int spline_order(int order) { return order == 0 ? 5 : order == 3 || order == 5 ? order : 0; }
@@ -121,99 +112,39 @@ int lk_spline_sample(lk_engine *e, int slot, int order, const float *xy, int n, 
 
 int lk_refine_spline(lk_engine *e, const lk_spline_config *cfg, const lk_result *records, const float *guesses, lk_result *records_out,
                      struct lk_znssd *info_out, double *sums_out) {
-  if (!e)
-    return LK_ERROR_BAD_DOMAIN;
-  if (!cfg)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_spline: no configuration");
-  if (!records_out && !info_out)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_spline: no output (records_out and info_out are both null)");
-  if (cfg->reserved[0] != 0 || cfg->reserved[1] != 0)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_spline: reserved words must be 0");
-  if (spline_order(cfg->order) == 0)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_spline: order must be 3 or 5 (0: 5)");
-  if (records && guesses)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_spline: records and guesses are both given (seeds are one or the other)");
-  if (!std::isfinite(cfg->chi_max))
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_spline: chi_max must be finite (<= 0: the error code alone decides)");
-  if (!std::isfinite(cfg->precision) || !std::isfinite(cfg->lambda0))
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_spline: precision and lambda0 must be finite (<= 0: the default)");
+  LkRefineCall c{"lk_refine_spline", records, guesses, nullptr, nullptr, records_out, info_out, sums_out, sizeof(struct lk_znssd), kLkZnSums};
+  if (int rc = lk_refine_check_head(e, c, cfg))
+    return rc;
   const int order_n = spline_order(cfg->order);
-  const bool held = !records && !guesses;
-  LkPassView v{};
-  if (int rc = lk_internal_pass_view(e, "lk_refine_spline", LK_VIEW_IMAGES | (held ? LK_VIEW_RECORDS : 0), cfg->def_slot, &v))
+  if (order_n == 0)
+    return lk_refine_refuse(e, c, "order must be 3 or 5 (0: 5)");
+  if (int rc = lk_refine_check_view(e, c))
     return rc;
   SplineState *st = nullptr;
-  if (int rc = lk_pass_state(e, LK_PASS_SPLINE, kWhere, &st))
+  if (int rc = lk_refine_prepare(e, c, LK_PASS_SPLINE, kWhere, &st))
     return rc;
-  const size_t n = (size_t)v.S;
-  lk_pass_order_by_group(v.h_rect0, v.h_off0, v.S, st->h_order, st->count);
-  st->h_count0.resize(n);
-  for (size_t s = 0; s < n; ++s) {
-    const int4 r = v.h_rect0[s];
-    st->h_count0[s] = r.z > 0 ? r.w : (int32_t)(v.h_off0[s + 1] - v.h_off0[s]);
-  }
-  LK_HIPCHK(st->order.ensure(n * sizeof(uint32_t)));
-  LK_HIPCHK(st->count0.ensure(n * sizeof(int32_t)));
-  LK_HIPCHK(st->rec_out.ensure(n * sizeof(lk_result)));
-  LK_HIPCHK(st->out.ensure(n * sizeof(struct lk_znssd)));
-  if (sums_out)
-    LK_HIPCHK(st->sums.ensure(n * kLkZnSums * sizeof(double)));
-  LK_HIPCHK(hipMemcpyAsync(st->order.p, st->h_order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
-  LK_HIPCHK(hipMemcpyAsync(st->count0.p, st->h_count0.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-  const lk_result *d_rec = guesses ? nullptr : v.result;
-  if (int rc = lk_pass_records(e, st->rec, records, n, v.stream, &d_rec))
-    return rc;
-  if (guesses) {
-    LK_HIPCHK(st->guess.ensure(n * 6 * sizeof(float)));
-    LK_HIPCHK(hipMemcpyAsync(st->guess.p, guesses, n * 6 * sizeof(float), hipMemcpyHostToDevice, v.stream));
-  }
+  const LkPassView &v = c.v;
   LK_HIPCHK(st->begin(v.stream));
-  if (int rc = spline_build(e, "lk_refine_spline", st, order_n, v.def, v.drows, v.dcols, v.stream))
+  if (int rc = spline_build(e, c.who, st, order_n, v.def, v.drows, v.dcols, v.stream))
     return rc;
   LK_HIPCHK(hipEventRecord(st->ev_mid, v.stream));
   LkSplineArgs a{};
   a.coef = st->coef.as<float>();
-  a.zn.ev = lk_pass_sector_eval(v, d_rec);
-  a.zn.guess = guesses ? st->guess.as<float>() : nullptr;
-  a.zn.count0 = st->count0.as<int32_t>();
-  a.zn.rec_out = st->rec_out.as<lk_result>();
+  lk_refine_fill(a.zn, c, st);
   a.zn.out = st->out.as<struct lk_znssd>();
-  a.zn.sums = sums_out ? st->sums.as<double>() : nullptr;
-  a.zn.level = v.level;
-  a.zn.max_iters = cfg->max_iters < 0 ? kSpDefaultIters : cfg->max_iters;
-  a.zn.chi_max = cfg->chi_max;
-  a.zn.precision = cfg->precision > 0.f ? cfg->precision : kSpDefaultPrecision;
-  a.zn.lambda0 = cfg->lambda0 > 0.f ? cfg->lambda0 : kSpDefaultLambda;
-  const uint32_t *order = st->order.as<uint32_t>();
-  for (int g = 0; g < 3; ++g) {
+  LK_HIPCHK(lk_pass_each_group(st->order.as<uint32_t>(), st->count, [&](int group, const uint32_t *order, int n) {
     a.zn.ev.order = order;
-    a.zn.n_sectors = st->count[g];
-    if (a.zn.n_sectors > 0)
-      LK_HIPCHK(lk_launch_spline(a, v.model, order_n, kLkPassGroups[g], v.stream));
-    order += st->count[g];
-  }
-  LK_HIPCHK(st->end(v.stream));
-  if (records_out)
-    LK_HIPCHK(hipMemcpyAsync(records_out, st->rec_out.p, n * sizeof(lk_result), hipMemcpyDeviceToHost, v.stream));
-  if (info_out)
-    LK_HIPCHK(hipMemcpyAsync(info_out, st->out.p, n * sizeof(struct lk_znssd), hipMemcpyDeviceToHost, v.stream));
-  if (sums_out)
-    LK_HIPCHK(hipMemcpyAsync(sums_out, st->sums.p, n * kLkZnSums * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-  LK_HIPCHK(hipStreamSynchronize(v.stream));
-  st->finished();
-  return LK_ERROR_NONE;
+    a.zn.n_sectors = n;
+    return lk_launch_spline(a, v.model, order_n, group, v.stream);
+  }));
+  return lk_refine_finish(e, c, st);
 }
 
 // bench hook (lk_internal.hpp)
 int lk_internal_spline_last(lk_engine *e, float *device_ms, int *count3, float *build_ms) {
-  if (!e)
-    return LK_ERROR_BAD_DOMAIN;
   SplineState *st = nullptr;
-  if (int rc = lk_pass_last(e, LK_PASS_SPLINE, "lk_internal_spline_last: no lk_refine_spline yet", device_ms, &st))
+  if (int rc = lk_pass_last_groups(e, LK_PASS_SPLINE, "lk_internal_spline_last: no lk_refine_spline yet", device_ms, count3, &st))
     return rc;
-  if (count3)
-    for (int g = 0; g < 3; ++g)
-      count3[g] = st->count[g];
   if (build_ms)
     LK_HIPCHK(hipEventElapsedTime(build_ms, st->ev0, st->ev_mid));
   return LK_ERROR_NONE;

@@ -58,14 +58,11 @@ int lk_parameter_uncertainty(lk_engine *e, const lk_uncertainty_config *cfg, con
   a.out = st->out.as<lk_uncertainty>();
   a.sums = sums_out ? st->sums.as<double>() : nullptr;
   LK_HIPCHK(st->begin(v.stream));
-  const uint32_t *order = st->order.as<uint32_t>();
-  for (int g = 0; g < 3; ++g) {
+  LK_HIPCHK(lk_pass_each_group(st->order.as<uint32_t>(), st->count, [&](int group, const uint32_t *order, int n_sectors) {
     a.ev.order = order;
-    a.n_sectors = st->count[g];
-    if (a.n_sectors > 0)
-      LK_HIPCHK(lk_launch_uncertainty(a, v.model, v.interp, kLkPassGroups[g], v.stream));
-    order += st->count[g];
-  }
+    a.n_sectors = n_sectors;
+    return lk_launch_uncertainty(a, v.model, v.interp, group, v.stream);
+  }));
   LK_HIPCHK(st->end(v.stream));
   LK_HIPCHK(hipMemcpyAsync(out, st->out.p, n * sizeof(lk_uncertainty), hipMemcpyDeviceToHost, v.stream));
   if (sums_out)
@@ -77,15 +74,8 @@ int lk_parameter_uncertainty(lk_engine *e, const lk_uncertainty_config *cfg, con
 
 // bench hook (lk_internal.hpp)
 int lk_internal_uncertainty_last(lk_engine *e, float *device_ms, int *count3) {
-  if (!e)
-    return LK_ERROR_BAD_DOMAIN;
-  UncertaintyState *st = nullptr;
-  if (int rc = lk_pass_last(e, LK_PASS_UNCERTAINTY, "lk_internal_uncertainty_last: no lk_parameter_uncertainty yet", device_ms, &st))
-    return rc;
-  if (count3)
-    for (int g = 0; g < 3; ++g)
-      count3[g] = st->count[g];
-  return LK_ERROR_NONE;
+  return lk_pass_last_groups<UncertaintyState>(e, LK_PASS_UNCERTAINTY, "lk_internal_uncertainty_last: no lk_parameter_uncertainty yet", device_ms,
+                                               count3);
 }
 
 } // extern "C"

@@ -1,30 +1,16 @@
 // lk_znssd.cpp - host side of the ZNSSD refinement (include/lk_engine.h: lk_refine_znssd, lk_znssd_step_from_sums).  The
-// kernel is lk_znssd.hip; criterion and step are lk_znssd.hpp.
+// kernel is lk_znssd.hip; criterion and step are lk_znssd.hpp; what the call does around its launches is lk_refine.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <vector>
 
 #include "../../include/lk_engine.h"
 #include "lk_launch.hpp"
-#include "lk_pass.hpp"
+#include "lk_refine.hpp"
 #include "lk_znssd.hpp"
 
-namespace {
-
-struct ZnssdState : LkPassState {
-  LkDevBytes rec, guess, order, count0, rec_out, out, sums;
-  std::vector<uint32_t> h_order;
-  std::vector<int32_t> h_count0;
-  int count[3] = {0, 0, 0};
-  hipError_t init() { return LkPassState::init(false); } // (no cell grid: no bounding box to land)
-};
-
-constexpr int kZnDefaultIters = 50;       // lk_config's documented defaults, for the words of the configuration left open
-constexpr float kZnDefaultPrecision = 1e-3f;
-constexpr float kZnDefaultLambda = 1e-3f;
-
-} // namespace
+// (the table of level-0 counts grows through it; the passes' units inline it, and the library goes on exporting it)
+template void std::vector<int32_t>::resize(std::vector<int32_t>::size_type);
 
 extern "C" {
 
@@ -38,107 +24,35 @@ int lk_znssd_step_from_sums(int model, int n, const double *sums, float lambda, 
   if (st < 0)
     return LK_ERROR_BAD_DOMAIN;
   *status = st;
-  if (delta6)
-    for (int k = 0; k < 6; ++k)
-      delta6[k] = delta[k];
-  if (crit)
-    *crit = cr.crit;
-  if (gain_offset2) {
-    gain_offset2[0] = cr.gain;
-    gain_offset2[1] = cr.offset;
-  }
+  lk_refine_step_out(delta, 6, cr, delta6, crit, gain_offset2);
   return LK_ERROR_NONE;
 }
 
 int lk_refine_znssd(lk_engine *e, const lk_znssd_config *cfg, const lk_result *records, const float *guesses, lk_result *records_out,
                     struct lk_znssd *info_out, double *sums_out) {
-  if (!e)
-    return LK_ERROR_BAD_DOMAIN;
-  if (!cfg)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_znssd: no configuration");
-  if (!records_out && !info_out)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_znssd: no output (records_out and info_out are both null)");
-  if (cfg->reserved[0] != 0 || cfg->reserved[1] != 0 || cfg->reserved[2] != 0)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_znssd: reserved words must be 0");
-  if (records && guesses)
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_znssd: records and guesses are both given (seeds are one or the other)");
-  if (!std::isfinite(cfg->chi_max))
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_znssd: chi_max must be finite (<= 0: the error code alone decides)");
-  if (!std::isfinite(cfg->precision) || !std::isfinite(cfg->lambda0))
-    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_refine_znssd: precision and lambda0 must be finite (<= 0: the default)");
-  const bool held = !records && !guesses;
-  LkPassView v{};
-  if (int rc = lk_internal_pass_view(e, "lk_refine_znssd", LK_VIEW_IMAGES | (held ? LK_VIEW_RECORDS : 0), cfg->def_slot, &v))
+  LkRefineCall c{"lk_refine_znssd", records, guesses, nullptr, nullptr, records_out, info_out, sums_out, sizeof(struct lk_znssd), kLkZnSums};
+  if (int rc = lk_refine_check_head(e, c, cfg))
     return rc;
-  ZnssdState *st = nullptr;
-  if (int rc = lk_pass_state(e, LK_PASS_ZNSSD, "hipEventCreate (lk_refine_znssd)", &st))
+  if (int rc = lk_refine_check_view(e, c))
     return rc;
-  const size_t n = (size_t)v.S;
-  lk_pass_order_by_group(v.h_rect0, v.h_off0, v.S, st->h_order, st->count);
-  st->h_count0.resize(n);
-  for (size_t s = 0; s < n; ++s) {
-    const int4 r = v.h_rect0[s];
-    st->h_count0[s] = r.z > 0 ? r.w : (int32_t)(v.h_off0[s + 1] - v.h_off0[s]);
-  }
-  LK_HIPCHK(st->order.ensure(n * sizeof(uint32_t)));
-  LK_HIPCHK(st->count0.ensure(n * sizeof(int32_t)));
-  LK_HIPCHK(st->rec_out.ensure(n * sizeof(lk_result)));
-  LK_HIPCHK(st->out.ensure(n * sizeof(struct lk_znssd)));
-  if (sums_out)
-    LK_HIPCHK(st->sums.ensure(n * kLkZnSums * sizeof(double)));
-  LK_HIPCHK(hipMemcpyAsync(st->order.p, st->h_order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, v.stream));
-  LK_HIPCHK(hipMemcpyAsync(st->count0.p, st->h_count0.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-  const lk_result *d_rec = guesses ? nullptr : v.result;
-  if (int rc = lk_pass_records(e, st->rec, records, n, v.stream, &d_rec))
+  LkRefineState *st = nullptr;
+  if (int rc = lk_refine_prepare(e, c, LK_PASS_ZNSSD, "hipEventCreate (lk_refine_znssd)", &st))
     return rc;
-  if (guesses) {
-    LK_HIPCHK(st->guess.ensure(n * 6 * sizeof(float)));
-    LK_HIPCHK(hipMemcpyAsync(st->guess.p, guesses, n * 6 * sizeof(float), hipMemcpyHostToDevice, v.stream));
-  }
   LkZnssdArgs a{};
-  a.ev = lk_pass_sector_eval(v, d_rec);
-  a.guess = guesses ? st->guess.as<float>() : nullptr;
-  a.count0 = st->count0.as<int32_t>();
-  a.rec_out = st->rec_out.as<lk_result>();
+  lk_refine_fill(a, c, st);
   a.out = st->out.as<struct lk_znssd>();
-  a.sums = sums_out ? st->sums.as<double>() : nullptr;
-  a.level = v.level;
-  a.max_iters = cfg->max_iters < 0 ? kZnDefaultIters : cfg->max_iters;
-  a.chi_max = cfg->chi_max;
-  a.precision = cfg->precision > 0.f ? cfg->precision : kZnDefaultPrecision;
-  a.lambda0 = cfg->lambda0 > 0.f ? cfg->lambda0 : kZnDefaultLambda;
-  LK_HIPCHK(st->begin(v.stream));
-  const uint32_t *order = st->order.as<uint32_t>();
-  for (int g = 0; g < 3; ++g) {
+  LK_HIPCHK(st->begin(c.v.stream));
+  LK_HIPCHK(lk_pass_each_group(st->order.as<uint32_t>(), st->count, [&](int group, const uint32_t *order, int n) {
     a.ev.order = order;
-    a.n_sectors = st->count[g];
-    if (a.n_sectors > 0)
-      LK_HIPCHK(lk_launch_znssd(a, v.model, v.interp, kLkPassGroups[g], v.stream));
-    order += st->count[g];
-  }
-  LK_HIPCHK(st->end(v.stream));
-  if (records_out)
-    LK_HIPCHK(hipMemcpyAsync(records_out, st->rec_out.p, n * sizeof(lk_result), hipMemcpyDeviceToHost, v.stream));
-  if (info_out)
-    LK_HIPCHK(hipMemcpyAsync(info_out, st->out.p, n * sizeof(struct lk_znssd), hipMemcpyDeviceToHost, v.stream));
-  if (sums_out)
-    LK_HIPCHK(hipMemcpyAsync(sums_out, st->sums.p, n * kLkZnSums * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-  LK_HIPCHK(hipStreamSynchronize(v.stream));
-  st->finished();
-  return LK_ERROR_NONE;
+    a.n_sectors = n;
+    return lk_launch_znssd(a, c.v.model, c.v.interp, group, c.v.stream);
+  }));
+  return lk_refine_finish(e, c, st);
 }
 
 // bench hook (lk_internal.hpp)
 int lk_internal_znssd_last(lk_engine *e, float *device_ms, int *count3) {
-  if (!e)
-    return LK_ERROR_BAD_DOMAIN;
-  ZnssdState *st = nullptr;
-  if (int rc = lk_pass_last(e, LK_PASS_ZNSSD, "lk_internal_znssd_last: no lk_refine_znssd yet", device_ms, &st))
-    return rc;
-  if (count3)
-    for (int g = 0; g < 3; ++g)
-      count3[g] = st->count[g];
-  return LK_ERROR_NONE;
+  return lk_pass_last_groups<LkRefineState>(e, LK_PASS_ZNSSD, "lk_internal_znssd_last: no lk_refine_znssd yet", device_ms, count3);
 }
 
 } // extern "C"

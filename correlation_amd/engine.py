@@ -13,6 +13,8 @@ from . import _ffi
 from ._ffi import (FM_U, FM_UV, FM_UVQ, FM_UVUXUYVXVY, IM_BICUBIC, IM_BILINEAR,  # noqa: F401
                    IM_NEAREST, IMG_DEF, IMG_NXT, IMG_UND, RESULT_DTYPE, LkConfig, LkStats)
 
+_ABSENT = object()   # (HipCorrelationEngine._refine) in place of an argument that a refinement pass does not have
+
 
 class LkError(RuntimeError):
     def __init__(self, code, message):
@@ -517,6 +519,38 @@ class HipCorrelationEngine:
         """lk_map_owner: the residual map's owner rule on the host (no engine needed)."""
         return _ffi.map_owner(centers, X, Y, radius, good)
 
+    # ---- what the five refinement passes share ----------------------------------------------------------------
+    def _refine(self, name, cfg_type, head, words, info_dtype, n_sums, return_sums, records, guesses, second=_ABSENT, mask=_ABSENT):
+        """One call of the refinement pass `name`.  head: (def_slot, chi_max, max_iters, precision, lambda0), max_iters < 0 and
+        precision <= 0 taking the engine's own; words: the configuration's words behind them, a mask's dimensions following.
+        second, mask: _ABSENT in a pass without the argument.  Returns (records, info) and, with return_sums, the sums."""
+        def_slot, chi_max, max_iters, precision, lambda0 = head
+        S, m = self.n_sectors, None if mask is None or mask is _ABSENT else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        if m is not None and m.ndim != 2:
+            raise ValueError(name[3:] + ": mask must be [rows][cols]")
+        if mask is not _ABSENT:
+            words += m.shape if m is not None else (0, 0)
+        cfg = cfg_type(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
+                       float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0), *words)
+        rec = None if records is None else np.ascontiguousarray(records, RESULT_DTYPE).reshape(S)
+        g, g2 = (None if a is None or a is _ABSENT else np.ascontiguousarray(a, np.float32).reshape(S, 6) for a in (guesses, second))
+        out, info = np.zeros(S, RESULT_DTYPE), np.zeros(S, info_dtype)
+        sums = np.zeros((S, n_sums), np.float64) if return_sums else None
+
+        def ptr(a, as_type=C.c_void_p):
+            return a.ctypes.data_as(as_type) if a is not None else None
+        args = [ptr(m)] * (mask is not _ABSENT) + [ptr(rec), ptr(g, _ffi._F)] + [ptr(g2, _ffi._F)] * (second is not _ABSENT)
+        self._chk(getattr(self.lib, name)(self._h, C.byref(cfg), *args, ptr(out), ptr(info), ptr(sums)))
+        return (out, info, sums) if return_sums else (out, info)
+
+    def _refine_last(self, name, extra=False):
+        """A refinement pass's bench hook: (device ms, count3) and, with extra, one more float behind them."""
+        ms, cnt, more = C.c_float(), (C.c_int * 3)(), C.c_float()
+        fn = getattr(self.lib, name)
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)] + [C.POINTER(C.c_float)] * extra
+        self._chk(fn(self._h, C.byref(ms), cnt, *[C.byref(more)] * extra))
+        return (ms.value, tuple(cnt), more.value) if extra else (ms.value, tuple(cnt))
+
     # ---- ZNSSD refinement: the sub-pixel solve that does not mind the lighting ----------------------------
     def refine_znssd(self, records=None, guesses=None, def_slot=-1, chi_max=0.0, max_iters=-1, precision=0.0, lambda0=0.0,
                      return_sums=False):
@@ -525,28 +559,12 @@ class HipCorrelationEngine:
         given [S], else the engine-held ones of the last batch solve.  max_iters < 0 and precision <= 0: the engine's own.
         Returns (records RESULT_DTYPE [S], info ZNSSD_DTYPE [S]) and, with return_sums, the 45 double sums of every sector
         at the returned parameters [S][45].  No engine state changes."""
-        cfg = _ffi.LkZnssdConfig(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
-                                 float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0))
-        rec = g = None
-        if records is not None:
-            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
-        if guesses is not None:
-            g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
-        out = np.zeros(self.n_sectors, RESULT_DTYPE)
-        info = np.zeros(self.n_sectors, _ffi.ZNSSD_DTYPE)
-        sums = np.zeros((self.n_sectors, _ffi.ZN_SUMS), np.float64) if return_sums else None
-        self._chk(self.lib.lk_refine_znssd(self._h, C.byref(cfg), rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
-                                           _ffi.fptr(g) if g is not None else None, out.ctypes.data_as(C.c_void_p),
-                                           info.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p) if return_sums else None))
-        return (out, info, sums) if return_sums else (out, info)
+        return self._refine("lk_refine_znssd", _ffi.LkZnssdConfig, (def_slot, chi_max, max_iters, precision, lambda0), (),
+                            _ffi.ZNSSD_DTYPE, _ffi.ZN_SUMS, return_sums, records, guesses)
 
     def znssd_last(self):
         """Bench hook: (device ms, the sectors the 16-, 64- and 512-lane groups took) of the last refine_znssd call."""
-        ms, cnt = C.c_float(), (C.c_int * 3)()
-        fn = self.lib.lk_internal_znssd_last
-        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-        self._chk(fn(self._h, C.byref(ms), cnt))
-        return ms.value, tuple(cnt)
+        return self._refine_last("lk_internal_znssd_last")
 
     @staticmethod
     def znssd_step_from_sums(model, n, sums, lam):
@@ -561,31 +579,12 @@ class HipCorrelationEngine:
         and the returned records written.  second: [S][6] second-order seeds in level-0 scale (None: zeros); feeding
         (records, info["p"][:, 6:]) back in continues a refinement.  Returns (records RESULT_DTYPE [S], info QUADRATIC_DTYPE
         [S]) and, with return_sums, the 88 double sums of every sector at the returned parameters.  No engine state changes."""
-        cfg = _ffi.LkQuadraticConfig(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
-                                     float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0))
-        rec = g = g2 = None
-        if records is not None:
-            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
-        if guesses is not None:
-            g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
-        if second is not None:
-            g2 = np.ascontiguousarray(second, np.float32).reshape(self.n_sectors, 6)
-        out = np.zeros(self.n_sectors, RESULT_DTYPE)
-        info = np.zeros(self.n_sectors, _ffi.QUADRATIC_DTYPE)
-        sums = np.zeros((self.n_sectors, _ffi.QD_SUMS), np.float64) if return_sums else None
-        self._chk(self.lib.lk_refine_quadratic(self._h, C.byref(cfg), rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
-                                               _ffi.fptr(g) if g is not None else None, _ffi.fptr(g2) if g2 is not None else None,
-                                               out.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p),
-                                               sums.ctypes.data_as(C.c_void_p) if return_sums else None))
-        return (out, info, sums) if return_sums else (out, info)
+        return self._refine("lk_refine_quadratic", _ffi.LkQuadraticConfig, (def_slot, chi_max, max_iters, precision, lambda0), (),
+                            _ffi.QUADRATIC_DTYPE, _ffi.QD_SUMS, return_sums, records, guesses, second=second)
 
     def quadratic_last(self):
         """Bench hook: (device ms, the sectors the 16-, 64- and 512-lane groups took) of the last refine_quadratic call."""
-        ms, cnt = C.c_float(), (C.c_int * 3)()
-        fn = self.lib.lk_internal_quadratic_last
-        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-        self._chk(fn(self._h, C.byref(ms), cnt))
-        return ms.value, tuple(cnt)
+        return self._refine_last("lk_internal_quadratic_last")
 
     @staticmethod
     def quadratic_step_from_sums(n, sums, lam):
@@ -599,29 +598,13 @@ class HipCorrelationEngine:
         (order 5) B-spline of the prefiltered level-py_start image; the engine's interpolation plays no part.  Arguments and
         return as refine_znssd: (records RESULT_DTYPE [S], info ZNSSD_DTYPE [S]) and, with return_sums, the 45 double sums
         [S][45].  No engine state changes."""
-        cfg = _ffi.LkSplineConfig(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
-                                  float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0), int(order))
-        rec = g = None
-        if records is not None:
-            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
-        if guesses is not None:
-            g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
-        out = np.zeros(self.n_sectors, RESULT_DTYPE)
-        info = np.zeros(self.n_sectors, _ffi.ZNSSD_DTYPE)
-        sums = np.zeros((self.n_sectors, _ffi.ZN_SUMS), np.float64) if return_sums else None
-        self._chk(self.lib.lk_refine_spline(self._h, C.byref(cfg), rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
-                                            _ffi.fptr(g) if g is not None else None, out.ctypes.data_as(C.c_void_p),
-                                            info.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p) if return_sums else None))
-        return (out, info, sums) if return_sums else (out, info)
+        return self._refine("lk_refine_spline", _ffi.LkSplineConfig, (def_slot, chi_max, max_iters, precision, lambda0), (int(order),),
+                            _ffi.ZNSSD_DTYPE, _ffi.ZN_SUMS, return_sums, records, guesses)
 
     def spline_last(self):
         """Bench hook: (device ms, the sectors the 16-, 64- and 512-lane groups took, of that time the build of the
         coefficient image) of the last refine_spline call."""
-        ms, cnt, build = C.c_float(), (C.c_int * 3)(), C.c_float()
-        fn = self.lib.lk_internal_spline_last
-        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float)]
-        self._chk(fn(self._h, C.byref(ms), cnt, C.byref(build)))
-        return ms.value, tuple(cnt), build.value
+        return self._refine_last("lk_internal_spline_last", extra=True)
 
     def spline_coefficients(self, slot, order=5):
         """lk_spline_coefficients: the float32 B-spline coefficient image [rows][cols] of the level-py_start image of `slot`,
@@ -653,35 +636,13 @@ class HipCorrelationEngine:
         undeformed image, nonzero = use (None: every pixel); min_fraction: a sector with fewer than min_fraction * n_L
         samples of positive weight is ZN_TOO_FEW.  The other arguments as refine_znssd.  Returns (records RESULT_DTYPE [S],
         info WEIGHTED_DTYPE [S]) and, with return_sums, the 45 weighted double sums [S][45].  No engine state changes."""
-        m = None
-        if mask is not None:
-            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-            if m.ndim != 2:
-                raise ValueError("refine_weighted: mask must be [rows][cols]")
-        cfg = _ffi.LkWeightedConfig(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
-                                    float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0), float(sigma),
-                                    float(min_fraction), m.shape[0] if m is not None else 0, m.shape[1] if m is not None else 0)
-        rec = g = None
-        if records is not None:
-            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
-        if guesses is not None:
-            g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
-        out = np.zeros(self.n_sectors, RESULT_DTYPE)
-        info = np.zeros(self.n_sectors, _ffi.WEIGHTED_DTYPE)
-        sums = np.zeros((self.n_sectors, _ffi.ZN_SUMS), np.float64) if return_sums else None
-        self._chk(self.lib.lk_refine_weighted(self._h, C.byref(cfg), m.ctypes.data_as(C.c_void_p) if m is not None else None,
-                                              rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
-                                              _ffi.fptr(g) if g is not None else None, out.ctypes.data_as(C.c_void_p),
-                                              info.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p) if return_sums else None))
-        return (out, info, sums) if return_sums else (out, info)
+        return self._refine("lk_refine_weighted", _ffi.LkWeightedConfig, (def_slot, chi_max, max_iters, precision, lambda0),
+                            (float(sigma), float(min_fraction)), _ffi.WEIGHTED_DTYPE, _ffi.ZN_SUMS, return_sums, records, guesses,
+                            mask=mask)
 
     def weighted_last(self):
         """Bench hook: (device ms, the sectors the 16-, 64- and 512-lane groups took) of the last refine_weighted call."""
-        ms, cnt = C.c_float(), (C.c_int * 3)()
-        fn = self.lib.lk_internal_weighted_last
-        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-        self._chk(fn(self._h, C.byref(ms), cnt))
-        return ms.value, tuple(cnt)
+        return self._refine_last("lk_internal_weighted_last")
 
     @staticmethod
     def weight_window(inv, dx, dy):
@@ -701,39 +662,13 @@ class HipCorrelationEngine:
         sigma, mask and min_fraction, each chosen independently.  second: [S][6] second-order seeds, order 2 only.  Returns
         (records RESULT_DTYPE [S], info COMPOSED_DTYPE [S]) and, with return_sums, the weighted double sums [S][45] (order 1)
         or [S][88] (order 2).  No engine state changes."""
-        m = None
-        if mask is not None:
-            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
-            if m.ndim != 2:
-                raise ValueError("refine_composed: mask must be [rows][cols]")
-        cfg = _ffi.LkComposedConfig(int(def_slot), float(chi_max), int(max_iters) if max_iters >= 0 else int(self.cfg.max_iters),
-                                    float(precision) if precision > 0 else float(self.cfg.precision), float(lambda0), int(order),
-                                    int(sampler), float(sigma), float(min_fraction), m.shape[0] if m is not None else 0,
-                                    m.shape[1] if m is not None else 0)
-        rec = g = g2 = None
-        if records is not None:
-            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(self.n_sectors)
-        if guesses is not None:
-            g = np.ascontiguousarray(guesses, np.float32).reshape(self.n_sectors, 6)
-        if second is not None:
-            g2 = np.ascontiguousarray(second, np.float32).reshape(self.n_sectors, 6)
-        out = np.zeros(self.n_sectors, RESULT_DTYPE)
-        info = np.zeros(self.n_sectors, _ffi.COMPOSED_DTYPE)
-        sums = np.zeros((self.n_sectors, _ffi.QD_SUMS if int(order) == 2 else _ffi.ZN_SUMS), np.float64) if return_sums else None
-        self._chk(self.lib.lk_refine_composed(self._h, C.byref(cfg), m.ctypes.data_as(C.c_void_p) if m is not None else None,
-                                              rec.ctypes.data_as(C.c_void_p) if rec is not None else None,
-                                              _ffi.fptr(g) if g is not None else None, _ffi.fptr(g2) if g2 is not None else None,
-                                              out.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p),
-                                              sums.ctypes.data_as(C.c_void_p) if return_sums else None))
-        return (out, info, sums) if return_sums else (out, info)
+        return self._refine("lk_refine_composed", _ffi.LkComposedConfig, (def_slot, chi_max, max_iters, precision, lambda0),
+                            (int(order), int(sampler), float(sigma), float(min_fraction)), _ffi.COMPOSED_DTYPE,
+                            _ffi.QD_SUMS if int(order) == 2 else _ffi.ZN_SUMS, return_sums, records, guesses, second=second, mask=mask)
 
     def composed_last(self):
         """Bench hook: (device ms, the sectors the 16-, 64- and 512-lane groups took) of the last refine_composed call."""
-        ms, cnt = C.c_float(), (C.c_int * 3)()
-        fn = self.lib.lk_internal_composed_last
-        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-        self._chk(fn(self._h, C.byref(ms), cnt))
-        return ms.value, tuple(cnt)
+        return self._refine_last("lk_internal_composed_last")
 
     @staticmethod
     def composed_step_from_sums(order, model, n_valid, N, sums, lam):
