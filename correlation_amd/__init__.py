@@ -28,6 +28,11 @@ from ._ffi import (TRACK_BAD_POINT, TRACK_DEGENERATE, TRACK_DTYPE, TRACK_INCREME
                    gauges_from_tracks, track_step)
 from ._ffi import (MOTION_AFFINE, MOTION_DEGENERATE, MOTION_DTYPE, MOTION_MIN_SECTORS, MOTION_OK, MOTION_RIGID,  # noqa: F401
                    MOTION_SIMILARITY, MOTION_TOO_FEW, MOTION_TRANSLATION, motion_apply, motion_from_sums, motion_remove)
+from ._ffi import (LENS_AFFINE, LENS_CORRECTED, LENS_DEGENERATE, LENS_DTYPE, LENS_FRAME_DTYPE, LENS_FRAME_OK,  # noqa: F401
+                   LENS_FRAME_TOO_FEW, LENS_FREE_CENTRE, LENS_FREE_K1, LENS_FREE_K2, LENS_FREE_P1, LENS_FREE_P2, LENS_MAX_ITERS,
+                   LENS_NOT_GOOD, LENS_OK, LENS_OUTSIDE, LENS_PARAMS, LENS_Q, LENS_RESULT_DTYPE, LENS_SIMILARITY, LENS_STEP_DTYPE,
+                   LENS_TRANSLATION, lens_correct_records, lens_distort, lens_step_from_sums, lens_sums_len, lens_undistort,
+                   make_lens)
 from ._ffi import (MAP_NO_OWNER, PHOTO_BAD_RECORD, PHOTO_FLAT, PHOTO_OK, PHOTO_OUT_OF_IMAGE, PHOTO_SUMS,  # noqa: F401
                    PHOTO_TOO_FEW, PHOTOMETRY_DTYPE, map_owner, photometry_from_sums)
 from ._ffi import (ZN_BAD_SEED, ZN_CONVERGED, ZN_FLAT, ZN_MAX_ITERS, ZN_NEGATIVE, ZN_OUT_OF_IMAGE, ZN_SINGULAR,  # noqa: F401

@@ -190,6 +190,43 @@ MOTION_DTYPE = np.dtype([(k, np.float32) for k in ("cx", "cy", "tx", "ty", "axx"
                         [(k, np.int32) for k in ("n_fit", "n_rejected", "status", "passes_run")])
 assert MOTION_DTYPE.itemsize == 64 and C.sizeof(LkMotionConfig) == 32
 
+# lens distortion (include/lk_engine.h: lk_lens_fit, lk_lens_correct)
+LENS_TRANSLATION, LENS_SIMILARITY, LENS_AFFINE = range(3)
+LENS_FREE_K1, LENS_FREE_K2, LENS_FREE_P1, LENS_FREE_P2, LENS_FREE_CENTRE = 1, 2, 4, 8, 16
+LENS_OK, LENS_MAX_ITERS, LENS_DEGENERATE = range(3)
+LENS_FRAME_OK, LENS_FRAME_TOO_FEW = range(2)
+LENS_Q = {LENS_TRANSLATION: 2, LENS_SIMILARITY: 4, LENS_AFFINE: 6}
+LENS_CORRECTED, LENS_NOT_GOOD, LENS_OUTSIDE = range(3)   # status of a record of lk_lens_correct
+
+
+def lens_sums_len(nuisance):
+    """doubles of a frame's sums: {n, the upper triangle of the W x W products (W = 7 + Q), n_outside}"""
+    w = 7 + LENS_Q[int(nuisance)]
+    return w * (w + 1) // 2 + 2
+
+
+class LkLensConfig(C.Structure):
+    _fields_ = [("source", C.c_int), ("chi_max", C.c_float), ("reserved", C.c_int * 2)]
+
+
+class LkLensFitConfig(C.Structure):
+    _fields_ = [("source", C.c_int), ("chi_max", C.c_float), ("min_sectors", C.c_int), ("free", C.c_uint), ("nuisance", C.c_int),
+                ("max_iters", C.c_int), ("tol", C.c_double), ("reserved", C.c_int * 2)]
+
+
+# lk_lens, lk_lens_result, lk_lens_frame and lk_lens_step as numpy records
+LENS_DTYPE = np.dtype([(k, np.float64) for k in ("cx", "cy", "rn", "k1", "k2", "p1", "p2", "reserved")])
+LENS_PARAMS = ("k1", "k2", "p1", "p2", "cx", "cy")   # the order of sigma, delta and the lens columns of a row
+LENS_RESULT_DTYPE = np.dtype([("lens", LENS_DTYPE), ("sigma", np.float64, 6), ("rms_before", np.float64), ("rms", np.float64),
+                              ("last_step", np.float64)] +
+                             [(k, np.int32) for k in ("status", "iterations", "n_records", "n_frames_used", "n_outside", "reserved")])
+LENS_FRAME_DTYPE = np.dtype([("nuisance", np.float64, 6), ("rms", np.float64), ("n", np.int32), ("status", np.int32)])
+LENS_STEP_DTYPE = np.dtype([("delta", np.float64, 6), ("sigma", np.float64, 6), ("chi2", np.float64), ("chi2_profiled", np.float64),
+                            ("scaled_step", np.float64)] +
+                           [(k, np.int32) for k in ("status", "n_records", "n_frames_used", "n_outside")])
+assert LENS_DTYPE.itemsize == 64 and LENS_RESULT_DTYPE.itemsize == 160 and LENS_FRAME_DTYPE.itemsize == 64
+assert LENS_STEP_DTYPE.itemsize == 136 and C.sizeof(LkLensConfig) == 16 and C.sizeof(LkLensFitConfig) == 40
+
 # photometry and the residual map (include/lk_engine.h: lk_photometry, lk_residual_map)
 PHOTO_OK, PHOTO_BAD_RECORD, PHOTO_OUT_OF_IMAGE, PHOTO_TOO_FEW, PHOTO_FLAT = range(5)
 PHOTO_SUMS = 8   # doubles per sector: sum f, sum g, sum f^2, sum g^2, sum f g, sum V^2, flagged samples, max |V|
@@ -438,6 +475,12 @@ SYMBOLS = {
     "lk_motion_from_sums": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "lk_motion_apply": (C.c_int, [_P, C.c_int, _F, _F]),
     "lk_motion_remove": (C.c_int, [C.c_int, _P, C.c_float, C.c_float, _P, _P]),
+    "lk_lens_distort": (C.c_int, [_P, C.c_int, _P, _P]),
+    "lk_lens_undistort": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "lk_lens_correct_record": (C.c_int, [C.c_int, _P, C.c_float, C.c_float, _P, _P, C.POINTER(C.c_int)]),
+    "lk_lens_step_from_sums": (C.c_int, [C.c_int, C.c_uint, C.c_double, C.c_int, C.c_int, _P, _P, _P]),
+    "lk_lens_correct": (C.c_int, [_P, C.POINTER(LkLensConfig), _P, C.c_int, _P, _P, _P, _P]),
+    "lk_lens_fit": (C.c_int, [_P, C.POINTER(LkLensFitConfig), _P, C.c_int, _P, _P, _P, _P, _P]),
     "lk_photometry": (C.c_int, [_P, C.POINTER(LkPhotometryConfig), _P, _P, _P]),
     "lk_photometry_from_sums": (C.c_int, [C.c_int, _P, _P]),
     "lk_residual_map": (C.c_int, [_P, C.POINTER(LkResidualMapConfig), _P, _P, _P, _P]),
@@ -894,3 +937,81 @@ def motion_remove(model, motion, centers, records, good=None):
             raise ValueError("lk_motion_remove: an unknown model, FM_U with an A that is not the identity, or an A without an inverse")
         out[s] = one[0]
     return out
+
+
+def make_lens(cx, cy, rn, k1=0.0, k2=0.0, p1=0.0, p2=0.0):
+    """one LENS_DTYPE record"""
+    lens = np.zeros(1, LENS_DTYPE)
+    lens[0] = (cx, cy, rn, k1, k2, p1, p2, 0.0)
+    return lens[0]
+
+
+def _lens_points(lens, xy):
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    one = np.ascontiguousarray(lens, LENS_DTYPE).reshape(1)
+    p = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    return one, p, np.zeros_like(p)
+
+
+def lens_distort(lens, xy):
+    """lk_lens_distort (host, the kernel's model): undistorted positions xy [n][2] -> where the camera shows them, float64."""
+    one, p, out = _lens_points(lens, xy)
+    if _compose_lib.lk_lens_distort(one.ctypes.data_as(_P), len(p), p.ctypes.data_as(_P), out.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_lens_distort: no positions, or a lens that is not finite, has rn <= 0 or a reserved word")
+    return out
+
+
+def lens_undistort(lens, xy, return_status=False):
+    """lk_lens_undistort (host, the kernel's Newton iteration): distorted positions xy [n][2] -> float64 [n][2]; with
+    return_status also uint8 [n]: 0, or LENS_OUTSIDE for a position outside the model's domain (copied)."""
+    one, p, out = _lens_points(lens, xy)
+    status = np.zeros(len(p), np.uint8)
+    if _compose_lib.lk_lens_undistort(one.ctypes.data_as(_P), len(p), p.ctypes.data_as(_P), out.ctypes.data_as(_P),
+                                      status.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_lens_undistort: no positions, or a lens that is not finite, has rn <= 0 or a reserved word")
+    return (out, status) if return_status else out
+
+
+def lens_correct_records(model, lens, centers, records, good=None):
+    """lk_lens_correct_record (host, the kernel's correction) over one frame: records [S] at centers [S][2] without the lens ->
+    (records [S], status uint8 [S]).  good [S]: the records to rewrite (the caller's good rule); None: all of them."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    one_lens = np.ascontiguousarray(lens, LENS_DTYPE).reshape(1)
+    c = np.ascontiguousarray(centers, np.float32).reshape(-1, 2)
+    rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(len(c))
+    out = rec.copy()
+    status = np.full(len(c), LENS_NOT_GOOD, np.uint8)
+    one = np.zeros(1, RESULT_DTYPE)
+    st = C.c_int()
+    for s in range(len(c)):
+        if good is not None and not good[s]:
+            continue
+        if _compose_lib.lk_lens_correct_record(int(model), one_lens.ctypes.data_as(_P), float(c[s, 0]), float(c[s, 1]),
+                                               rec[s:s + 1].ctypes.data_as(_P), one.ctypes.data_as(_P), C.byref(st)) != 0:
+            raise ValueError("lk_lens_correct_record: an unknown model or a refused lens")
+        out[s] = one[0]
+        status[s] = st.value
+    return out, status
+
+
+def lens_step_from_sums(nuisance, free, rn, sums, min_sectors=None):
+    """lk_lens_step_from_sums (host): the sums [F][lens_sums_len(nuisance)] of one evaluation -> (the LENS_STEP_DTYPE record,
+    float64 [F][6] = the step of every frame's nuisance)."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.ascontiguousarray(sums, np.float64)
+    n = lens_sums_len(nuisance) if int(nuisance) in LENS_Q else 1
+    s = s.reshape(-1, n)
+    if min_sectors is None:
+        min_sectors = LENS_Q.get(int(nuisance), 2)
+    out = np.zeros(1, LENS_STEP_DTYPE)
+    dn = np.zeros((len(s), 6), np.float64)
+    if _compose_lib.lk_lens_step_from_sums(int(nuisance), int(free), float(rn), int(min_sectors), len(s), s.ctypes.data_as(_P),
+                                           out.ctypes.data_as(_P), dn.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_lens_step_from_sums: an unknown nuisance, an empty or unknown free, rn <= 0 or min_sectors < Q")
+    return out[0], dn

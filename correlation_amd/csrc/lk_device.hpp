@@ -349,6 +349,29 @@ struct LkMotionArgs {
   double reject;           // (double)cfg->reject; <= 0: no trimming
 };
 
+// Lens distortion (lk_lens.hip, include/lk_engine.h: lk_lens_fit, lk_lens_correct).  The fit: every frame's sums of the rows
+// of lk_lens.hpp in chunks of `chunk` sectors, then the chunks joined; the correction: a thread per (frame, sector).
+struct LkLensFitArgs {
+  const float4 *pack;      // [F][S] {cx, cy, u, v} of a good sector, cx = NaN for one that is not (lk_pack_prep_kernel)
+  const uint8_t *fit_mask; // [S] or null
+  const double *nuisance;  // [F][6] the frames' nuisance parameters of this evaluation
+  double *partial;         // [F][chunks][len]
+  double *sums;            // [F][len], len = lk_lens_sums_len(Q): {n, the triangle, n_outside}
+  lk_lens lens;
+  int n_frames, n_sectors, chunk, chunks, nuisance_kind;
+  double ox, oy;           // o of the nuisance: the centre of the centres' bounding box
+};
+struct LkLensCorrectArgs {
+  const float4 *pack;      // [F][S] as above: the good rule, evaluated once per record
+  const lk_result *rec;    // [F][S]
+  const float2 *center;    // [S]
+  lk_result *rec_out;      // [F][S]
+  float2 *centres_out;     // [S] U(X)
+  uint8_t *status;         // [F][S]
+  lk_lens lens;
+  int n_frames, n_sectors, model;
+};
+
 // Outlier flags (lk_outlier.hip, include/lk_engine.h: lk_flag_outliers): one pass of the (detrended) normalised median test.
 struct LkOutlierArgs {
   LkReseedGrid grid;

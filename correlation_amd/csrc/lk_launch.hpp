@@ -192,3 +192,10 @@ hipError_t lk_launch_field_map(const LkFieldArgs &a, int weight, int frame, int 
 hipError_t lk_launch_motion_pass(const LkMotionArgs &a, hipStream_t st);
 // a thread per (frame, sector): a.rec without the motion a.out[f] -> a.rec_out
 hipError_t lk_launch_motion_remove(const LkMotionArgs &a, hipStream_t st);
+
+// ---- lk_lens.hip: lens distortion (lk_lens_fit, lk_lens_correct)
+// one evaluation of the fit: the sums of every frame's rows (one workgroup per chunk and frame), then the chunks joined by
+// ascending index into a.sums - two kernels; a.chunks = the chunks of a.chunk sectors that cover a.n_sectors
+hipError_t lk_launch_lens_sums(const LkLensFitArgs &a, hipStream_t st);
+// a thread per (frame, sector): a.rec without the lens -> a.rec_out, a.status; frame 0's threads write a.centres_out
+hipError_t lk_launch_lens_correct(const LkLensCorrectArgs &a, hipStream_t st);

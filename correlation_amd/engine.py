@@ -962,6 +962,96 @@ class HipCorrelationEngine:
         """lk_motion_remove: the kernel's removal on the host (no engine needed)."""
         return _ffi.motion_remove(model, motion, centers, records, good)
 
+    # ---- lens distortion (include/lk_engine.h: lk_lens_fit, lk_lens_correct) -------------
+    def _lens_records(self, who, n_frames, records, source):
+        """the records / n_frames / source arguments shared by lens_fit and lens_correct, as rigid_motion's"""
+        if source is None:
+            source = _ffi.TRACK_RECORDS_CALLER if records is not None else _ffi.TRACK_RECORDS_ENGINE
+        S = self.n_sectors
+        rec = None
+        if records is not None:
+            rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(-1, S)
+            if n_frames is None:
+                n_frames = rec.shape[0]
+            elif int(n_frames) > rec.shape[0]:
+                raise ValueError(who + ": fewer frames of records than n_frames")
+        elif source == _ffi.TRACK_RECORDS_WINDOW and not n_frames:
+            n_frames = self._seq_frames
+            if n_frames == 0 and self.lib.lk_get_sequence_results_device(self._h, None, None) == 0:
+                raise ValueError(who + ": a window this object did not launch is held; pass its n_frames")
+        elif n_frames is None:
+            n_frames = 1
+        return int(source), int(n_frames), rec
+
+    def lens_default(self):
+        """The start of lens_fit: the centre of the bounding box of the committed centres, rn = half its diagonal, no
+        distortion (a LENS_DTYPE record)."""
+        c = np.float32([self.sector_info(s)[1:] for s in range(self.n_sectors)]).astype(np.float64)
+        lo, hi = c.min(axis=0), c.max(axis=0)
+        return _ffi.make_lens((lo[0] + hi[0]) / 2.0, (lo[1] + hi[1]) / 2.0, float(np.hypot(*(hi - lo))) / 2.0)
+
+    def lens_fit(self, free=_ffi.LENS_FREE_K1, nuisance=_ffi.LENS_TRANSLATION, init=None, n_frames=None, records=None, source=None,
+                 fit_mask=None, chi_max=0.0, min_sectors=None, max_iters=10, tol=1e-8, return_frames=False, return_sums=False):
+        """lk_lens_fit: the lens from records of a rigidly shifted specimen -> one LENS_RESULT_DTYPE record; with return_frames
+        and / or return_sums a tuple (result, LENS_FRAME_DTYPE [F], float64 [2][F][lens_sums_len(nuisance)] = the sums of the
+        first and of the last evaluation), the parts asked for in that order.  free: LENS_FREE_* bits; init None:
+        lens_default().  records / source / n_frames as rigid_motion.  min_sectors None: the nuisance's Q.  No engine state
+        changes."""
+        source, n_frames, rec = self._lens_records("lens_fit", n_frames, records, source)
+        S = self.n_sectors
+        mask = None
+        if fit_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(fit_mask) != 0, np.uint8).reshape(-1)
+            if len(mask) != S:
+                raise ValueError("lens_fit: fit_mask must have one entry per sector")
+        if init is None:
+            init = self.lens_default()
+        lens = np.ascontiguousarray(init, _ffi.LENS_DTYPE).reshape(1)
+        if min_sectors is None:
+            min_sectors = _ffi.LENS_Q.get(int(nuisance), 2)
+        cfg = _ffi.LkLensFitConfig(source, float(chi_max), int(min_sectors), int(free), int(nuisance), int(max_iters), float(tol))
+        F = max(n_frames, 0)
+        out = np.zeros(1, _ffi.LENS_RESULT_DTYPE)
+        frames = np.zeros(F, _ffi.LENS_FRAME_DTYPE) if return_frames else None
+        sums = np.zeros((2, F, _ffi.lens_sums_len(nuisance)), np.float64) if return_sums and int(nuisance) in _ffi.LENS_Q else None
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self.lib.lk_lens_fit(self._h, C.byref(cfg), ptr(lens), n_frames, ptr(rec), ptr(mask), ptr(out), ptr(frames), ptr(sums)))
+        if not return_frames and not return_sums:
+            return out[0]
+        return (out[0],) + ((frames,) if return_frames else ()) + ((sums,) if return_sums else ())
+
+    def lens_correct(self, lens, n_frames=None, records=None, source=None, chi_max=0.0, return_centres=False, return_status=False):
+        """lk_lens_correct: the records [F][S] with the lens (a LENS_DTYPE record) taken out; with return_centres and / or
+        return_status a tuple (records, float32 [S][2] = U(centre), uint8 [F][S] = LENS_CORRECTED / _NOT_GOOD / _OUTSIDE), the
+        parts asked for in that order.  records / source / n_frames as rigid_motion.  No engine state changes."""
+        source, n_frames, rec = self._lens_records("lens_correct", n_frames, records, source)
+        S = self.n_sectors
+        one = np.ascontiguousarray(lens, _ffi.LENS_DTYPE).reshape(1)
+        cfg = _ffi.LkLensConfig(source, float(chi_max))
+        F = max(n_frames, 0)
+        out = np.zeros((F, S), RESULT_DTYPE)
+        cen = np.zeros((S, 2), np.float32) if return_centres else None
+        status = np.zeros((F, S), np.uint8) if return_status else None
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self.lib.lk_lens_correct(self._h, C.byref(cfg), ptr(one), n_frames, ptr(rec), ptr(out), ptr(cen), ptr(status)))
+        if not return_centres and not return_status:
+            return out
+        return (out,) + ((cen,) if return_centres else ()) + ((status,) if return_status else ())
+
+    def lens_last(self):
+        """Bench hook: (device ms, chunk size, chunks per frame, evaluations, ms of the last evaluation's kernels) of the last
+        lens_fit or lens_correct call."""
+        ms, chunk, chunks, evals, eval_ms = C.c_float(), C.c_int(), C.c_int(), C.c_int(), C.c_float()
+        fn = self.lib.lk_internal_lens_last
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        self._chk(fn(self._h, C.byref(ms), C.byref(chunk), C.byref(chunks), C.byref(evals), C.byref(eval_ms)))
+        return ms.value, chunk.value, chunks.value, evals.value, eval_ms.value
+
     # ---- stand-alone pieces -------------------------------------------------------------
     def evaluate(self, sector, level, p):
         pp = np.zeros(6, np.float32)

@@ -987,6 +987,135 @@ int lk_motion_apply(const lk_motion *m, int n, const float *xy, float *uv_out);
  * pointer, an unknown model, LK_FM_U with an A that is not the identity, or an A without an inverse (out untouched). */
 int lk_motion_remove(int model, const lk_motion *m, float cx, float cy, const lk_result *in, lk_result *out);
 
+/* ---- lens distortion: fitted to records of a rigidly shifted specimen, and taken out of records ---- */
+/* The records hold displacements measured in the distorted image.  A barrel distortion of 3 % at the corner turns a pure
+ * 12 px translation into a field that bends by 0.1 px rms, which lk_strain_field reads as 5e-3 of strain.  lk_lens_fit finds
+ * the lens from records of the unloaded specimen translated a few times (Pan et al. 2013, Yoneyama et al. 2006);
+ * lk_lens_correct takes a lens out of any records (csrc/lk_lens.hpp, csrc/lk_lens.hip, csrc/lk_lens.cpp).
+ *   model     Brown-Conrady in OpenCV's convention with one normalising radius rn > 0 (level-0 pixels) in place of the focal
+ *             lengths.  With rho = (x_u - c) / rn and r2 = rho . rho:
+ *               D(x_u) = c + rn [ rho (1 + k1 r2 + k2 r2^2) + (2 p1 rx ry + p2 (r2 + 2 rx^2),  p1 (r2 + 2 ry^2) + 2 p2 rx ry) ]
+ *             carries an undistorted position to where the camera shows it.  J_D = dD/dx_u is closed-form and symmetric.
+ *   inverse   U = D^-1 by Newton's iteration on rho with J_D, from rho_d, always 6 steps (the error squares: 5e-2, 3e-3, 1e-5,
+ *             1e-10 at a rim distortion of 5 %).  If J_D has det <= 0 (or is not finite) at an iterate or at the result the
+ *             point is OUTSIDE the model's domain: that is a status, and nothing computed from it is written.
+ *   bytes     double arithmetic, only + - * /, no fused multiply-add: the host functions below and the kernels give the same
+ *             bytes.
+ *   good      the shared rule of lk_rigid_motion (`good` there), with cfg->chi_max.
+ *   records   cfg->source = LK_TRACK_RECORDS_CALLER / _ENGINE / _WINDOW with lk_track_points' rules and refusals, exactly as
+ *             lk_rigid_motion (`records` there); a window is read in place.
+ *
+ * lk_lens_correct
+ *   For every good record, with X the committed centre and x = X + (u, v)  (v = 0 for LK_FM_U):
+ *     X_u = U(X),  x_u = U(x),  (u', v') = x_u - X_u;  the record's own gradient becomes F' = J_D(x_u)^-1 F J_D(X_u),
+ *   written back in the model's layout as lk_motion_remove does: LK_FM_UVUXUYVXVY p2 .. p5;  LK_FM_UVQ F = [[1, -q], [q, 1]],
+ *   q' = (F'yx - F'xy) / 2;  LK_FM_UV and LK_FM_U the displacement alone (LK_FM_U: u' alone is written).  Each output is
+ *   rounded to float once; chi, the counts, the error code and undCenterX/Y are copied.
+ *   status_out [n_frames][S]: 0 corrected;  1 not good, copied;  2 X or x outside the model's domain, copied.
+ *   centres_out [S][2] receives U(X) as floats (X itself where X is outside).  The committed centres stay where they are, so
+ *   the passes downstream see corrected displacements at uncorrected positions: a gradient they form over those positions
+ *   is off by the local stretch of the lens, an error of distortion x strain (3 % of a strain, at the corner, for the lens
+ *   above) - second order, and removable by handing them centres_out where they take positions.
+ *   One thread per (frame, sector); the call changes no engine state and is allowed in every mode.
+ *
+ * lk_lens_fit
+ *   nuisance  what a frame's true motion may be, N(X_u), with o the centre of the centres' bounding box as in lk_rigid_motion:
+ *               LK_LENS_TRANSLATION  Q = 2  N = t
+ *               LK_LENS_SIMILARITY   Q = 4  N = t + a (X_u - o) + b (X_u - o)^perp,  (x, y)^perp = (-y, x)
+ *               LK_LENS_AFFINE       Q = 6  N = t + G (X_u - o),  G = [[gxx, gxy], [gyx, gyy]]
+ *             A frame's nuisance parameters {tx, ty | a, b | gxx, gxy, gyx, gyy} are state of the fit and start at 0.
+ *   fit set   the good records with fit_mask[s] != 0 (all good records when fit_mask is NULL); a frame with fewer than
+ *             cfg->min_sectors of them is skipped (LK_LENS_FRAME_TOO_FEW).  A member with X or x outside the domain is
+ *             counted in n_outside and adds nothing.
+ *   rows      per member r = U(X + u) - U(X) - N(U(X)) and, per component, one row W = 7 + Q wide,
+ *               a = [dr/dk1, dr/dk2, dr/dp1, dr/dp2, dr/dcx, dr/dcy | dr/dn (Q) | r],
+ *             analytic: dU/dtheta = -J_D^-1 dD/dtheta at the undistorted point, dD/dc = I - J_D,
+ *             dr/dtheta = dx_u/dtheta - (I + grad N) dX_u/dtheta.  All six lens columns are always formed.
+ *   sums      per frame 2 + W (W + 1) / 2 doubles: {n, the upper triangle, row-major, of sum (a_x a_x^T + a_y a_y^T),
+ *             n_outside} - 47, 68 or 93 doubles.  Order: lk_rigid_motion's (chunks of 2048 sectors by ascending index, the
+ *             test hook LK_LENS_CHUNK=64; one workgroup per (chunk, frame); each lane adds ascending; a fixed butterfly within a
+ *             wavefront, wavefronts ascending, chunks ascending).  A frame's sums are the same bytes alone, inside a longer
+ *             call, from any source and on every run.  sums_out, if not NULL, receives [2][n_frames][that many]: the sums of
+ *             the first evaluation (at init, nuisance 0) and of the last (at the result).
+ *   step      lk_lens_step_from_sums, host, double: every used frame's nuisance block is eliminated by Schur complement
+ *             (a Cholesky of its Jacobi-scaled Q x Q block), the lens block of the free parameters is Jacobi-scaled and
+ *             factored by Cholesky; a pivot <= 1e-10 on either unit diagonal, a diagonal <= 0 or no usable frame gives
+ *             LK_LENS_DEGENERATE (no translation at all; one parameter too many).  While k1 = k2 = p1 = p2 = 0 exactly the
+ *             centre's columns are zero, so lk_lens_fit holds the centre in such an iteration.
+ *   loop      per iteration one evaluation on the device (the chunk sums and their join), one small download, one step;
+ *             stop when max_j |delta_j| / s_j <= tol, s = 1 for the coefficients and rn for the centre, else after
+ *             max_iters: LK_LENS_MAX_ITERS.  A last evaluation at the result gives rms = sqrt(sum |r|^2 / n_records), sigma
+ *             = sqrt of the diagonal of s^2 S^-1 with S the reduced lens block and s^2 = sum |r|^2 / (2 n_records - free
+ *             parameters - Q frames used) (0 for held parameters), n_records, n_frames_used, n_outside.  rms_before is that
+ *             of init with every frame's nuisance at its own best value.  A degenerate step ends the loop with the lens as
+ *             it stood.
+ *   errors    LK_ERROR_BAD_DOMAIN with a message, outputs untouched: the sources' refusals; a null configuration, lens or
+ *             output; rn not finite or <= 0 or any other field of the lens not finite; a non-zero `reserved` of the lens or
+ *             the configuration; and for the fit: empty or unknown bits in `free`; unknown nuisance; the centre free with
+ *             LK_LENS_AFFINE (to first order a shift of the centre is an affine field, which the nuisance absorbs);
+ *             LK_FM_U; max_iters outside 1 .. 32; tol negative or not finite; min_sectors < Q; chi_max not finite.
+ *   scope     not covered: resampling frames into undistorted coordinates; trimming passes; k3 and thin-prism terms;
+ *             lk_group, lk_tracker, the report CSV and the CudaClass adapter. */
+typedef struct lk_lens { double cx, cy, rn, k1, k2, p1, p2, reserved; } lk_lens;   /* 64 bytes; reserved must be 0 */
+enum { LK_LENS_TRANSLATION = 0, LK_LENS_SIMILARITY = 1, LK_LENS_AFFINE = 2 };
+enum { LK_LENS_FREE_K1 = 1, LK_LENS_FREE_K2 = 2, LK_LENS_FREE_P1 = 4, LK_LENS_FREE_P2 = 8, LK_LENS_FREE_CENTRE = 16 };
+enum { LK_LENS_OK = 0, LK_LENS_MAX_ITERS = 1, LK_LENS_DEGENERATE = 2 };
+enum { LK_LENS_FRAME_OK = 0, LK_LENS_FRAME_TOO_FEW = 1 };
+typedef struct lk_lens_config {       /* lk_lens_correct */
+  int   source;        /* LK_TRACK_RECORDS_* */
+  float chi_max;       /* the shared good rule; <= 0: the error code alone decides */
+  int   reserved[2];   /* must be 0 */
+} lk_lens_config;
+typedef struct lk_lens_fit_config {
+  int      source;       /* LK_TRACK_RECORDS_* */
+  float    chi_max;
+  int      min_sectors;  /* per frame, >= Q */
+  unsigned free;         /* LK_LENS_FREE_* bits; held parameters keep init's values */
+  int      nuisance;     /* LK_LENS_TRANSLATION / _SIMILARITY / _AFFINE */
+  int      max_iters;    /* 1 .. 32 */
+  double   tol;          /* >= 0 */
+  int      reserved[2];  /* must be 0 */
+} lk_lens_fit_config;                 /* 40 bytes */
+typedef struct lk_lens_result {       /* 160 bytes: what lk_lens_fit returns */
+  lk_lens lens;
+  double  sigma[6];                   /* of k1, k2, p1, p2, cx, cy; 0 for held parameters */
+  double  rms_before, rms, last_step; /* pixels, pixels, max_j |delta_j| / s_j of the last step taken */
+  int32_t status, iterations, n_records, n_frames_used, n_outside, reserved;
+} lk_lens_result;
+typedef struct lk_lens_frame {        /* 64 bytes */
+  double  nuisance[6];                /* {tx, ty, ...}; those beyond Q are 0 */
+  double  rms;
+  int32_t n, status;                  /* members of the fit set; LK_LENS_FRAME_* */
+} lk_lens_frame;
+typedef struct lk_lens_step {         /* 136 bytes */
+  double  delta[6];                   /* the step of k1, k2, p1, p2, cx, cy; 0 for held parameters */
+  double  sigma[6];
+  double  chi2, chi2_profiled, scaled_step; /* sum |r|^2 of the used frames; the same with every frame's nuisance at its best */
+  int32_t status, n_records, n_frames_used, n_outside;
+} lk_lens_step;
+/* n positions xy [n][2] in doubles -> xy_out [n][2].  LK_ERROR_BAD_DOMAIN for a null pointer, n < 1 or a lens that the
+ * `errors` paragraph refuses.  lk_lens_undistort: status_out [n] (or NULL) 0, or 2 for a position outside the model's domain,
+ * which is copied. */
+int lk_lens_distort(const lk_lens *lens, int n, const double *xy, double *xy_out);
+int lk_lens_undistort(const lk_lens *lens, int n, const double *xy, double *xy_out, uint8_t *status_out);
+/* the kernel's own correction of one record compiled for the host: `in` at the centre (cx, cy) -> `out`, *status (or NULL) 0 or
+ * 2.  The caller applies the good rule.  LK_ERROR_BAD_DOMAIN for a null pointer, an unknown model or a refused lens. */
+int lk_lens_correct_record(int model, const lk_lens *lens, float cx, float cy, const lk_result *in, lk_result *out, int *status);
+/* one Gauss-Newton step from the sums [n_frames][2 + W (W + 1) / 2] of the `sums` paragraph.  nuisance_delta: [n_frames][6]
+ * or NULL, the step of every frame's nuisance (0 for a skipped frame).  With a status other than LK_LENS_OK delta, sigma and
+ * nuisance_delta are 0; chi2, n_records, n_frames_used and n_outside are filled regardless.  LK_ERROR_BAD_DOMAIN for a null
+ * pointer, an unknown nuisance, an empty or unknown `free`, rn not finite or <= 0, n_frames < 1 or min_sectors < Q. */
+int lk_lens_step_from_sums(int nuisance, unsigned free, double rn, int min_sectors, int n_frames, const double *sums,
+                           lk_lens_step *out, double *nuisance_delta);
+/* records: host [n_frames][S] or NULL (see `records`); records_out: host [n_frames][S]; centres_out: [S][2] floats or NULL;
+ * status_out: [n_frames][S] or NULL.  Synchronous.  Changes no engine state. */
+int lk_lens_correct(lk_engine *e, const lk_lens_config *cfg, const lk_lens *lens, int n_frames, const lk_result *records,
+                    lk_result *records_out, float *centres_out, uint8_t *status_out);
+/* init: the start, and the values of the held parameters; fit_mask: host [S] or NULL; out: one record; frames_out: [n_frames]
+ * or NULL; sums_out: see `sums`, or NULL.  Synchronous.  Changes no engine state. */
+int lk_lens_fit(lk_engine *e, const lk_lens_fit_config *cfg, const lk_lens *init, int n_frames, const lk_result *records,
+                const uint8_t *fit_mask, lk_lens_result *out, lk_lens_frame *frames_out, double *sums_out);
+
 /* ---- photometry and the back-warped residual map: the grey values once more ---------------- */
 /* chi is a plain sum of squared grey-level differences: a frame that is 20 % darker gives every sector a large chi although
  * the match is perfect.  lk_photometry evaluates every good sector once at its record's parameters and reports the

@@ -142,6 +142,33 @@ def run_motion():
     return out
 
 
+def run_lens():
+    import correlation_amd as ca
+    e, rec = solved("grid", ca.FM_UVUXUYVXVY, ca.IM_BICUBIC)
+    start = e.lens_default()
+    true = ca.make_lens(start["cx"] + 5.0, start["cy"] - 4.0, start["rn"], -0.03, 0.008)
+    cen = np.float32([e.sector_info(s)[1:] for s in range(e.n_sectors)]).astype(np.float64)
+    seen = ca.lens_undistort(true, cen)
+    frames = np.stack([rec.copy() for _ in range(4)])
+    for f, t in enumerate(((12.0, 0.0), (-12.0, 0.0), (0.0, 9.0), (8.0, -6.0))):   # a shifted specimen seen through the lens
+        frames["p"][f][:, :2] = ca.lens_distort(true, seen + np.float64(t)) - cen
+    frames["error_code"][1][60:64] = 3
+    mask = np.arange(e.n_sectors) % 24 < 18
+    out = {}
+    four = ca.LENS_FREE_K1 | ca.LENS_FREE_K2 | ca.LENS_FREE_CENTRE
+    for nuisance, name, free in ((ca.LENS_TRANSLATION, "translation", four), (ca.LENS_SIMILARITY, "similarity", four),
+                                 (ca.LENS_AFFINE, "affine", ca.LENS_FREE_K1 | ca.LENS_FREE_K2)):
+        for tag, kw in (("", {}), ("_masked", dict(fit_mask=mask)), ("_too_few", dict(min_sectors=e.n_sectors + 1))):
+            fit, per_frame, sums = e.lens_fit(free, nuisance, records=frames, return_frames=True, return_sums=True, **kw)
+            out["lens_" + name + tag + ".fit"] = np.frombuffer(fit.tobytes(), np.uint8)
+            out["lens_" + name + tag + ".frames"] = np.frombuffer(per_frame.tobytes(), np.uint8)
+            out["lens_" + name + tag + ".sums"] = sums
+    fixed, centres, status = e.lens_correct(true, records=frames, return_centres=True, return_status=True)
+    out.update(fields("lens_correct.records", fixed))
+    out["lens_correct.centres"], out["lens_correct.status"] = centres, status
+    return out
+
+
 def run_plan():
     import correlation_amd as ca
     out = {}
@@ -472,6 +499,7 @@ VARIANTS += [("outlier_g%d_cap%s" % (g, cap), {"LK_OUTLIER_GROUP": str(g), "LK_O
 VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (16, 64)]
 VARIANTS += [("field_walk%d" % w, {"LK_FIELD_WALK": str(w)}, run_field) for w in (0, 1)]
 VARIANTS += [("motion_chunk%d" % c, {"LK_MOTION_CHUNK": str(c)}, run_motion) for c in (64, 2048)]
+VARIANTS += [("lens_chunk%d" % c, {"LK_LENS_CHUNK": str(c)}, run_lens) for c in (64, 2048)]
 VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
              ("pattern", {}, run_pattern), ("noise", {}, run_noise), ("znssd", {}, run_znssd), ("quadratic", {}, run_quadratic),
              ("spline", {}, run_spline), ("weighted", {}, run_weighted), ("composed", {}, run_composed)]
