@@ -10,8 +10,8 @@ from ._ffi import (ERROR_BAD_DOMAIN, ERROR_CORRELATION_MAX_ITERS_REACHED, ERROR_
                    FM_UVUXUYVXVY, IM_BICUBIC, IM_BICUBIC_SEPARABLE, IM_BILINEAR, IM_NEAREST, IMG_DEF, IMG_NXT, IMG_UND,
                    LIB_PATH, N_PARAMS, RESULT_DTYPE, SYMBOLS, UPDATE_BACKWARD, UPDATE_FORWARD, compose_inverse,
                    load_library)
-from ._ffi import (FLAVOUR_FAST, FLAVOUR_REFERENCE, FLAVOUR_SAFE, LAUNCH_EVAL, LAUNCH_FINISHER, LAUNCH_MAIN,  # noqa: F401
-                   LAUNCH_REPORT_CAPACITY, LAUNCH_SAFE_PASS, LAUNCH_STARVED)
+from ._ffi import (FLAVOUR_FAST, FLAVOUR_REFERENCE, FLAVOUR_SAFE, LAUNCH_BACKWARD, LAUNCH_BACKWARD_EVAL,  # noqa: F401
+                   LAUNCH_EVAL, LAUNCH_FINISHER, LAUNCH_MAIN, LAUNCH_REPORT_CAPACITY, LAUNCH_SAFE_PASS, LAUNCH_STARVED)
 from ._ffi import (GS_NO_CANDIDATE, GS_OK, GS_TEXTURELESS, GS_TOO_FEW, GS_TOO_LARGE, GS_WEAK,  # noqa: F401
                    GUESS_MATCH_DTYPE)
 from ._ffi import ROTATED_MATCH_DTYPE, RS_MAX_ANGLES, rotation_table  # noqa: F401

@@ -43,7 +43,7 @@ class LkStats(C.Structure):
 
 
 # launch report (include/lk_engine.h: lk_get_launch_report)
-(LAUNCH_MAIN, LAUNCH_STARVED, LAUNCH_FINISHER, LAUNCH_SAFE_PASS, LAUNCH_EVAL) = range(5)
+(LAUNCH_MAIN, LAUNCH_STARVED, LAUNCH_FINISHER, LAUNCH_SAFE_PASS, LAUNCH_EVAL, LAUNCH_BACKWARD, LAUNCH_BACKWARD_EVAL) = range(7)
 FLAVOUR_FAST, FLAVOUR_SAFE, FLAVOUR_REFERENCE = range(3)
 LAUNCH_REPORT_CAPACITY = 64
 

@@ -376,16 +376,26 @@ __global__ void __launch_bounds__(GROUP) lk_backward_eval_kernel(LkBackwardEvalA
 
 } // namespace
 
-hipError_t lk_launch_backward(const LkBackwardArgs &a, int model, int interp, int group, hipStream_t st) {
+// What lk_get_launch_report tells about a backward launch, noted where M, I and G are compile-time values: the SAFE solver,
+// no frame pipeline, no team, no queue.
+template <int M, int I, int G> static inline void bw_report(lk_launch_record *rep, int role, int threads, int sectors, int grid) {
+  if (rep)
+    *rep = lk_launch_record{M, I, G, threads, LK_FLAVOUR_SAFE, 0, role, sectors, 0, 0, grid, 0};
+}
+
+hipError_t lk_launch_backward(const LkBackwardArgs &a, int model, int interp, int group, hipStream_t st, lk_launch_record *rep) {
   return dispatch_sector_kernel(model, interp, group, [&](auto m, auto i, auto g) {
     constexpr int M = decltype(m)::value, I = decltype(i)::value, G = decltype(g)::value;
+    bw_report<M, I, G>(rep, LK_LAUNCH_BACKWARD, sector_group_threads<G>(), a.n_sectors, sector_group_blocks<G>(a.n_sectors));
     return launch_sector_groups<G>(lk_backward_kernel<M, I, G>, a, a.n_sectors, st);
   });
 }
 
-hipError_t lk_launch_backward_eval(const LkBackwardEvalArgs &a, int model, int interp, int group, hipStream_t st) {
+hipError_t lk_launch_backward_eval(const LkBackwardEvalArgs &a, int model, int interp, int group, hipStream_t st,
+                                   lk_launch_record *rep) {
   return dispatch_sector_kernel(model, interp, group, [&](auto m, auto i, auto g) {
     constexpr int M = decltype(m)::value, I = decltype(i)::value, G = decltype(g)::value;
+    bw_report<M, I, G>(rep, LK_LAUNCH_BACKWARD_EVAL, G, 1, 1); // (one workgroup of G threads, not sector_group_threads<G>())
     hipLaunchKernelGGL((lk_backward_eval_kernel<M, I, G>), dim3(1), dim3(G), 0, st, a);
     return hipGetLastError();
   });

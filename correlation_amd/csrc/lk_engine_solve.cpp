@@ -309,7 +309,7 @@ static int launch_all_backward(lk_engine *e, const float *d_guess, lk_result *d_
     b.order = (set ? set->bw_order : e->d_bw_order.p) + e->bw_begin[g];
     b.n_sectors = set ? set->bw_count[g] : e->bw_begin[g + 1] - e->bw_begin[g];
     if (b.n_sectors > 0)
-      HIPCHK(lk_launch_backward(b, e->cfg.fitting_model, e->cfg.interpolation, kBwGroups[g], e->stream));
+      HIPCHK(lk_launch_backward(b, e->cfg.fitting_model, e->cfg.interpolation, kBwGroups[g], e->stream, e->launch_report_slot()));
   }
   return solve_end(e, 1, LK_UPDATE_BACKWARD);
 }
@@ -548,7 +548,8 @@ int lk_correlate(lk_engine *e, int sector, float *guess_inout, lk_result *out) {
     b.n_sectors = 1;
     if ((rc = solve_begin(e)))
       return rc;
-    HIPCHK(lk_launch_backward(b, e->cfg.fitting_model, e->cfg.interpolation, lk_bw_group(level0_count(e, sector)), e->stream));
+    HIPCHK(lk_launch_backward(b, e->cfg.fitting_model, e->cfg.interpolation, lk_bw_group(level0_count(e, sector)), e->stream,
+                              e->launch_report_slot()));
     if ((rc = solve_end(e, 1, LK_UPDATE_BACKWARD)))
       return rc;
   } else {
@@ -721,7 +722,9 @@ int lk_evaluate_backward(lk_engine *e, int sector, int level, const float *p, fl
   for (int i = 0; i < 6; ++i)
     a.p[i] = i < e->P ? p[i] : 0.f;
   a.out = e->d_scratch.p;
-  HIPCHK(lk_launch_backward_eval(a, e->cfg.fitting_model, e->cfg.interpolation, lk_bw_group(level0_count(e, sector)), e->stream));
+  e->launch_report_begin();
+  HIPCHK(lk_launch_backward_eval(a, e->cfg.fitting_model, e->cfg.interpolation, lk_bw_group(level0_count(e, sector)), e->stream,
+                                 e->launch_report_slot()));
   return evaluation_out(e, H36, b6, chi, error);
 }
 

@@ -9,8 +9,8 @@
 #include "lk_device.hpp"
 
 // ---- lk_kernels.hip: the forward solve and the known-answer entry points
-// rep (these three launchers): where to note the instance launched and what the launcher decided for it (lk_get_launch_report);
-// nullptr: nowhere
+// rep (these three launchers and the two of lk_backward.hip): where to note the instance launched and what the launcher
+// decided for it (lk_get_launch_report); nullptr: nowhere
 hipError_t lk_launch_solve(const LkSolveArgs &a, int model, int interp, int group, hipStream_t st, lk_launch_record *rep = nullptr);
 // flavour: 0 fast (root-free Cholesky; a bad pivot raises the gate of the SAFE pass behind it), 1 SAFE (the QR inside the
 // kernel), 2 reference order (a.reference_order = T)
@@ -24,8 +24,11 @@ hipError_t lk_launch_sample(int interp, const uint8_t *def, int rows, int cols, 
                             float4 *out, hipStream_t st);
 
 // ---- lk_backward.hip: the inverse-compositional solve
-hipError_t lk_launch_backward(const LkBackwardArgs &a, int model, int interp, int group, hipStream_t st);
-hipError_t lk_launch_backward_eval(const LkBackwardEvalArgs &a, int model, int interp, int group, hipStream_t st);
+// rep: as lk_launch_solve's (roles LK_LAUNCH_BACKWARD and LK_LAUNCH_BACKWARD_EVAL)
+hipError_t lk_launch_backward(const LkBackwardArgs &a, int model, int interp, int group, hipStream_t st,
+                              lk_launch_record *rep = nullptr);
+hipError_t lk_launch_backward_eval(const LkBackwardEvalArgs &a, int model, int interp, int group, hipStream_t st,
+                                   lk_launch_record *rep = nullptr);
 
 // ---- lk_guess_search.hip: the integer-pixel ZNCC search
 hipError_t lk_launch_guess_search(const LkGuessSearchArgs &a, hipStream_t st);

@@ -167,9 +167,13 @@ template <class F> hipError_t dispatch_sector_kernel(int model, int interp, int 
 // A kernel of `n_sectors` lane groups: rows and wavefronts share workgroups of 256 threads, a 512-lane group is its own.
 // From inside dispatch_sector_kernel: launch_sector_groups<GROUP>(the_kernel<MODEL, INTERP, GROUP>, args, n_sectors, stream).
 template <int GROUP> constexpr int sector_group_threads() { return GROUP <= 64 ? 256 : GROUP; }
-template <int GROUP, class Args> hipError_t launch_sector_groups(void (*kernel)(Args), const Args &a, int n_sectors, hipStream_t st) {
+// the workgroups launch_sector_groups makes for n_sectors lane groups (what a launch report records as its grid)
+template <int GROUP> constexpr int sector_group_blocks(int n_sectors) {
   constexpr int per_block = sector_group_threads<GROUP>() / GROUP;
-  const int blocks = (n_sectors + per_block - 1) / per_block;
+  return (n_sectors + per_block - 1) / per_block;
+}
+template <int GROUP, class Args> hipError_t launch_sector_groups(void (*kernel)(Args), const Args &a, int n_sectors, hipStream_t st) {
+  const int blocks = sector_group_blocks<GROUP>(n_sectors);
   if (blocks <= 0)
     return hipSuccess;
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(sector_group_threads<GROUP>()), 0, st, a);

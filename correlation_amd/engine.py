@@ -1116,9 +1116,9 @@ class HipCorrelationEngine:
         return out
 
     def launch_report(self):
-        """The kernel launches of the most recent solving call (correlate, correlate_all*, a sequence window, evaluate) in
-        launch order: a list of dicts with the fields of lk_launch_record (include/lk_engine.h) but `reserved`.  Raises if
-        the call made more launches than the engine keeps."""
+        """The kernel launches of the most recent solving call (correlate, correlate_all*, a sequence window, evaluate,
+        evaluate_backward) in launch order: a list of dicts with the fields of lk_launch_record (include/lk_engine.h) but
+        `reserved`.  Raises if the call made more launches than the engine keeps."""
         rec = (_ffi.LkLaunchRecord * _ffi.LAUNCH_REPORT_CAPACITY)()
         n, over = C.c_int(), C.c_int()
         self._chk(self.lib.lk_get_launch_report(self._h, rec, _ffi.LAUNCH_REPORT_CAPACITY, C.byref(n), C.byref(over)))

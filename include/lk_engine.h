@@ -1955,7 +1955,9 @@ typedef enum {
   LK_LAUNCH_STARVED = 1,   /* the one-lane kernel of the starved levels, in front of the main launch */
   LK_LAUNCH_FINISHER = 2,  /* the 16-lane finisher of the sectors the one-lane kernel parked */
   LK_LAUNCH_SAFE_PASS = 3, /* the SAFE pass behind a fast launch: 16-lane rows for one pair, the window again for a window */
-  LK_LAUNCH_EVAL = 4       /* the evaluation kernel (lk_evaluate) */
+  LK_LAUNCH_EVAL = 4,      /* the evaluation kernel (lk_evaluate) */
+  LK_LAUNCH_BACKWARD = 5,  /* the backward update's lane-group launch: one per non-empty group, in the order 16, 64, 512 */
+  LK_LAUNCH_BACKWARD_EVAL = 6 /* the backward evaluation kernel (lk_evaluate_backward): one workgroup of `group` threads */
 } lk_launch_role;
 typedef enum { LK_FLAVOUR_FAST = 0, LK_FLAVOUR_SAFE = 1, LK_FLAVOUR_REFERENCE = 2 } lk_launch_flavour;
 #define LK_LAUNCH_REPORT_CAPACITY 64 /* six classes x four launches, a window's SAFE pass per class, and room to spare */
@@ -1974,10 +1976,12 @@ typedef struct {
   int reserved;
 } lk_launch_record;
 /* The launches of the engine's most recent solving call - lk_correlate, lk_correlate_all*, lk_correlate_sequence_async
- * (its SAFE re-run included; a window that runs as the one-pair loop reports its last frame) and lk_evaluate - in the order
- * the host issued them.  out: room for `capacity` records, or NULL to ask for the count alone.  *n_out = records the call
- * made (at most LK_LAUNCH_REPORT_CAPACITY are kept); *overflow = 1 if it made more than are kept.  Host state only:
- * no device call, no synchronisation. */
+ * (its SAFE re-run included; a window that runs as the one-pair loop reports its last frame), lk_evaluate and
+ * lk_evaluate_backward - in the order the host issued them.  A backward solve (lk_set_update) reports one LK_LAUNCH_BACKWARD
+ * record per non-empty lane group (flavour SAFE; seq, team_w and persistent 0; threads 256 for 16 and 64 lanes, 512 for 512).
+ * out: room for `capacity` records, or NULL to ask for the count alone.  *n_out = records the call made (at most
+ * LK_LAUNCH_REPORT_CAPACITY are kept); *overflow = 1 if it made more than are kept.  Host state only: no device call, no
+ * synchronisation. */
 int lk_get_launch_report(lk_engine *e, lk_launch_record *out, int capacity, int *n_out, int *overflow);
 /* Lanes per sector of the next one-pair batch solve (lk_correlate_all*), registration order: groups[s] is the lane group of
  * sector s's size class after promotions and the LK_FORCE_* hooks, or - in reference-order mode - of the batch rule there

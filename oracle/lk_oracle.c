@@ -327,6 +327,17 @@ int lko_interpolate(int interp, const uint8_t *img, int rows, int cols, float x,
   return c.error;
 }
 
+void lko_interpolate_many(int interp, const uint8_t *img, int rows, int cols, const float *xy, int n, float *out4) {
+  for (int k = 0; k < n; ++k) { /* lko_interpolate per point: a fresh context each, so that no error flag carries over */
+    float w = 0.f, wx = 0.f, wy = 0.f;
+    const int err = lko_interpolate(interp, img, rows, cols, xy[2 * k], xy[2 * k + 1], &w, &wx, &wy);
+    out4[4 * k] = w;
+    out4[4 * k + 1] = wx;
+    out4[4 * k + 2] = wy;
+    out4[4 * k + 3] = (float)err;
+  }
+}
+
 /* ------------------------------------------------------------------------------------ */
 /* warp model                                                                           */
 /* ------------------------------------------------------------------------------------ */

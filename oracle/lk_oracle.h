@@ -128,6 +128,8 @@ void lko_bicubic_coeffs(const uint8_t *img, int step, int ix, int iy, float a[16
 /* sample value + gradient; returns 0 ok / 1 out of image (interpolation_class.cpp:79-226) */
 int lko_interpolate(int interp, const uint8_t *img, int rows, int cols, float x, float y,
                     float *w, float *wx, float *wy);
+/* lko_interpolate at n points xy[n][2]: out4[k] = {w, wx, wy, its return value} */
+void lko_interpolate_many(int interp, const uint8_t *img, int rows, int cols, const float *xy, int n, float *out4);
 /* warp of one sample (model_class.cpp:48-202): def position and dT/dp rows */
 void lko_model_point(int model, float x, float y, float cx, float cy, const float *p,
                      float *xd, float *yd, float dTx[6], float dTy[6]);

@@ -63,6 +63,8 @@ def lib():
         L.lko_pyramid_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.lko_bicubic_coeffs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _F]
         L.lko_interpolate.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, _F, _F, _F]
+        L.lko_interpolate_many.restype = None
+        L.lko_interpolate_many.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, _F, C.c_int, _F]
         L.lko_model_point.argtypes = [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _F, _F, _F, _F, _F]
         L.lko_evaluate.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                    C.c_int, _F, C.c_int, C.c_float, C.c_float, _F, _F, _F, _F]
@@ -205,10 +207,10 @@ def interpolate(interp, img, x, y, _pad=None):
 
 
 def interpolate_many(interp, img, xy):
-    out = np.zeros((len(xy), 4), np.float32)
-    pad = _padded(img)
-    for k, (x, y) in enumerate(np.asarray(xy, np.float32)):
-        out[k] = interpolate(interp, img, float(x), float(y), pad)
+    pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    out = np.zeros((len(pts), 4), np.float32)
+    a, rows = _padded(img)
+    lib().lko_interpolate_many(interp, a.ctypes.data_as(C.c_void_p), rows, a.shape[1], _fp(pts), len(pts), _fp(out))
     return out
 
 

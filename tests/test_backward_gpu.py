@@ -1,21 +1,18 @@
 """Backward update (lk_set_update(LK_UPDATE_BACKWARD), the inverse-compositional LM solve): one evaluation against numpy
-float64 sums built from the engine's own levels, sample lists and sampler; whole solves against a numpy restatement of the
-loop in include/lk_engine.h; accuracy on a full-size speckle pair against the analytic map and the forward mode; byte
-equality of records across batches, single-sector calls, modes and sequence windows; mode rules; edges."""
+float64 sums built from the oracle's levels, decimated lists and sampler (backward_ref.py); whole solves against its numpy
+restatement of the loop in include/lk_engine.h; accuracy on a full-size speckle pair against the analytic map and the
+forward mode; byte equality of records across batches, single-sector calls, modes and sequence windows; mode rules;
+edges."""
 import numpy as np
 import pytest
 
 import correlation_amd as ca
 from correlation_amd import _ffi
 
+import backward_ref as br
+from backward_ref import P, F32, close  # noqa: F401  (the restatement lives in backward_ref.py, on the oracle alone)
+
 pytestmark = pytest.mark.gpu
-
-P = {ca.FM_U: 1, ca.FM_UV: 2, ca.FM_UVQ: 3, ca.FM_UVUXUYVXVY: 6}
-F32 = np.float32
-
-
-def round_like_host(v):
-    return np.trunc(np.asarray(v, F32) + F32(0.5)).astype(np.int64)
 
 
 def decimate(lib, pts):
@@ -25,71 +22,55 @@ def decimate(lib, pts):
     return out[:k]
 
 
-def level_points(e, s, level):
-    xy = e.level_xy(level, s)
-    if len(xy):
-        return xy
-    pts = e.getUndXY0ToCPU(s)
-    for _ in range(level):
-        pts = decimate(e.lib, pts)
-    return pts
+def sampler_of(e, interp):
+    """the `sampler` of backward_ref.Frames: None where the oracle has the sampler, the engine's lk_sample for the separable
+    bicubic extension (test_separable_bicubic_extension pins it)"""
+    if interp != ca.IM_BICUBIC_SEPARABLE:
+        return None
+    return lambda slot, level, pts: e.sample(slot, level, pts)
 
 
-def level_center(e, s, level):
-    _, cx, cy = e.sector_info(s)
-    if level == 0:
-        return F32(cx), F32(cy)
-    inv = F32(1.0) / F32(1 << level)
-    return F32(cx) * inv, F32(cy) * inv
+def rows_sorted(xy):
+    xy = np.asarray(xy, F32).reshape(-1, 2)
+    return xy[np.lexsort((xy[:, 0], xy[:, 1]))]
 
 
-def warp(model, x, y, cx, cy, p):
-    """Warp<MODEL>::apply in float32, left to right"""
-    p = np.asarray(p, F32)
-    dx, dy = x - cx, y - cy
-    if model == ca.FM_U:
-        return x + p[0], y.copy(), dx, dy
-    if model == ca.FM_UV:
-        return x + p[0], y + p[1], dx, dy
-    if model == ca.FM_UVQ:
-        return (x + p[0]) - p[2] * dy, (y + p[1]) + p[2] * dx, dx, dy
-    return ((x + p[0]) + p[2] * dx) + p[3] * dy, ((y + p[1]) + p[4] * dx) + p[5] * dy, dx, dy
+def oracle_lists(oracle, domain):
+    """the level-0 sample lists of build()'s sectors by the oracle: rect_sector_geometry and rect_points, annular_points,
+    blob_points, the registered point lists as they are"""
+    if domain == "rect":
+        xdim, ydim, cen = oracle.rect_sector_geometry(60.0, 60.0, 451.0, 451.0, 6, 6)
+        return [oracle.rect_points(cx - xdim, cy - ydim, cx + xdim, cy + ydim) for cx, cy in cen]
+    out = [oracle.annular_points(r0, dr, 0.2 + k * 1.05, 0.9, 256.0, 250.0, 6) for r0, dr in ((45.0, 30.0), (80.0, 35.0)) for k in range(6)]
+    ang = np.linspace(0, 2 * np.pi, 24, endpoint=False)
+    out += [oracle.blob_points(np.stack([c[0] + 40 * np.cos(ang), c[1] + 35 * np.sin(ang)], 1).astype(F32))
+            for c in ((100.3, 400.7), (410.2, 405.1), (400.6, 100.4))]
+    rng = np.random.default_rng(3)
+    out += [(np.array(c) + rng.uniform(-25, 25, (300, 2))).astype(F32)
+            for c in ((380.0, 120.0), (120.0, 130.0), (150.0, 60.0), (330.0, 60.0), (460.0, 250.0), (60.0, 250.0))]
+    out += [oracle.rect_points(x0, y0, x0 + 50, y0 + 42) for x0, y0 in ((330, 330), (160, 320), (250, 440))]
+    return out
 
 
-def jac(model, gx, gy, dx, dy):
-    gx, gy, dx, dy = [np.asarray(t, np.float64) for t in (gx, gy, dx, dy)]
-    if model == ca.FM_U:
-        return gx[:, None]
-    if model == ca.FM_UV:
-        return np.stack([gx, gy], 1)
-    if model == ca.FM_UVQ:
-        return np.stack([gx, gy, gx * (-dy) + gy * dx], 1)
-    return np.stack([gx, gy, gx * dx, gx * dy, gy * dx, gy * dy], 1)
-
-
-class RefSector:
-    """the template of one sector at one level, from the engine's own pieces (float64 sums)"""
-
-    def __init__(self, e, model, s, level):
-        self.e, self.model, self.level = e, model, level
-        pts = level_points(e, s, level).astype(F32)
-        self.x, self.y = pts[:, 0], pts[:, 1]
-        self.cx, self.cy = level_center(e, s, level)
-        und = e.get_pyramid_level(ca.IMG_UND, level)
-        ux = np.clip(round_like_host(self.x), 0, und.shape[1] - 1)
-        uy = np.clip(round_like_host(self.y), 0, und.shape[0] - 1)
-        self.T = und[uy, ux].astype(np.float64)
-        g = e.sample(ca.IMG_UND, level, np.stack([ux, uy], 1).astype(F32))
-        self.tbad = bool(g[:, 3].any())
-        self.G = jac(model, g[:, 1], g[:, 2], self.x - self.cx, self.y - self.cy)
-        self.H = self.G.T @ self.G
-        self.n = len(self.x)
-
-    def evaluate(self, p):
-        xd, yd, _, _ = warp(self.model, self.x, self.y, self.cx, self.cy, p)
-        w = self.e.sample(ca.IMG_DEF, self.level, np.stack([xd, yd], 1))
-        V = self.T - w[:, 0].astype(np.float64)
-        return self.G.T @ V, float(V @ V), bool(w[:, 3].any())
+def problems_of(oracle, e, pair, model, interp, domain):
+    """backward_ref's problem of every sector of build(): the level-0 lists are the oracle's (oracle_lists; the engine's own are
+    the same samples), the centres the committed ones; everything an evaluation computes - pyramids, decimated lists, level
+    centres, template and samples - is the oracle's.  The engine's own level lists and its host decimation (lk_roi_decimate)
+    are cross-checked against the oracle's here."""
+    frames = br.Frames(oracle, interp, pair[0], pair[1], sampler=sampler_of(e, interp))
+    lists = oracle_lists(oracle, domain)
+    assert len(lists) == e.n_sectors
+    out = []
+    for s in range(e.n_sectors):
+        assert np.array_equal(rows_sorted(lists[s]), rows_sorted(e.getUndXY0ToCPU(s))), s
+        pb = br.Problem(frames, model, lists[s], e.sector_info(s)[1:3])
+        for level in (1, 2):
+            assert np.array_equal(decimate(e.lib, pb.lists[level - 1]), pb.lists[level]), (s, level)
+            xy = e.level_xy(level, s)
+            if len(xy):   # (an implicit rectangle has no list on the device)
+                assert np.array_equal(rows_sorted(xy), rows_sorted(pb.lists[level])), (s, level)
+        out.append(pb)
+    return out
 
 
 def pair512():
@@ -123,25 +104,21 @@ def build(pair, model=ca.FM_UVUXUYVXVY, interp=ca.IM_BICUBIC, domain="rect", **c
     return e
 
 
-def close(got, want, rtol=2e-5, atol=1e-3):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    return np.abs(got - want).max() <= rtol * max(np.abs(want).max(), 1.0) + atol
-
-
 @pytest.mark.parametrize("domain", ["rect", "mixed"])
 @pytest.mark.parametrize("model,interp", [(ca.FM_UVUXUYVXVY, ca.IM_BICUBIC), (ca.FM_UVQ, ca.IM_BICUBIC_SEPARABLE),
                                           (ca.FM_UV, ca.IM_BILINEAR), (ca.FM_U, ca.IM_NEAREST),
                                           (ca.FM_UVUXUYVXVY, ca.IM_BILINEAR)])
-def test_one_evaluation_against_numpy(domain, model, interp):
+def test_one_evaluation_against_numpy(oracle, domain, model, interp):
     pair = pair512()
     e = build(pair, model, interp, domain)
+    problems = problems_of(oracle, e, pair, model, interp, domain)
     n = P[model]
     p = np.array([1.1, -0.6, 0.0015, 0.0008, -0.0007, -0.0012], F32)[:n]
     if model == ca.FM_UVQ:
         p[2] = 0.001
     for s in range(e.n_sectors):
         for level in (0, 1, 2):
-            ref = RefSector(e, model, s, level)
+            ref = problems[s].sector(level)
             scale = F32(1.0 / (1 << level))
             pl = p.copy()
             pl[:min(n, 2)] *= scale
@@ -160,102 +137,19 @@ def test_one_evaluation_against_numpy(domain, model, interp):
     e.close()
 
 
-def solve_ref(e, model, s, guess, precision=1e-3, max_iters=50, py=(0, 1, 2)):
-    """numpy restatement of the backward loop of include/lk_engine.h (float64 sums and solve, the engine's sampler, the
-    host copy of the kernel's composition)"""
-    n = P[model]
-    py_start, py_step, py_stop = py
-    p = np.zeros(6, F32)
-    p[:n] = guess[:n]
-    reached, error, lg_chi, level_old = 0, 0, F32(np.finfo(F32).max), 0
-    min_l, max_l = F32(1e-9), F32(1e9)
-
-    def translate(p, src, dst):
-        mag = F32(1.0) / F32(1 << (dst - src)) if dst - src > 0 else F32(1 << (src - dst))
-        p[:min(n, 2)] = (p[:min(n, 2)] * mag).astype(F32)
-
-    def step(ref, b, lam, p_from):
-        A = ref.H / ref.n
-        A[np.diag_indices(n)] *= (1.0 + float(lam))
-        delta = np.linalg.solve(A, b / ref.n).astype(F32)
-        return ca.compose_inverse(model, p_from[:n], -delta)
-
-    early = False
-    for level in range(py_stop, py_start - 1, -py_step):
-        translate(p, level_old, level)
-        error, lam, lg_chi = 0, F32(1e-4), F32(np.finfo(F32).max)
-        ref = RefSector(e, model, s, level)
-        if ref.tbad:
-            error, early = ca.ERROR_INTERPOLATION_OUT_OF_IMAGE, True
-            translate(p, level, 0)
-            break
-        lg_p = p.copy()
-        first, use_saved, saved, it, kb = True, True, None, 0, None
-        while True:
-            ok, tent = True, None
-            if first:
-                tent = p.copy()
-            else:
-                it += 1
-                if it > max_iters or lam >= max_l:
-                    error = ca.ERROR_CORRELATION_MAX_ITERS_REACHED
-                    break
-                reached = it
-                if use_saved:
-                    tent, ok = saved, saved is not None
-                else:
-                    p = lg_p.copy()
-                    tent = step(ref, kb, lam, lg_p)
-                    ok = tent is not None
-            chi = F32(np.inf)
-            if ok:
-                p = tent.copy()
-                b, chi64, bad = ref.evaluate(tent)
-                if bad:
-                    error, early = ca.ERROR_INTERPOLATION_OUT_OF_IMAGE, first
-                    break
-                chi = F32(chi64) * F32(1.0 / ref.n)
-                la = lam
-                if not first:
-                    la = lam * F32(0.4)
-                    la = la if la > min_l else min_l
-                saved = step(ref, b, la, tent)
-                if saved is not None:
-                    p = saved.copy()
-            if first:
-                lg_chi, kb, first = chi, b, False
-                continue
-            mx = chi if lg_chi < chi else lg_chi
-            with np.errstate(invalid="ignore"):
-                delta_chi = abs((lg_chi - chi) / (mx + F32(precision)))
-            if chi <= lg_chi:
-                lg_chi, lg_p, kb, use_saved = chi, tent.copy(), b, True
-                lam = max(lam * F32(0.4), min_l)
-            else:
-                lam, use_saved = min(lam * F32(10.0), max_l), False
-            if delta_chi < precision:
-                break
-        if early:
-            translate(p, level, 0)
-            break
-        level_old = level
-    if not early:
-        translate(p, level_old, 0)
-    return p, lg_chi, reached, error
-
-
 @pytest.mark.parametrize("domain", ["rect", "mixed"])
 @pytest.mark.parametrize("model", [ca.FM_UVUXUYVXVY, ca.FM_UV, ca.FM_UVQ])
-def test_whole_solves_against_restatement(domain, model):
+def test_whole_solves_against_restatement(oracle, domain, model):
     pair = pair512()
     e = build(pair, model, ca.IM_BICUBIC, domain)
+    problems = problems_of(oracle, e, pair, model, ca.IM_BICUBIC, domain)
     e.set_update(ca.UPDATE_BACKWARD)
     S = e.n_sectors
     got = e.correlate_all(np.zeros(6, F32))
     n = P[model]
     it_diff, chi_loose = 0, 0
     for s in range(S):
-        p, chi, it, err = solve_ref(e, model, s, np.zeros(6, F32))
+        p, chi, it, err = br.solve_ref(problems[s], np.zeros(6, F32))
         r = got[s]
         assert r["error_code"] == err, (s, r, err)
         it_diff += int(r["iterations"] != it)

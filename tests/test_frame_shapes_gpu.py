@@ -10,6 +10,7 @@ import pytest
 
 import correlation_amd as ca
 
+import backward_ref as BACKWARD   # solve_ref, close: the backward restatement on the oracle alone
 import frame_shapes_ref as fs
 
 pytestmark = pytest.mark.gpu
@@ -418,7 +419,6 @@ def test_window_records_on_non_square_frames(oracle, orientation, mode):
 
 
 # ---- 6. the backward update -------------------------------------------------------------------------------------------------
-BACKWARD = fs.module("test_backward_gpu")         # solve_ref, close
 
 
 @pytest.mark.parametrize("model", [ca.FM_UVUXUYVXVY, ca.FM_UV], ids=["affine", "uv"])
@@ -434,11 +434,13 @@ def test_backward_solves_on_the_unequal_pair(oracle, orientation, model):
     e.set_update(ca.UPDATE_BACKWARD)
     got = e.correlate_all(ZERO)
     n = BACKWARD.P[model]
+    frames = BACKWARD.Frames(oracle, ca.IM_BICUBIC, *fs.pair(orientation, "unequal"))
     assert np.array_equal(got["error_code"] == fs.OUT_OF_IMAGE, g.edge) and np.array_equal(got["error_code"] == 0, ~g.edge)
     assert np.array_equal(got["error_code"], want["error_code"])      # (the forward oracle's codes: the same sectors leave)
     it_diff = 0
     for s in range(len(g)):
-        p, chi, it, err = BACKWARD.solve_ref(e, model, s, ZERO)
+        assert tuple(e.sector_info(s)[1:3]) == tuple(g.rect_centers[s])
+        p, chi, it, err = BACKWARD.solve_ref(BACKWARD.Problem(frames, model, g.lists[s], g.rect_centers[s]), ZERO)
         r = got[s]
         assert r["error_code"] == err, (s, r, err)
         it_diff += int(r["iterations"] != it)

@@ -73,7 +73,7 @@ def sampler_of(e, interp, level):
     return lambda pts: e.sample(ca.IMG_DEF, level, pts) if len(pts) else np.zeros((0, 4), np.float32)
 
 
-def check_photometry(oracle, e, model, interp, rec, out, sums, level, rects, chi_max=0.0):
+def check_photometry(oracle, e, model, interp, rec, out, sums, level, rects, chi_max=0.0, ratios=None):
     """every sector of the engine: status, the six sums within the bound, the flagged count, max |V| exactly, the record byte
     for byte the host function of the device's sums and within the restatement's tolerance -> worst sum error / bound"""
     P = _ffi.N_PARAMS[model]
@@ -81,7 +81,8 @@ def check_photometry(oracle, e, model, interp, rec, out, sums, level, rects, chi
     good = rr.good_records(rec, model, chi_max)
     worst = 0.0
     for s in range(e.n_sectors):
-        xy = ur.rect_rows(*ur.rect_level(rects[s], level)) if s < len(rects) else e.level_xy(level, s)
+        is_rect = s < len(rects) and rects[s] is not None     # (None in rects: a list sector among the rectangles)
+        xy = ur.rect_rows(*ur.rect_level(rects[s], level)) if is_rect else e.level_xy(level, s)
         n = len(xy)
         assert out["n_points"][s] == n and not out["reserved"][s].any()
         want = None
@@ -109,6 +110,8 @@ def check_photometry(oracle, e, model, interp, rec, out, sums, level, rects, chi
         assert (err <= bound).all(), (s, err, bound)
         assert sums[s][6] == 0.0 and sums[s][7] == float(np.abs(V).max()), (s, sums[s][6:], np.abs(V).max())
         worst = max(worst, ratio)
+        if ratios is not None:
+            ratios.append((s, ratio))
         assert ca.photometry_from_sums(n, sums[s]).tobytes() == out[s].tobytes(), s
         rr.check_record(out[s], f, g, V, sums[s], (model, interp, s))
     return worst

@@ -59,7 +59,7 @@ def good_record(rec, P):
     return rec["error_code"] == 0 and np.isfinite(rec["chi"]) and np.isfinite(rec["p"][:P]).all()
 
 
-def check_against_oracle(oracle, e, model, interp, rec, out, sums, level, rects, n_annular):
+def check_against_oracle(oracle, e, model, interp, rec, out, sums, level, rects, n_annular, cond_max=1e4, ratios=None):
     """every sector of the engine: status, sums within the bound, the record byte for byte the host function of the device's
     sums and within the restatement's tolerance -> (worst sum error / bound, statuses)"""
     P = _ffi.N_PARAMS[model]
@@ -70,7 +70,8 @@ def check_against_oracle(oracle, e, model, interp, rec, out, sums, level, rects,
             return e.sample(ca.IMG_DEF, level, pts)
     worst = 0.0
     for s in range(e.n_sectors):
-        xy = ur.rect_rows(*ur.rect_level(rects[s], level)) if s < len(rects) else e.level_xy(level, s)
+        is_rect = s < len(rects) and rects[s] is not None     # (None in rects: a list sector among the rectangles)
+        xy = ur.rect_rows(*ur.rect_level(rects[s], level)) if is_rect else e.level_xy(level, s)
         n = len(xy)
         assert out["n_points"][s] == n and out["reserved"][s] == 0
         if not good_record(rec[s], P):
@@ -92,8 +93,10 @@ def check_against_oracle(oracle, e, model, interp, rec, out, sums, level, rects,
         print(f"model {model} interp {interp} level {level} sector {s} (n = {n}): worst sum error / bound {ratio:.3g}")
         assert (err <= bound).all(), (s, err, bound)
         worst = max(worst, ratio)
+        if ratios is not None:
+            ratios.append((s, ratio))
         assert ca.uncertainty_from_sums(model, n, sums[s], level).tobytes() == out[s].tobytes(), s
-        ur.check_record(out[s], model, n, sums[s], level, (model, interp, s))
+        ur.check_record(out[s], model, n, sums[s], level, (model, interp, s), cond_max.get(s, 1e4) if isinstance(cond_max, dict) else cond_max)
     return worst
 
 

@@ -67,11 +67,66 @@ def errors_against_the_map(rec, centres):
 CASES = [(m, ca.IM_BICUBIC) for m in MODELS] + [(ca.FM_UVUXUYVXVY, ca.IM_BILINEAR), (ca.FM_UVUXUYVXVY, ca.IM_BICUBIC_SEPARABLE)]
 
 
-@pytest.mark.parametrize("model,interp", CASES)
-def test_sums_and_info_of_the_seed_evaluation(oracle, pair, model, interp):
-    und, dfm = pair
+def check_seed_evaluation(oracle, e, und, dfm, model, interp, lists, centres, g, sampler=None, ratios=None, refine=None, allow_refused=False):
+    """refine_znssd with max_iters = 0 from the seeds g: per sector the sums against the oracle's per-sample floats within
+    64 n 2^-53 sum|terms|, the info the host function of the device's sums bit for bit, the record; the same call again gives
+    the same bytes -> (worst sum error / bound, the records).  refine: the pass (default e.refine_znssd; lk_refine_spline has the
+    same contract under its own sampler).  allow_refused: a sector may be one the criterion refuses or whose step is singular (a
+    starved sector of test_pass_instances_gpu.py); without it every sector must evaluate and step, as ever."""
     P = _ffi.N_PARAMS[model]
     used = zr.layout(P)[4]
+    n0 = [e.sector_info(s)[0] for s in range(e.n_sectors)]
+    refine = refine or e.refine_znssd
+    rec, info, sums = refine(guesses=g, max_iters=0, return_sums=True)
+    worst = 0.0
+    for s in range(e.n_sectors):
+        xy, (cx, cy) = lists[s], centres[s]
+        n = len(xy)
+        f, gg, H, bad = zr.sample_floats(oracle, interp, model, und, dfm, xy, cx, cy, g[s], sampler)
+        assert not bad.any()
+        terms = zr.sum_terms(f, gg, H)
+        bound = 64.0 * n * 2.0 ** -53 * np.abs(terms).sum(axis=0)
+        err = np.abs(sums[s][:used] - terms.sum(axis=0))
+        ratio = float((err[bound > 0] / bound[bound > 0]).max())
+        assert (err <= bound).all(), (s, err, bound)
+        assert not sums[s][used:].any(), (s, sums[s][used:])
+        worst = max(worst, ratio)
+        if ratios is not None:
+            ratios.append((s, ratio))
+        # the info is the host function of the device's sums, bit for bit
+        status, delta, crit, gain, offset = ca.znssd_step_from_sums(model, n, sums[s], zr.LAMBDA0)
+        refused, _, _, _, zncc = zr.criterion(model, n, sums[s])
+        i = info[s]
+        if allow_refused:   # (the step's status is the restatement's: a starved sector's matrix may be singular)
+            assert status == zr.step(model, n, sums[s], zr.LAMBDA0)[0] and (status == 0 or n < 16), (s, status)
+            assert i["status"] == (refused if refused else ca.ZN_MAX_ITERS) and i["n_points"] == n, (s, status, i)
+        else:
+            assert status == 0 and not refused and i["status"] == ca.ZN_MAX_ITERS and i["n_points"] == n, (s, status, i)
+        assert (i["iterations"], i["evaluations"]) == (0, 1) and i["shift"] == 0 and i["last_step"] == 0 and not i["reserved"].any()
+        if not refused:
+            for name, want in (("gain", gain), ("offset", offset), ("znssd", crit), ("zncc", zncc), ("zncc_seed", zncc)):
+                assert i[name].tobytes() == np.float32(want).tobytes(), (s, name, i[name], want)
+            assert i["lambda"] == np.float32(zr.LAMBDA0)
+        # the record: the seed, the forward evaluation's chi, the committed centre and the level-0 count
+        r = rec[s]
+        assert r["p"][:P].tobytes() == g[s][:P].tobytes() and not r["p"][P:].any(), (s, r)
+        V = (f - gg).astype(np.float64)
+        assert abs(float(r["chi"]) - (V * V).mean()) <= 1e-6 * (V * V).mean(), (s, r["chi"], (V * V).mean())
+        if not refused:
+            assert r["error_code"] == ca.ERROR_CORRELATION_MAX_ITERS_REACHED and r["iterations"] == 0
+        assert r["n_points"] == n0[s] and (r["und_cx"], r["und_cy"]) == (np.float32(cx), np.float32(cy)), (s, r)
+    print(f"model {model} interp {interp}: worst sum error / bound {worst:.3g}")
+    # the same call again: the same bytes
+    again = refine(guesses=g, max_iters=0, return_sums=True)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(again, (rec, info, sums)))
+    return worst, rec
+
+
+@pytest.mark.parametrize("model,interp", CASES)
+def test_sums_and_info_of_the_seed_evaluation(oracle, pair, model, interp):
+    """(all sixteen (model, interpolator) pairs run on the geometry of test_pass_instances_gpu.py; this one keeps the grid
+    sectors and the 24 x 24 wavefront sector)"""
+    und, dfm = pair
     # a quarter of the grid, and the three sectors of the other kinds
     rects = zr.GRID[::4] + zr.RECTS[len(zr.GRID):]
     with make_engine(und, dfm, rects, model=model, interp=interp) as e:
@@ -79,44 +134,10 @@ def test_sums_and_info_of_the_seed_evaluation(oracle, pair, model, interp):
         assert n0[:len(rects)] == [361] * 16 + [576, 9216] and 0 < n0[-1] <= 512 and n0[-1] % 16
         lists, centres = geometry(e, rects)
         sampler = (lambda pts: e.sample(ca.IMG_DEF, 0, pts)) if interp == ca.IM_BICUBIC_SEPARABLE else None
-        g = near_guesses(e.n_sectors)
-        rec, info, sums = e.refine_znssd(guesses=g, max_iters=0, return_sums=True)
-        worst = 0.0
-        for s in range(e.n_sectors):
-            xy, (cx, cy) = lists[s], centres[s]
-            n = len(xy)
-            f, gg, H, bad = zr.sample_floats(oracle, interp, model, und, dfm, xy, cx, cy, NEAR, sampler)
-            assert not bad.any()
-            terms = zr.sum_terms(f, gg, H)
-            bound = 64.0 * n * 2.0 ** -53 * np.abs(terms).sum(axis=0)
-            err = np.abs(sums[s][:used] - terms.sum(axis=0))
-            ratio = float((err[bound > 0] / bound[bound > 0]).max())
-            assert (err <= bound).all(), (s, err, bound)
-            assert not sums[s][used:].any(), (s, sums[s][used:])
-            worst = max(worst, ratio)
-            # the info is the host function of the device's sums, bit for bit
-            status, delta, crit, gain, offset = ca.znssd_step_from_sums(model, n, sums[s], zr.LAMBDA0)
-            zncc = zr.criterion(model, n, sums[s])[4]
-            i = info[s]
-            assert status == 0 and i["status"] == ca.ZN_MAX_ITERS and i["n_points"] == n, (s, status, i)
-            assert (i["iterations"], i["evaluations"]) == (0, 1) and i["shift"] == 0 and i["last_step"] == 0 and not i["reserved"].any()
-            for name, want in (("gain", gain), ("offset", offset), ("znssd", crit), ("zncc", zncc), ("zncc_seed", zncc)):
-                assert i[name].tobytes() == np.float32(want).tobytes(), (s, name, i[name], want)
-            assert i["lambda"] == np.float32(zr.LAMBDA0)
-            # the record: the seed, the forward evaluation's chi, the committed centre and the level-0 count
-            r = rec[s]
-            assert r["p"][:P].tobytes() == NEAR[:P].tobytes() and not r["p"][P:].any(), (s, r)
-            V = (f - gg).astype(np.float64)
-            assert abs(float(r["chi"]) - (V * V).mean()) <= 1e-6 * (V * V).mean(), (s, r["chi"], (V * V).mean())
-            assert r["error_code"] == ca.ERROR_CORRELATION_MAX_ITERS_REACHED and r["iterations"] == 0
-            assert r["n_points"] == n0[s] and (r["und_cx"], r["und_cy"]) == (np.float32(cx), np.float32(cy)), (s, r)
-        print(f"model {model} interp {interp}: worst sum error / bound {worst:.3g}")
+        _, rec = check_seed_evaluation(oracle, e, und, dfm, model, interp, lists, centres, near_guesses(e.n_sectors), sampler)
         # the forward evaluation's chi (lk_evaluate, scaled by 1 / n as the solve scales it) at the same parameters
         chi = e.evaluate(0, 0, NEAR)[2] / n0[0]
         assert abs(float(rec["chi"][0]) - chi) <= n0[0] * 2.0 ** -23 * chi, (rec["chi"][0], chi)   # (its float summation)
-        # the same call again: the same bytes
-        again = e.refine_znssd(guesses=g, max_iters=0, return_sums=True)
-        assert all(a.tobytes() == b.tobytes() for a, b in zip(again, (rec, info, sums)))
 
 
 # ---- 2, 3. fixed point and accuracy on the clean pair ---------------------------------------------------------------------------
@@ -128,6 +149,35 @@ def clean_run(pair):
     return dict(rec=rec, info=info, sums=sums, lists=lists, centres=centres)
 
 
+def check_fixed_point(oracle, und, dfm, model, interp, lists, centres, rec, info, sums, sampler=None):
+    """every ZN_CONVERGED sector: the restatement evaluated at the returned parameters gives a step below 4 x precision at the
+    returned lambda, and the kept sums are those of the returned parameters; every sector with sums: the info is the host
+    function of them, bit for bit -> the largest weighted step"""
+    used = zr.layout(_ffi.N_PARAMS[model])[4]
+    worst = 0.0
+    for s in range(len(lists)):
+        xy, (cx, cy) = lists[s], centres[s]
+        n = len(xy)
+        if sums[s].any() and info["evaluations"][s] > 0 and info["status"][s] not in (ca.ZN_TOO_FEW, ca.ZN_FLAT, ca.ZN_OUT_OF_IMAGE, ca.ZN_NEGATIVE,
+                                                                                           ca.ZN_BAD_SEED):
+            _, _, crit, gain, offset = ca.znssd_step_from_sums(model, n, sums[s], float(info["lambda"][s]))
+            zncc = zr.criterion(model, n, sums[s])[4]
+            for name, want in (("gain", gain), ("offset", offset), ("znssd", crit), ("zncc", zncc)):
+                assert info[name][s].tobytes() == np.float32(want).tobytes(), (s, name, info[name][s], want)
+        if info["status"][s] != ca.ZN_CONVERGED:
+            continue
+        f, g, H, bad = zr.sample_floats(oracle, interp, model, und, dfm, xy, cx, cy, rec["p"][s], sampler)
+        ref = zr.sums_of(f, g, H, bad)
+        st, delta = zr.step(model, n, ref, float(info["lambda"][s]))[:2]
+        w = zr.weighted_step(model, n, delta)
+        worst = max(worst, w)
+        assert st == 0 and w < 4.0 * zr.PRECISION, (s, st, w, info[s])
+        # the kept sums are those of the returned parameters
+        bound = 64.0 * n * 2.0 ** -53 * np.abs(zr.sum_terms(f, g, H)).sum(axis=0)
+        assert (np.abs(sums[s][:used] - ref[:used]) <= bound).all() and sums[s][used] == 0, s
+    return worst
+
+
 def test_fixed_point_of_the_converged_sectors(oracle, pair, clean_run):
     """the restatement evaluated at the returned parameters gives a step below 4 x precision at the returned lambda"""
     und, dfm = pair
@@ -137,19 +187,8 @@ def test_fixed_point_of_the_converged_sectors(oracle, pair, clean_run):
     assert not np.isin(info["status"], (ca.ZN_MAX_ITERS, ca.ZN_STALLED)).any(), info["status"]
     assert (info["status"] == ca.ZN_CONVERGED).all(), info["status"]
     assert (rec["error_code"] == 0).all() and (rec["iterations"] == info["iterations"]).all()
-    worst = 0.0
-    model = ca.FM_UVUXUYVXVY
-    for s in range(S):
-        xy, (cx, cy) = clean_run["lists"][s], clean_run["centres"][s]
-        f, g, H, bad = zr.sample_floats(oracle, ca.IM_BICUBIC, model, und, dfm, xy, cx, cy, rec["p"][s])
-        sums = zr.sums_of(f, g, H, bad)
-        st, delta = zr.step(model, len(xy), sums, float(info["lambda"][s]))[:2]
-        w = zr.weighted_step(model, len(xy), delta)
-        worst = max(worst, w)
-        assert st == 0 and w < 4.0 * zr.PRECISION, (s, st, w, info[s])
-        # the kept sums are those of the returned parameters
-        bound = 64.0 * len(xy) * 2.0 ** -53 * np.abs(zr.sum_terms(f, g, H)).sum(axis=0)
-        assert (np.abs(clean_run["sums"][s][:44] - sums[:44]) <= bound).all() and clean_run["sums"][s][44] == 0, s
+    worst = check_fixed_point(oracle, und, dfm, ca.FM_UVUXUYVXVY, ca.IM_BICUBIC, clean_run["lists"], clean_run["centres"], rec, info,
+                              clean_run["sums"])
     print(f"largest weighted step of the restatement at the returned state: {worst:.3g} (allowed {4.0 * zr.PRECISION:.3g})")
 
 
