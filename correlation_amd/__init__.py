@@ -33,6 +33,10 @@ from ._ffi import (LENS_AFFINE, LENS_CORRECTED, LENS_DEGENERATE, LENS_DTYPE, LEN
                    LENS_NOT_GOOD, LENS_OK, LENS_OUTSIDE, LENS_PARAMS, LENS_Q, LENS_RESULT_DTYPE, LENS_SIMILARITY, LENS_STEP_DTYPE,
                    LENS_TRANSLATION, lens_correct_records, lens_distort, lens_step_from_sums, lens_sums_len, lens_undistort,
                    make_lens)
+from ._ffi import (CAMERA_DTYPE, STEREO_BAD_RECORD, STEREO_BEHIND, STEREO_OK, STEREO_OUTSIDE_LENS, STEREO_PARALLEL,  # noqa: F401
+                   STEREO_POINT_DTYPE, STEREO_SUMS, STEREO_SURFACE_DEGENERATE, STEREO_SURFACE_DTYPE, STEREO_SURFACE_FILLED,
+                   STEREO_SURFACE_FLOATS, STEREO_SURFACE_OK, STEREO_SURFACE_TOO_FEW, make_camera, stereo_fundamental, stereo_project,
+                   stereo_surface_from_sums, stereo_triangulate)
 from ._ffi import (MAP_NO_OWNER, PHOTO_BAD_RECORD, PHOTO_FLAT, PHOTO_OK, PHOTO_OUT_OF_IMAGE, PHOTO_SUMS,  # noqa: F401
                    PHOTO_TOO_FEW, PHOTOMETRY_DTYPE, map_owner, photometry_from_sums)
 from ._ffi import (ZN_BAD_SEED, ZN_CONVERGED, ZN_FLAT, ZN_MAX_ITERS, ZN_NEGATIVE, ZN_OUT_OF_IMAGE, ZN_SINGULAR,  # noqa: F401

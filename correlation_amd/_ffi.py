@@ -227,6 +227,28 @@ LENS_STEP_DTYPE = np.dtype([("delta", np.float64, 6), ("sigma", np.float64, 6), 
 assert LENS_DTYPE.itemsize == 64 and LENS_RESULT_DTYPE.itemsize == 160 and LENS_FRAME_DTYPE.itemsize == 64
 assert LENS_STEP_DTYPE.itemsize == 136 and C.sizeof(LkLensConfig) == 16 and C.sizeof(LkLensFitConfig) == 40
 
+# a two-camera rig (include/lk_engine.h: lk_stereo_points, lk_stereo_strain)
+STEREO_OK, STEREO_BAD_RECORD, STEREO_OUTSIDE_LENS, STEREO_PARALLEL, STEREO_BEHIND = range(5)
+STEREO_SURFACE_OK, STEREO_SURFACE_FILLED, STEREO_SURFACE_TOO_FEW, STEREO_SURFACE_DEGENERATE = range(4)
+STEREO_SUMS = 23   # Sx, Sy, Sxx, Sxy, Syy, then Sf, Sxf, Syf of X, Y, Z, U, V, W
+
+
+class LkStereoConfig(C.Structure):
+    _fields_ = [("radius", C.c_float), ("chi_max", C.c_float), ("min_neighbours", C.c_int), ("reserved", C.c_int)]
+
+
+# lk_camera, lk_stereo_point and lk_stereo_surface as numpy records
+CAMERA_DTYPE = np.dtype([(k, np.float64) for k in ("fx", "fy", "cx", "cy", "skew")] +
+                        [("R", np.float64, (3, 3)), ("t", np.float64, 3), ("lens", LENS_DTYPE), ("reserved", np.float64, 7)])
+STEREO_POINT_DTYPE = np.dtype([("X", np.float64), ("Y", np.float64), ("Z", np.float64), ("residual", np.float32, 4),
+                               ("epipolar", np.float32), ("angle", np.float32), ("status", np.int32), ("reserved", np.int32, 3)])
+STEREO_SURFACE_FLOATS = ("X", "Y", "Z", "U", "V", "W", "nx", "ny", "nz", "exx", "eyy", "exy", "e1", "e2", "theta", "biot1", "biot2",
+                         "normal", "residual")
+STEREO_SURFACE_DTYPE = np.dtype([(k, np.float32) for k in STEREO_SURFACE_FLOATS] +
+                                [("neighbours", np.int32), ("status", np.int32), ("reserved", np.int32, 11)])
+assert CAMERA_DTYPE.itemsize == 256 and STEREO_POINT_DTYPE.itemsize == 64 and STEREO_SURFACE_DTYPE.itemsize == 128
+assert C.sizeof(LkStereoConfig) == 16
+
 # photometry and the residual map (include/lk_engine.h: lk_photometry, lk_residual_map)
 PHOTO_OK, PHOTO_BAD_RECORD, PHOTO_OUT_OF_IMAGE, PHOTO_TOO_FEW, PHOTO_FLAT = range(5)
 PHOTO_SUMS = 8   # doubles per sector: sum f, sum g, sum f^2, sum g^2, sum f g, sum V^2, flagged samples, max |V|
@@ -481,6 +503,12 @@ SYMBOLS = {
     "lk_lens_step_from_sums": (C.c_int, [C.c_int, C.c_uint, C.c_double, C.c_int, C.c_int, _P, _P, _P]),
     "lk_lens_correct": (C.c_int, [_P, C.POINTER(LkLensConfig), _P, C.c_int, _P, _P, _P, _P]),
     "lk_lens_fit": (C.c_int, [_P, C.POINTER(LkLensFitConfig), _P, C.c_int, _P, _P, _P, _P, _P]),
+    "lk_stereo_project": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "lk_stereo_fundamental": (C.c_int, [_P, _P]),
+    "lk_stereo_triangulate": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "lk_stereo_surface_from_sums": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_double, _P, _P]),
+    "lk_stereo_points": (C.c_int, [_P, C.POINTER(LkStereoConfig), _P, _P, C.c_int, _P, _P, _P, _P]),
+    "lk_stereo_strain": (C.c_int, [_P, C.POINTER(LkStereoConfig), C.c_int, _P, _P, _P]),
     "lk_photometry": (C.c_int, [_P, C.POINTER(LkPhotometryConfig), _P, _P, _P]),
     "lk_photometry_from_sums": (C.c_int, [C.c_int, _P, _P]),
     "lk_residual_map": (C.c_int, [_P, C.POINTER(LkResidualMapConfig), _P, _P, _P, _P]),
@@ -1015,3 +1043,76 @@ def lens_step_from_sums(nuisance, free, rn, sums, min_sectors=None):
                                            out.ctypes.data_as(_P), dn.ctypes.data_as(_P)) != 0:
         raise ValueError("lk_lens_step_from_sums: an unknown nuisance, an empty or unknown free, rn <= 0 or min_sectors < Q")
     return out[0], dn
+
+
+def make_camera(fx, fy, cx, cy, R=None, t=(0.0, 0.0, 0.0), skew=0.0, lens=None):
+    """one CAMERA_DTYPE record: x_cam = R X + t, then the pinhole, then `lens` (a LENS_DTYPE record in pixels; None: no lens)"""
+    cam = np.zeros(1, CAMERA_DTYPE)
+    cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["skew"] = fx, fy, cx, cy, skew
+    cam["R"][0] = np.eye(3) if R is None else np.asarray(R, np.float64).reshape(3, 3)
+    cam["t"][0] = np.asarray(t, np.float64).reshape(3)
+    if lens is not None:
+        cam["lens"][0] = np.ascontiguousarray(lens, LENS_DTYPE).reshape(1)[0]
+    return cam[0]
+
+
+def _rig(cams):
+    """cams: two CAMERA_DTYPE records -> a contiguous [2] array"""
+    rig = np.zeros(2, CAMERA_DTYPE)
+    rig[0], rig[1] = cams[0], cams[1]
+    return rig
+
+
+def stereo_project(cam, xyz, return_status=False):
+    """lk_stereo_project (host, the kernel's camera): world points xyz [n][3] -> pixels float64 [n][2] as the camera shows them;
+    with return_status also uint8 [n]: 0, or 1 for a point that is not in front of the camera (pixel 0, 0)."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    one = np.ascontiguousarray(cam, CAMERA_DTYPE).reshape(1)
+    p = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    out, status = np.zeros((len(p), 2)), np.zeros(len(p), np.uint8)
+    if _compose_lib.lk_stereo_project(one.ctypes.data_as(_P), len(p), p.ctypes.data_as(_P), out.ctypes.data_as(_P),
+                                      status.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_stereo_project: no points, or a camera that is refused")
+    return (out, status) if return_status else out
+
+
+def stereo_fundamental(cams):
+    """lk_stereo_fundamental (host): F float64 [3][3] of the rig, (m1, 1)^T F (m0, 1) = 0 for undistorted pixels of one point."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    rig, F = _rig(cams), np.zeros((3, 3))
+    if _compose_lib.lk_stereo_fundamental(rig.ctypes.data_as(_P), F.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_stereo_fundamental: a camera that is refused")
+    return F
+
+
+def stereo_triangulate(cams, x0, x1):
+    """lk_stereo_triangulate (host, the kernel's function): pixels x0 [n][2] of camera 0 and x1 [n][2] of camera 1 ->
+    STEREO_POINT_DTYPE [n]."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    rig = _rig(cams)
+    a, b = np.ascontiguousarray(x0, np.float64).reshape(-1, 2), np.ascontiguousarray(x1, np.float64).reshape(-1, 2)
+    out = np.zeros(len(a), STEREO_POINT_DTYPE)
+    if len(a) != len(b) or _compose_lib.lk_stereo_triangulate(rig.ctypes.data_as(_P), len(a), a.ctypes.data_as(_P), b.ctypes.data_as(_P),
+                                                              out.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_stereo_triangulate: no pairs, x0 and x1 of different lengths, or a camera that is refused")
+    return out
+
+
+def stereo_surface_from_sums(n, sums23, min_neighbours=3, self_good=True, residual_sum=0.0, return_planes=False):
+    """lk_stereo_surface_from_sums (host, the kernel's function): the STEREO_SURFACE_DTYPE record of a window of n members
+    with the STEREO_SUMS sums; with return_planes also float64 [6][3] = {f0, fx, fy} of the planes of X, Y, Z, U, V, W."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    s = np.ascontiguousarray(sums23, np.float64).reshape(STEREO_SUMS)
+    out, planes = np.zeros(1, STEREO_SURFACE_DTYPE), np.zeros((6, 3))
+    if _compose_lib.lk_stereo_surface_from_sums(int(n), s.ctypes.data_as(_P), int(min_neighbours), int(bool(self_good)), float(residual_sum),
+                                                out.ctypes.data_as(_P), planes.ctypes.data_as(_P)) != 0:
+        raise ValueError("lk_stereo_surface_from_sums: n < 0 or min_neighbours < 3")
+    return (out[0], planes) if return_planes else out[0]

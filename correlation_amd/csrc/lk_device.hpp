@@ -372,6 +372,31 @@ struct LkLensCorrectArgs {
   int n_frames, n_sectors, model;
 };
 
+// A two-camera rig (lk_stereo.hip, include/lk_engine.h: lk_stereo_points, lk_stereo_strain).
+struct LkStereoRig {       // what a kernel reads of a rig: the two cameras and F, formed once on the host
+  lk_camera cam[2];
+  double F[9];
+};
+struct LkStereoPointsArgs { // a thread per (frame, sector), the reference state as the first frame of `out`
+  LkStereoRig rig;
+  const float2 *center;    // [S]
+  const lk_result *ref1;   // [S]
+  const lk_result *rec0;   // [F][S] (null with n_frames = 0, as rec1)
+  const lk_result *rec1;   // [F][S]
+  lk_stereo_point *out;    // [1 + F][S]: the reference state, then the frames
+  int n_frames, n_sectors, model;
+  float chi_max;
+};
+struct LkStereoStrainArgs { // a lane group per (frame, sector) on the recovery pass's cell grid
+  LkReseedGrid grid;
+  const float2 *center;         // [S]
+  const lk_stereo_point *ref;   // [S]
+  const lk_stereo_point *pts;   // [F][S]
+  lk_stereo_surface *out;       // [F][S]
+  int n_frames, n_sectors, min_neighbours;
+  double radius;
+};
+
 // Outlier flags (lk_outlier.hip, include/lk_engine.h: lk_flag_outliers): one pass of the (detrended) normalised median test.
 struct LkOutlierArgs {
   LkReseedGrid grid;

@@ -91,11 +91,11 @@ struct LkPassSlot {
   virtual ~LkPassSlot() = default;
 };
 enum LkPass { LK_PASS_RESEED, LK_PASS_STRAIN, LK_PASS_UNCERTAINTY, LK_PASS_OUTLIER, LK_PASS_TRACK, LK_PASS_RESIDUAL, LK_PASS_PATTERN,
-              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_ROTATED, LK_PASS_MOTION, LK_PASS_NOISE, LK_PASS_LENS, LK_PASS_COUNT };
+              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_ROTATED, LK_PASS_MOTION, LK_PASS_NOISE, LK_PASS_LENS, LK_PASS_STEREO, LK_PASS_COUNT };
 LkPassSlot **lk_internal_pass_slot(lk_engine *e, int which);
 
 // What a post-processing pass reads of the engine (lk_strain_field, lk_parameter_uncertainty, lk_flag_outliers,
-// lk_track_points, lk_photometry, lk_residual_map, lk_field_map, lk_rigid_motion, lk_lens_fit, lk_lens_correct).  Allowed in every mode, reference-order included.  `need` says what the
+// lk_track_points, lk_photometry, lk_residual_map, lk_field_map, lk_rigid_motion, lk_lens_fit, lk_lens_correct, lk_stereo_points, lk_stereo_strain).  Allowed in every mode, reference-order included.  `need` says what the
 // call depends on; every refusal is prefixed with `who`, the function the caller called.
 enum : unsigned {
   LK_VIEW_RECORDS = 1u, // the engine-held records of a finished batch solve of the committed sectors (`result`)
@@ -193,4 +193,8 @@ int lk_internal_noise_last(lk_engine *e, float *device_ms, int *workgroups);
 // of the fit; the time covers the pack and the kernels of every evaluation with the downloads and host steps between them
 // (lk_lens_fit) or the pack and the correction (lk_lens_correct), not the bounding box's round trip or the copies of records
 int lk_internal_lens_last(lk_engine *e, float *device_ms, int *chunk, int *chunks, int *evaluations, float *eval_ms);
+// lk_stereo_points or lk_stereo_strain: the lane group and the expected members of a sector's 3 x 3 cells (both 0 after
+// lk_stereo_points) and the frames of the points held on the device (-1: none); the time covers the kernels - for
+// lk_stereo_strain with the bounding box's round trip and the grid - not the copies of records, points or results
+int lk_internal_stereo_last(lk_engine *e, float *device_ms, int *group, double *members, int *held_frames);
 }

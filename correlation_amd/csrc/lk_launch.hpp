@@ -202,3 +202,9 @@ hipError_t lk_launch_motion_remove(const LkMotionArgs &a, hipStream_t st);
 hipError_t lk_launch_lens_sums(const LkLensFitArgs &a, hipStream_t st);
 // a thread per (frame, sector): a.rec without the lens -> a.rec_out, a.status; frame 0's threads write a.centres_out
 hipError_t lk_launch_lens_correct(const LkLensCorrectArgs &a, hipStream_t st);
+
+// ---- lk_stereo.hip: a two-camera rig (lk_stereo_points, lk_stereo_strain)
+// a thread per (frame, sector) of a.n_frames + 1 frames, the reference state first: the triangulated points -> a.out
+hipError_t lk_launch_stereo_points(const LkStereoPointsArgs &a, hipStream_t st);
+// group: 16 or 64 lanes per (frame, sector)
+hipError_t lk_launch_stereo_strain(const LkStereoStrainArgs &a, int group, hipStream_t st);

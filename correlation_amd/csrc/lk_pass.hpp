@@ -1,5 +1,5 @@
 // lk_pass.hpp - the host plumbing the add-on passes share (lk_reseed.cpp, lk_strain.cpp, lk_uncertainty.cpp, lk_outlier.cpp,
-// lk_track.cpp, lk_residual.cpp, lk_pattern.cpp, lk_field.cpp, lk_motion.cpp, lk_noise.cpp, lk_lens.cpp and, through lk_refine.hpp, the five
+// lk_track.cpp, lk_residual.cpp, lk_pattern.cpp, lk_field.cpp, lk_motion.cpp, lk_noise.cpp, lk_lens.cpp, lk_stereo.cpp and, through lk_refine.hpp, the five
 // refinement passes; the error macro also lk_guess_search.cpp): device buffers that free themselves, the state a pass keeps on
 // its slot of the engine, the upload of caller records, the bounding box and cell grid over the centres, the order of the
 // sectors by lane group and the launch per group.  Host only: no .hip file includes it; the device half is lk_neighbours.hpp

@@ -1052,6 +1052,73 @@ class HipCorrelationEngine:
         self._chk(fn(self._h, C.byref(ms), C.byref(chunk), C.byref(chunks), C.byref(evals), C.byref(eval_ms)))
         return ms.value, chunk.value, chunks.value, evals.value, eval_ms.value
 
+    # ---- a two-camera rig (include/lk_engine.h: lk_stereo_points, lk_stereo_strain) ---------
+    def stereo_points(self, cams, ref1, rec0=None, rec1=None, chi_max=0.0):
+        """lk_stereo_points: cams = two CAMERA_DTYPE records; ref1 [S] = camera 0 reference -> camera 1 reference; rec0, rec1
+        [F][S] = camera 0 reference -> frame f of camera 0 / of camera 1 (both None: the shape alone) -> (STEREO_POINT_DTYPE [S]
+        of the reference state, STEREO_POINT_DTYPE [F][S]).  The points stay on the device for stereo_strain().  No engine state
+        changes."""
+        S = self.n_sectors
+        rig = _ffi._rig(cams)
+        ref1 = np.ascontiguousarray(ref1, RESULT_DTYPE).reshape(-1)
+        if (rec0 is None) != (rec1 is None):
+            raise ValueError("stereo_points: rec0 and rec1 must both be given or both be None")
+        if rec0 is not None:
+            rec0, rec1 = np.ascontiguousarray(rec0, RESULT_DTYPE), np.ascontiguousarray(rec1, RESULT_DTYPE)
+            rec0, rec1 = rec0.reshape(-1, rec0.shape[-1]), rec1.reshape(-1, rec1.shape[-1])
+            if rec0.shape != rec1.shape or rec0.shape[1] != S:
+                raise ValueError("stereo_points: rec0 and rec1 must both be [n_frames][n_sectors]")
+        if len(ref1) != S:
+            raise ValueError("stereo_points: ref1 must have one record per sector")
+        F = 0 if rec0 is None else len(rec0)
+        ref_out = np.zeros(S, _ffi.STEREO_POINT_DTYPE)
+        out = np.zeros((F, S), _ffi.STEREO_POINT_DTYPE)
+        cfg = _ffi.LkStereoConfig(0.0, float(chi_max), 0, 0)
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self.lib.lk_stereo_points(self._h, C.byref(cfg), ptr(rig), ptr(ref1), F, ptr(rec0), ptr(rec1), ptr(ref_out),
+                                            ptr(out) if F else None))
+        return ref_out, out
+
+    def stereo_strain(self, radius, ref_points=None, points=None, n_frames=None, min_neighbours=3):
+        """lk_stereo_strain: the strain of the surface through the 3-D points, per (frame, sector) -> STEREO_SURFACE_DTYPE [F][S].
+        ref_points [S] and points [F][S] (both None: the points the last stereo_points left on the device, whose frame count
+        n_frames then defaults to).  No engine state changes."""
+        S = self.n_sectors
+        if (ref_points is None) != (points is None):
+            raise ValueError("stereo_strain: ref_points and points must both be given or both be None")
+        if points is not None:
+            ref_points = np.ascontiguousarray(ref_points, _ffi.STEREO_POINT_DTYPE).reshape(-1)
+            points = np.ascontiguousarray(points, _ffi.STEREO_POINT_DTYPE)
+            points = points.reshape(-1, points.shape[-1])
+            if len(ref_points) != S or points.shape[1] != S:
+                raise ValueError("stereo_strain: ref_points must be [n_sectors] and points [n_frames][n_sectors]")
+            if n_frames is None:
+                n_frames = len(points)
+            elif n_frames != len(points):
+                raise ValueError("stereo_strain: n_frames differs from the frames of points")
+        elif n_frames is None:
+            n_frames = self.stereo_last()[3]
+        F = max(int(n_frames), 0)
+        out = np.zeros((F, S), _ffi.STEREO_SURFACE_DTYPE)
+        cfg = _ffi.LkStereoConfig(float(radius), 0.0, int(min_neighbours), 0)
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self.lib.lk_stereo_strain(self._h, C.byref(cfg), int(n_frames), ptr(ref_points), ptr(points), ptr(out)))
+        return out
+
+    def stereo_last(self):
+        """Bench hook: (device ms, lane group, expected members of a sector's 3 x 3 cells, frames of the points held on the
+        device) of the last stereo_points or stereo_strain call (group and members 0 after stereo_points)."""
+        ms, group, members, held = C.c_float(), C.c_int(), C.c_double(), C.c_int()
+        fn = self.lib.lk_internal_stereo_last
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        self._chk(fn(self._h, C.byref(ms), C.byref(group), C.byref(members), C.byref(held)))
+        return ms.value, group.value, members.value, held.value
+
     # ---- stand-alone pieces -------------------------------------------------------------
     def evaluate(self, sector, level, p):
         pp = np.zeros(6, np.float32)

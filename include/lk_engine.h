@@ -1116,6 +1116,129 @@ int lk_lens_correct(lk_engine *e, const lk_lens_config *cfg, const lk_lens *lens
 int lk_lens_fit(lk_engine *e, const lk_lens_fit_config *cfg, const lk_lens *init, int n_frames, const lk_result *records,
                 const uint8_t *fit_mask, lk_lens_result *out, lk_lens_frame *frames_out, double *sums_out);
 
+/* ---- a two-camera rig: 3-D points from matched records, and strain measured in the specimen's own surface ---- */
+/* Every pass above reads a record as a displacement in the image plane of one camera: a 1 % out-of-plane motion at 400 mm
+ * stand-off reads as 2.5e-3 of dilatation in lk_strain_field, and a tube or a dome has no image plane at all.  With a second,
+ * calibrated camera lk_stereo_points turns matched records into 3-D points and lk_stereo_strain turns a field of 3-D points
+ * into the strain of the surface (csrc/lk_stereo.hpp, csrc/lk_stereo.hip, csrc/lk_stereo.cpp).  The
+ * matching is the existing solve: a cross-camera pair is an image pair (camera 0's reference frame as the undeformed image,
+ * a frame of camera 1 as the deformed one).  The calibration of the rig is input.
+ *   data      one engine serves camera 0; its sectors are committed on camera 0's reference frame.  With c the committed
+ *             centre widened to double, u = p[0], v = p[1] (v = 0 for LK_FM_U), all records solved against camera 0's
+ *             reference frame:
+ *               ref1 [S]      camera 0 reference -> camera 1 reference: the reference state's pixels are c and c + (u, v)
+ *               rec0 [F][S]   camera 0 reference -> camera 0's frame f:  pixel 0 of frame f is c + (u, v)
+ *               rec1 [F][S]   camera 0 reference -> camera 1's frame f:  pixel 1 of frame f is c + (u, v)
+ *   camera    lk_camera: x_cam = R X + t; the undistorted pixel (fx x/z + skew y/z + cx, fy y/z + cy); then lk_lens_distort
+ *             of `lens` (lk_lens_fit's model, in pixels - a fitted lens plugs in unchanged).  Back: lk_lens_undistort, then
+ *             K^-1.  A lens with k1 = k2 = p1 = p2 = 0 is the identity, exactly, and its other fields are not read.
+ *   triangulation  lk_stereo_triangulate of one pair of pixels, in double, + - * / sqrt only, no fused multiply-add: the
+ *             host function and the kernel give the same bytes.
+ *               1. both pixels undistorted (6 Newton steps each, lk_lens_undistort's);
+ *               2. the rays o_k = -R_k^T t_k, d_k = R_k^T K_k^-1 (m_k, 1) in the world frame;
+ *               3. the start: the midpoint of the common perpendicular, from a = d0.d0, b = d0.d1, c = d1.d1, d = d0.(o0 - o1),
+ *                  e = d1.(o0 - o1), det = a c - b^2, s = (b e - c d) / det, t = (a e - b d) / det;
+ *               4. always 7 Gauss-Newton steps on the four reprojection residuals (observed - projected, undistorted
+ *                  pixels) over X: J^T J (3 x 3) factored as L D L^T in one written order.
+ *             residual[4] = the residuals at the result {x0, y0, x1, y1};  epipolar = the signed distance, in undistorted
+ *             pixels of camera 1, of pixel 1 from the line F (m0, 1), F = K1^-T [t_r]x R_r K0^-1 formed once on the host
+ *             (lk_stereo_fundamental; R_r = R1 R0^T, t_r = t1 - R_r t0);  angle = atan2(|d0 x d1|, d0 . d1) in radians.
+ *   status    of a point, checked in this order: LK_STEREO_BAD_RECORD  a record it reads is not good (the shared rule with
+ *             cfg->chi_max; every frame's point reads ref1 too) or a pixel is not finite;  LK_STEREO_OUTSIDE_LENS  a pixel
+ *             outside a lens's domain;  LK_STEREO_PARALLEL  det <= 1e-12 a c (the rays within 1e-6 rad; scale-free), or a
+ *             result that is not finite;  LK_STEREO_BEHIND  s <= 0 or t <= 0, or an iterate with z <= 0 in a camera;  else
+ *             LK_STEREO_OK.  A point that is not OK has every numeric field 0, never NaN.
+ *   lk_stereo_points  one launch, one thread per (frame, sector), the reference state as frame -1: ref_out [S] from ref1,
+ *             out [F][S] from rec0 and rec1.  n_frames = 0 with rec0 = rec1 = out = NULL gives the shape alone.  The points stay
+ *             on the device for a following lk_stereo_strain.  A frame's bytes are the same alone and inside a longer call.
+ *
+ * lk_stereo_strain: per (frame, sector) the strain of the surface through the 3-D points, measured in the surface
+ *   window    lk_strain_field's (`window`, `order` there): the members of the 3 x 3 cells around c_s within cfg->radius of it,
+ *             (dx, dy) = c_j - c_s in double.  A member is good when its reference point and its point of the frame are both
+ *             LK_STEREO_OK.  n = their count.
+ *   fit       least-squares planes over (dx, dy) of six functions: X, Y, Z of the reference point and U = P_f - P_ref (three
+ *             components, formed in double per member).  23 double sums: n, Sx, Sy, Sxx, Sxy, Syy and Sf, Sxf, Syf of each;
+ *             the moments, D and the solve are lk_strain_field's (`fit` there).
+ *   tensor    a1 = dP/dx, a2 = dP/dy (reference tangents);  b_i = a_i + dU/d(x, y);  G = [a_i . a_j],  g = [b_i . b_j];
+ *             Ra = the upper-triangular factor of G: r11 = sqrt(G11), r12 = G12 / r11, r22 = sqrt(G22 - r12^2);
+ *             C = Ra^-T g Ra^-1;  E = (C - I) / 2 = {exx, exy; exy, eyy}, the Green-Lagrange strain in the orthonormal
+ *             tangent basis e1 = a1 / |a1|, e2 perpendicular to e1 in the tangent plane, n = e1 x e2.  E is exact for any
+ *             homogeneous 3-D affine map of a plane, whatever its pose and whatever the image parametrisation (DESIGN.md
+ *             section 32).  e1, e2, theta: lk_strain_from_gradient's formulas;  biot_k = sqrt(1 + 2 e_k) - 1;  normal = the
+ *             fitted displacement at c_s along n.
+ *   residual  a second walk sums the squared 3-D misfit of the three displacement planes;  residual = sqrt(sum / n).
+ *   status    checked in this order: TOO_FEW  n < cfg->min_neighbours;  DEGENERATE  lk_strain_field's rule, or
+ *             G11 G22 - G12^2 <= 1e-12 G11 G22 (the surface seen edge-on);  FILLED  a valid fit at a sector whose own points
+ *             are not both OK;  OK.  TOO_FEW and DEGENERATE: every float field is 0, neighbours = n.
+ *   sources   ref_points [S] and points [n_frames][S] from the caller, or both NULL: the arrays the last lk_stereo_points
+ *             left on the device, with that call's n_frames.  Both sources give the same bytes.
+ *   bytes     lane groups of 16 or 64 per (frame, sector), each with its own fixed order (the host picks as lk_strain_field
+ *             does; test hook LK_STEREO_GROUP=16 / 64).  Within a group size a record's bytes are the same on every run,
+ *             alone or in a longer call and from either source.  Across the two group sizes neighbours and status are the
+ *             same (unless a window sits at a threshold) and the float fields agree within the rounding of double sums
+ *             taken in another order.  Lane 0 rounds each output to float once.
+ *   modes     both calls are synchronous, allowed in every mode, and change no engine state (lk_strain_field's `modes`).
+ *   errors    LK_ERROR_BAD_DOMAIN with a message, outputs untouched: no committed sectors; a null configuration, rig, ref1,
+ *             ref_out or output; n_frames < 0 (lk_stereo_points) or < 1 (lk_stereo_strain) or above 65534; frame arguments
+ *             that are null with n_frames > 0 or not null with n_frames = 0; chi_max not finite; radius not finite or <= 0;
+ *             min_neighbours < 3; non-zero reserved words; a camera that lk_stereo_project refuses; one point array null and
+ *             the other not; device-held points with no lk_stereo_points before, with another n_frames or another sector
+ *             count.
+ *   scope     not covered: calibration of the rig; epipolar-constrained search; dense 3-D maps; lk_group, lk_tracker, the
+ *             report CSV and the CudaClass adapter. */
+typedef struct lk_camera {            /* 256 bytes */
+  double  fx, fy, cx, cy, skew;       /* pixels; fx, fy > 0 */
+  double  R[9], t[3];                 /* row-major rotation and translation: x_cam = R X + t */
+  lk_lens lens;                       /* pixel domain; all four coefficients 0: no lens */
+  double  reserved[7];                /* must be 0 */
+} lk_camera;
+enum { LK_STEREO_OK = 0, LK_STEREO_BAD_RECORD = 1, LK_STEREO_OUTSIDE_LENS = 2, LK_STEREO_PARALLEL = 3, LK_STEREO_BEHIND = 4 };
+enum { LK_STEREO_SURFACE_OK = 0, LK_STEREO_SURFACE_FILLED = 1, LK_STEREO_SURFACE_TOO_FEW = 2, LK_STEREO_SURFACE_DEGENERATE = 3 };
+typedef struct lk_stereo_point {      /* 64 bytes */
+  double  X, Y, Z;                    /* world units */
+  float   residual[4];                /* {x0, y0, x1, y1}: observed - projected, undistorted pixels */
+  float   epipolar, angle;            /* undistorted pixels of camera 1; radians */
+  int32_t status, reserved[3];        /* LK_STEREO_* */
+} lk_stereo_point;
+typedef struct lk_stereo_config {     /* 16 bytes; lk_stereo_points reads chi_max, lk_stereo_strain radius and min_neighbours */
+  float radius;          /* strain window in level-0 pixels of camera 0's reference frame (<=, tested in double) */
+  float chi_max;         /* the shared good rule; <= 0: the error code alone decides */
+  int   min_neighbours;  /* >= 3, counting the sector itself when it is good */
+  int   reserved;        /* must be 0 */
+} lk_stereo_config;
+typedef struct lk_stereo_surface {    /* 128 bytes, one per (frame, sector) */
+  float   X, Y, Z;                    /* the fitted reference point at c_s */
+  float   U, V, W;                    /* the fitted displacement at c_s */
+  float   nx, ny, nz;                 /* the unit normal of the reference surface, e1 x e2 */
+  float   exx, eyy, exy, e1, e2, theta; /* Green-Lagrange in (e1, e2); principal strains e1 >= e2, angle of the first from the basis vector e1 */
+  float   biot1, biot2;               /* sqrt(1 + 2 e_k) - 1 */
+  float   normal;                     /* (U, V, W) . n */
+  float   residual;                   /* world units */
+  int32_t neighbours, status;         /* LK_STEREO_SURFACE_* */
+  int32_t reserved[11];
+} lk_stereo_surface;
+/* Host functions: the kernels' own code compiled for the host; no GPU needed.  LK_ERROR_BAD_DOMAIN for a null pointer, n < 1
+ * or a refused camera: non-zero reserved words, intrinsics, R or t that are not finite, fx or fy <= 0, an R with an entry of
+ * R^T R more than 1e-9 off the identity, or - unless all four coefficients are 0 - a lens that lk_lens_distort refuses.
+ * lk_stereo_project: world points xyz [n][3] -> pixels xy_out [n][2] as the camera shows them; status_out [n] (or NULL) 0, or 1
+ * for a point that is not in front of the camera (its pixel is 0, 0). */
+int lk_stereo_project(const lk_camera *cam, int n, const double *xyz, double *xy_out, uint8_t *status_out);
+/* F [9], row-major, of cams [2] (see `triangulation`) */
+int lk_stereo_fundamental(const lk_camera *cams, double *F_out);
+/* n pairs of pixels x0 [n][2] in camera 0 and x1 [n][2] in camera 1 -> out [n] */
+int lk_stereo_triangulate(const lk_camera *cams, int n, const double *x0, const double *x1, lk_stereo_point *out);
+/* one window: the count n >= 0, sums23 = {Sx, Sy, Sxx, Sxy, Syy, then Sf, Sxf, Syf of X, Y, Z, U, V, W}, whether the sector's
+ * own points are OK, and the second walk's sum of squared misfits -> the record; planes_out [18] (or NULL) receives
+ * {f0, fx, fy} of the six planes in double.  LK_ERROR_BAD_DOMAIN for a null pointer, n < 0 or min_neighbours < 3. */
+int lk_stereo_surface_from_sums(int n, const double *sums23, int min_neighbours, int self_good, double residual_sum,
+                                lk_stereo_surface *out, double *planes_out);
+/* cams: [2]; ref1: host [S]; rec0, rec1: host [n_frames][S]; ref_out: [S]; out: [n_frames][S].  Synchronous. */
+int lk_stereo_points(lk_engine *e, const lk_stereo_config *cfg, const lk_camera *cams, const lk_result *ref1, int n_frames,
+                     const lk_result *rec0, const lk_result *rec1, lk_stereo_point *ref_out, lk_stereo_point *out);
+/* ref_points: host [S] and points: host [n_frames][S], or both NULL; out: [n_frames][S].  Synchronous. */
+int lk_stereo_strain(lk_engine *e, const lk_stereo_config *cfg, int n_frames, const lk_stereo_point *ref_points,
+                     const lk_stereo_point *points, lk_stereo_surface *out);
+
 /* ---- photometry and the back-warped residual map: the grey values once more ---------------- */
 /* chi is a plain sum of squared grey-level differences: a frame that is 20 % darker gives every sector a large chi although
  * the match is perfect.  lk_photometry evaluates every good sector once at its record's parameters and reports the

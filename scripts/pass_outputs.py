@@ -169,6 +169,41 @@ def run_lens():
     return out
 
 
+def run_stereo():
+    """a plane Z = 400 + 0.2 X seen by two cameras 20 degrees apart (no calibration involved: the records are exact
+    projections), stretched and pushed back a little more in each of three frames"""
+    import correlation_amd as ca
+    e, rec = solved("grid", ca.FM_UVUXUYVXVY, ca.IM_BICUBIC)
+    cen = np.float32([e.sector_info(s)[1:] for s in range(e.n_sectors)]).astype(np.float64)
+    th = np.deg2rad(20.0)
+    R1 = np.float64([[np.cos(th), 0.0, np.sin(th)], [0.0, 1.0, 0.0], [-np.sin(th), 0.0, np.cos(th)]])
+    C1 = np.float64([400.0 * np.sin(th), 0.0, 400.0 * (1.0 - np.cos(th))])
+    cams = [ca.make_camera(800.0, 800.0, 127.5, 127.5, lens=ca.make_lens(126.0, 117.0, 147.785, -0.03, 0.008)),
+            ca.make_camera(800.0, 802.0, 127.5, 125.5, R=R1, t=-R1 @ C1, skew=0.05, lens=ca.make_lens(130.0, 125.0, 150.0, 0.02, 0.0, 1e-3, -5e-4))]
+    m = (ca.lens_undistort(cams[0]["lens"], cen) - 127.5) / 800.0          # camera 0's rays (x, y, 1) through the centres
+    depth = 400.0 / (1.0 - 0.2 * m[:, 0])
+    P = np.stack([m[:, 0] * depth, m[:, 1] * depth, depth], 1)
+
+    def records(pixels, bad):
+        out = rec.copy()
+        out["p"][:, :2] = (pixels - cen).astype(np.float32)
+        out["error_code"][:] = 0
+        out["chi"][:] = 0.5
+        out["error_code"][bad] = 3
+        return out
+
+    frames = [P * [1.0 + 0.01 * k, 1.0 - 0.005 * k, 1.0] + [0.5 * k, 0.0, 2.0 * k] for k in (1, 2, 3)]
+    ref1 = records(ca.stereo_project(cams[1], P), [40, 41])
+    rec0 = np.stack([records(ca.stereo_project(cams[0], X), [100]) for X in frames])
+    rec1 = np.stack([records(ca.stereo_project(cams[1], X), [575]) for X in frames])
+    ref_pts, pts = e.stereo_points(cams, ref1, rec0, rec1)
+    out = {"stereo.ref_points": np.frombuffer(ref_pts.tobytes(), np.uint8), "stereo.points": np.frombuffer(pts.tobytes(), np.uint8)}
+    for name, radius in (("", RADIUS), ("_tiny", TINY_RADIUS)):
+        out["stereo.surface" + name] = np.frombuffer(e.stereo_strain(radius).tobytes(), np.uint8)
+    out["stereo.surface_caller"] = np.frombuffer(e.stereo_strain(RADIUS, ref_pts, pts).tobytes(), np.uint8)
+    return out
+
+
 def run_plan():
     import correlation_amd as ca
     out = {}
@@ -500,6 +535,7 @@ VARIANTS += [("track_g%d" % g, {"LK_TRACK_GROUP": str(g)}, run_track) for g in (
 VARIANTS += [("field_walk%d" % w, {"LK_FIELD_WALK": str(w)}, run_field) for w in (0, 1)]
 VARIANTS += [("motion_chunk%d" % c, {"LK_MOTION_CHUNK": str(c)}, run_motion) for c in (64, 2048)]
 VARIANTS += [("lens_chunk%d" % c, {"LK_LENS_CHUNK": str(c)}, run_lens) for c in (64, 2048)]
+VARIANTS += [("stereo_g%d" % g, {"LK_STEREO_GROUP": str(g)}, run_stereo) for g in (16, 64)]
 VARIANTS += [("plan", {}, run_plan), ("map", {}, run_map), ("evaluate", {}, run_evaluate), ("backward", {}, run_backward),
              ("pattern", {}, run_pattern), ("noise", {}, run_noise), ("znssd", {}, run_znssd), ("quadratic", {}, run_quadratic),
              ("spline", {}, run_spline), ("weighted", {}, run_weighted), ("composed", {}, run_composed)]
