@@ -197,4 +197,10 @@ int lk_internal_lens_last(lk_engine *e, float *device_ms, int *chunk, int *chunk
 // lk_stereo_points) and the frames of the points held on the device (-1: none); the time covers the kernels - for
 // lk_stereo_strain with the bounding box's round trip and the grid - not the copies of records, points or results
 int lk_internal_stereo_last(lk_engine *e, float *device_ms, int *group, double *members, int *held_frames);
+// Test hook (tests/test_cell_grid_gpu.py), no pass's last call: the cell grid over the committed centres that a neighbour pass
+// builds for `radius` (lk_pass_grid, in buffers of its own), its geometry and its tables - cell_of [S], start [nx ny + 1] (the
+// caller's array holds start_capacity words; 4 S + 1025 always suffice), members [S]; any pointer may be null.  Changes no
+// engine state; allowed in every mode.
+int lk_internal_cell_grid(lk_engine *e, float radius, int *nx, int *ny, double *cell, double *x0, double *y0, uint32_t *cell_of,
+                          uint32_t *start, size_t start_capacity, uint32_t *members);
 }

@@ -1,6 +1,7 @@
 // lk_reseed.cpp - host side of the recovery pass (include/lk_engine.h: lk_reseed_failed, lk_get_reseed_info,
 // lk_reseed_plan).  The kernels are lk_reseed.hip; the retries are solved by the engine's own launch code
-// (lk_internal_solve_set -> launch_all) on a sector set this file compacts on the device.
+// (lk_internal_solve_set -> launch_all) on a sector set this file compacts on the device.  Also the test hook that shows the
+// cell grid every neighbour pass shares (lk_internal.hpp: lk_internal_cell_grid).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -260,6 +261,47 @@ int lk_reseed_plan(lk_engine *e, const lk_reseed_config *cfg, const lk_result *r
   LK_HIPCHK(hipMemcpyAsync(guesses_out, st->guess.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
   LK_HIPCHK(hipMemcpyAsync(info_out, st->plan_info.p, n * sizeof(lk_reseed_info), hipMemcpyDeviceToHost, v.stream));
   LK_HIPCHK(hipStreamSynchronize(v.stream));
+  return LK_ERROR_NONE;
+}
+
+// test hook (lk_internal.hpp): the grid every neighbour pass would build, in buffers of its own that go with the call
+int lk_internal_cell_grid(lk_engine *e, float radius, int *nx, int *ny, double *cell, double *x0, double *y0, uint32_t *cell_of,
+                          uint32_t *start, size_t start_capacity, uint32_t *members) {
+  if (!e)
+    return LK_ERROR_BAD_DOMAIN;
+  if (!std::isfinite(radius) || !(radius > 0.f))
+    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_internal_cell_grid: radius must be finite and positive");
+  LkPassView v{};
+  if (int rc = lk_internal_pass_view(e, "lk_internal_cell_grid", 0, -1, &v))
+    return rc;
+  LkPassState st;
+  LkDevBytes bbox;
+  LkCellGridBufs bufs;
+  LK_HIPCHK(st.init());
+  LK_HIPCHK(bbox.ensure(4 * sizeof(float)));
+  LkReseedGrid g{};
+  if (int rc = lk_pass_grid(e, "lk_internal_cell_grid", &st, bbox, bufs, v.center, v.S, radius, v.stream, &g))
+    return rc;
+  const size_t n = (size_t)v.S, n_cells = (size_t)g.nx * (size_t)g.ny;
+  if (start && start_capacity < n_cells + 1)
+    return lk_internal_fail(e, LK_ERROR_BAD_DOMAIN, "lk_internal_cell_grid: start holds fewer than nx ny + 1 words");
+  if (cell_of)
+    LK_HIPCHK(hipMemcpyAsync(cell_of, g.cell_of, n * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+  if (start)
+    LK_HIPCHK(hipMemcpyAsync(start, g.start, (n_cells + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+  if (members)
+    LK_HIPCHK(hipMemcpyAsync(members, g.members, n * sizeof(uint32_t), hipMemcpyDeviceToHost, v.stream));
+  LK_HIPCHK(hipStreamSynchronize(v.stream)); // (the buffers are freed on return)
+  if (nx)
+    *nx = g.nx;
+  if (ny)
+    *ny = g.ny;
+  if (cell)
+    *cell = g.cell;
+  if (x0)
+    *x0 = g.x0;
+  if (y0)
+    *y0 = g.y0;
   return LK_ERROR_NONE;
 }
 

@@ -403,6 +403,24 @@ class HipCorrelationEngine:
                                           info.ctypes.data_as(C.c_void_p)))
         return g, info
 
+    def cell_grid(self, radius):
+        """Test hook (lk_internal_cell_grid): the cell grid a neighbour pass builds over the committed centres for `radius`,
+        as a dict: nx, ny, cell, x0, y0 and the tables cell_of uint32 [S], start uint32 [nx ny + 1], members uint32 [S].
+        No engine state changes."""
+        S = self.n_sectors
+        nx, ny, cell, x0, y0 = C.c_int(), C.c_int(), C.c_double(), C.c_double(), C.c_double()
+        cell_of, members = np.zeros(S, np.uint32), np.zeros(S, np.uint32)
+        start = np.zeros(4 * S + 1025, np.uint32)      # the sizing rule caps the table at 4 S + 1024 cells
+        fn = self.lib.lk_internal_cell_grid
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                       C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        self._chk(fn(self._h, float(radius), C.byref(nx), C.byref(ny), C.byref(cell), C.byref(x0), C.byref(y0),
+                     cell_of.ctypes.data_as(C.c_void_p), start.ctypes.data_as(C.c_void_p), start.size,
+                     members.ctypes.data_as(C.c_void_p)))
+        return dict(nx=nx.value, ny=ny.value, cell=cell.value, x0=x0.value, y0=y0.value, cell_of=cell_of,
+                    start=start[:nx.value * ny.value + 1].copy(), members=members)
+
     # ---- strain field: windowed plane fit of the solved displacements ------------------------------
     def strain_field(self, radius, chi_max=0.0, min_neighbours=3, tensor=_ffi.STRAIN_GREEN_LAGRANGE, records=None):
         """lk_strain_field: a STRAIN_DTYPE array [S] from the engine-held records of the last batch solve (after

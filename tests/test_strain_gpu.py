@@ -15,6 +15,7 @@ import pytest
 
 import correlation_amd as ca
 from correlation_amd import _ffi, speckle
+from records_ref import synthetic_records  # noqa: F401  (other test modules import it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -118,14 +119,16 @@ def scale_of(rec, model, chi_max):
     return float(np.abs(rec["p"][good][:, :1 if model == ca.FM_U else 2]).max())
 
 
-def check_against_reference(got, ref, U, what):
+def check_against_reference(got, ref, U, what, pitch=SIDE):
+    """pitch: the h of the tolerance (the docstring above) - this file's lattice, or the nominal pitch of another layout
+    (tests/test_cell_grid_gpu.py)"""
     vals, nbrs, status, _ = ref
     assert np.array_equal(got["status"], status), what
     assert np.array_equal(got["neighbours"], nbrs), what
     assert not got["reserved"].any()
     worst = 0.0
     for k, name in enumerate(FLOATS):
-        tol = 2.0 ** -22 * np.abs(vals[:, k]) + 1e-9 * U / SIDE
+        tol = 2.0 ** -22 * np.abs(vals[:, k]) + 1e-9 * U / pitch
         err = np.abs(got[name].astype(np.float64) - vals[:, k])
         worst = max(worst, float((err / tol).max()))
         assert (err <= tol).all(), (what, name, int(np.argmax(err / tol)), float(err.max()))
@@ -136,22 +139,6 @@ def check_against_reference(got, ref, U, what):
 
 
 # ---- 1. against the float64 brute force over all pairs ------------------------------------------------------------------
-def synthetic_records(S, rng, chi_max, share):
-    """random displacements of a few pixels; `share` of the sectors made bad in EACH of three ways: an error code, a NaN
-    parameter, a chi above chi_max"""
-    rec = np.zeros(S, ca.RESULT_DTYPE)
-    rec["p"] = rng.normal(0, 1, (S, 6)) * np.float32([8, 8, 0.05, 0.05, 0.05, 0.05])
-    rec["chi"] = rng.uniform(0.1, 0.9 * chi_max, S)
-    rec["n_points"] = 361
-    rec["iterations"] = rng.integers(1, 20, S)
-    k = max(1, int(round(share * S)))
-    bad = rng.permutation(S)[:3 * k]
-    rec["error_code"][bad[:k]] = rng.integers(1, 6, k)
-    rec["p"][bad[k:2 * k], 0] = np.nan
-    rec["chi"][bad[2 * k:]] = chi_max * 1.5
-    return rec
-
-
 ANNULAR = [(20.0, 12.0, 0.3 + 1.1 * k, 0.9, 120.0 + 7.0 * k, 118.0 - 5.0 * k, 6) for k in range(4)]
 LAYOUTS = {
     "grid": (grid_rects(), ()),
