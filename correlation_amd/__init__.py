@@ -15,6 +15,8 @@ from ._ffi import (FLAVOUR_FAST, FLAVOUR_REFERENCE, FLAVOUR_SAFE, LAUNCH_BACKWAR
 from ._ffi import (GS_NO_CANDIDATE, GS_OK, GS_TEXTURELESS, GS_TOO_FEW, GS_TOO_LARGE, GS_WEAK,  # noqa: F401
                    GUESS_MATCH_DTYPE)
 from ._ffi import ROTATED_MATCH_DTYPE, RS_MAX_ANGLES, rotation_table  # noqa: F401
+from ._ffi import (EP_MAX_BAND, EP_MAX_GROUP, EP_MAX_NODES, EP_MAX_STATIONS, EPIPOLAR_CURVE_DTYPE, EPIPOLAR_MATCH_DTYPE,  # noqa: F401
+                   GS_NO_CURVE, GS_TOO_LONG, epipolar_curves)
 from ._ffi import (RESEED_GOOD, RESEED_INFO_DTYPE, RESEED_NO_NEIGHBOUR, RESEED_NOT_IMPROVED, RESEED_PLANNED,  # noqa: F401
                    RESEED_RECOVERED)
 from ._ffi import (STRAIN_DEGENERATE, STRAIN_DTYPE, STRAIN_FILLED, STRAIN_GREEN_LAGRANGE, STRAIN_OK, STRAIN_SMALL,  # noqa: F401

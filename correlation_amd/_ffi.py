@@ -98,6 +98,39 @@ ROTATED_MATCH_DTYPE = np.dtype({"names": [f for f, _ in LkRotatedMatch._fields_]
                                 "itemsize": C.sizeof(LkRotatedMatch)})
 assert ROTATED_MATCH_DTYPE.itemsize == 64
 
+# stereo initial guess along the epipolar curve (include/lk_engine.h: lk_search_epipolar)
+GS_NO_CURVE, GS_TOO_LONG = 6, 7
+EP_MAX_BAND, EP_MAX_NODES, EP_MAX_STATIONS, EP_MAX_GROUP = 8, 33, 2048, 4096
+
+
+class LkEpipolarSearch(C.Structure):
+    _fields_ = [("search", LkGuessSearch), ("n_nodes", C.c_int), ("shape", C.c_int), ("reserved", C.c_int * 3),
+                ("z_near", C.c_double), ("z_far", C.c_double), ("normal", C.c_double * 3)]
+
+
+class LkEpipolarCurve(C.Structure):
+    _fields_ = [("axis", C.c_int32), ("first_station", C.c_int32), ("n_stations", C.c_int32), ("first_index", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class LkEpipolarMatch(C.Structure):
+    _fields_ = [("shift_x", C.c_int32), ("shift_y", C.c_int32), ("station", C.c_int32), ("band_offset", C.c_int32),
+                ("node", C.c_int32), ("n_samples", C.c_int32), ("n_valid", C.c_int32), ("status", C.c_int32),
+                ("score", C.c_double), ("runner_up", C.c_double), ("station_refined", C.c_float), ("inv_depth", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
+# lk_epipolar_curve and lk_epipolar_match as numpy records (same layouts as the structures)
+EPIPOLAR_CURVE_DTYPE = np.dtype([(k, np.int32) for k in ("axis", "first_station", "n_stations", "first_index", "status")] +
+                                [("reserved", np.int32, (3,))])
+EPIPOLAR_MATCH_DTYPE = np.dtype([(k, np.int32) for k in ("shift_x", "shift_y", "station", "band_offset", "node", "n_samples",
+                                                         "n_valid", "status")] +
+                                [("score", np.float64), ("runner_up", np.float64), ("station_refined", np.float32),
+                                 ("inv_depth", np.float32), ("reserved", np.int32, (2,))])
+assert C.sizeof(LkEpipolarSearch) == 80 and LkEpipolarSearch.z_near.offset == 40
+assert EPIPOLAR_CURVE_DTYPE.itemsize == C.sizeof(LkEpipolarCurve) == 32
+assert EPIPOLAR_MATCH_DTYPE.itemsize == C.sizeof(LkEpipolarMatch) == 64
+
 # recovery pass (include/lk_engine.h: lk_reseed_failed)
 RESEED_GOOD, RESEED_RECOVERED, RESEED_NO_NEIGHBOUR, RESEED_NOT_IMPROVED, RESEED_PLANNED = range(5)
 
@@ -480,6 +513,11 @@ SYMBOLS = {
     "lk_search_rotated": (C.c_int, [_P, C.POINTER(LkRotatedSearch), _F]),
     "lk_get_rotated_search_info": (C.c_int, [_P, _P]),
     "lk_get_rotated_search_profile": (C.c_int, [_P, _P]),
+    "lk_search_epipolar": (C.c_int, [_P, C.POINTER(LkEpipolarSearch), _P, _P, _F]),
+    "lk_get_epipolar_search_info": (C.c_int, [_P, _P]),
+    "lk_get_epipolar_search_profile": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
+    "lk_epipolar_curves": (C.c_int, [C.POINTER(LkEpipolarSearch), _P, C.c_int, _F, _P, C.c_int, _P, C.POINTER(C.c_int), C.c_int,
+                                     _P, _P, _P, _P]),
     "lk_rotation_table": (C.c_int, [C.POINTER(LkRotatedSearch), _F]),
     "lk_reseed_failed": (C.c_int, [_P, C.POINTER(LkReseedConfig), _P, _I]),
     "lk_get_reseed_info": (C.c_int, [_P, _P]),
@@ -1116,3 +1154,49 @@ def stereo_surface_from_sums(n, sums23, min_neighbours=3, self_good=True, residu
                                                 out.ctypes.data_as(_P), planes.ctypes.data_as(_P)) != 0:
         raise ValueError("lk_stereo_surface_from_sums: n < 0 or min_neighbours < 3")
     return (out[0], planes) if return_planes else out[0]
+
+
+def epipolar_config(z_near, z_far, level=-1, band=1, n_nodes=17, shape=0, normal=None, min_samples=0, min_score=0.0, def_slot=-1):
+    """an LkEpipolarSearch (include/lk_engine.h: lk_epipolar_search); normal None: camera 0's optical axis"""
+    nrm = (0.0, 0.0, 0.0) if normal is None else tuple(float(v) for v in np.asarray(normal, np.float64).reshape(3))
+    return LkEpipolarSearch(LkGuessSearch(int(level), int(band), int(min_samples), float(min_score), int(def_slot)), int(n_nodes),
+                            int(shape), (C.c_int * 3)(0, 0, 0), float(z_near), float(z_far), (C.c_double * 3)(*nrm))
+
+
+def _depth_range(depth_range, n):
+    if depth_range is None:
+        return None
+    dr = np.ascontiguousarray(depth_range, np.float64)
+    if dr.shape != (n, 2):
+        raise ValueError("depth_range must be [n][2]")
+    return dr
+
+
+def epipolar_curves(cams, centres, z_near, z_far, level, band=1, n_nodes=17, shape=0, normal=None, depth_range=None, cfg=None):
+    """lk_epipolar_curves (host, the table the kernels of lk_search_epipolar read) of centres [n][2] at pyramid `level`:
+    -> dict(curves EPIPOLAR_CURVE_DTYPE [n], other int32 [stations], node int32 [stations], inv_depth float64 [stations],
+    shape float32 [n][n_nodes][4] or None).  cfg: an LkEpipolarSearch that replaces the keyword arguments."""
+    global _compose_lib
+    if _compose_lib is None:
+        _compose_lib = load_library()
+    if cfg is None:
+        cfg = epipolar_config(z_near, z_far, level, band, n_nodes, shape, normal)
+    rig = _rig(cams)
+    cen = np.ascontiguousarray(centres, np.float32).reshape(-1, 2)
+    n = len(cen)
+    dr = _depth_range(depth_range, n)
+    curves, count = np.zeros(max(n, 1), EPIPOLAR_CURVE_DTYPE), C.c_int(0)
+
+    def ptr(a):
+        return None if a is None else a.ctypes.data_as(_P)
+    fn = _compose_lib.lk_epipolar_curves
+    if fn(C.byref(cfg), ptr(rig), n, fptr(cen), ptr(dr), int(level), ptr(curves), C.byref(count), 0, None, None, None, None) != 0:
+        raise ValueError("lk_epipolar_curves: a configuration, camera, depth range, level or centre list that is refused")
+    m = max(count.value, 1)
+    other, node, inv_depth = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float64)
+    shp = np.zeros((n, cfg.n_nodes, 4), np.float32) if cfg.shape else None
+    if fn(C.byref(cfg), ptr(rig), n, fptr(cen), ptr(dr), int(level), ptr(curves), C.byref(count), m, ptr(other), ptr(node),
+          ptr(inv_depth), ptr(shp)) != 0:
+        raise ValueError("lk_epipolar_curves: refused")
+    k = count.value
+    return dict(curves=curves[:n], other=other[:k], node=node[:k], inv_depth=inv_depth[:k], shape=shp)

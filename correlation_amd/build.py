@@ -19,7 +19,7 @@ SOURCES = ["lk_engine.cpp", "lk_engine_images.cpp", "lk_engine_sectors.cpp", "lk
            "lk_quadratic.cpp", "lk_quadratic.hip", "lk_spline.cpp", "lk_spline.hip",
            "lk_weighted.cpp", "lk_weighted.hip", "lk_composed.cpp", "lk_composed.hip",
            "lk_motion.cpp", "lk_motion.hip", "lk_noise.cpp", "lk_noise.hip", "lk_lens.cpp", "lk_lens.hip",
-           "lk_stereo.cpp", "lk_stereo.hip"]
+           "lk_stereo.cpp", "lk_stereo.hip", "lk_epipolar_search.cpp", "lk_epipolar_search.hip"]
 HEADERS = ["lk_engine_state.hpp", "lk_device.hpp", "lk_roi.hpp", "lk_solver_common.hpp", "lk_compose.hpp", "lk_launch.hpp", "lk_search_common.hpp", "lk_neighbours.hpp", "lk_rect_walk.hpp", "lk_sector_eval.hpp", "lk_cell_grid.hpp", "lk_pass.hpp", "lk_refine.hpp", "lk_strain.hpp", "lk_uncertainty.hpp", "lk_outlier.hpp", "lk_track.hpp", "lk_residual.hpp", "lk_pattern.hpp", "lk_field.hpp", "lk_znssd.hpp", "lk_znssd_loop.hpp", "lk_quadratic.hpp", "lk_quadratic_loop.hpp", "lk_spline.hpp", "lk_weighted.hpp", "lk_sector_policies.hpp", "lk_composed.hpp", "lk_motion.hpp", "lk_noise.hpp", "lk_lens.hpp", "lk_stereo.hpp", os.path.join("..", "..", "include", "lk_engine.h"),
            os.path.join("..", "..", "include", "lk_tracker.h"), os.path.join("..", "..", "include", "lk_group.h")]
 

@@ -222,6 +222,32 @@ struct LkRotatedSearchArgs {
 };
 constexpr int kLkRsReduceThreads = 64; // lanes of the reduce kernel's group
 
+// Stereo guess along the epipolar curve (lk_epipolar_search.hip): one workgroup per (sector, run) scores a run of stations that
+// share one template map - with shape = 1 the stations of one node, run k being node k's; with shape = 0, where every station
+// shares the identity, a stretch of the curve - and writes an LkEpNodeRecord and its stations' part of the profile; one lane
+// group per sector reduces the records to an lk_epipolar_match and the guess.
+struct LkEpNodeRecord { // 32 bytes
+  double best;          // -2 where the run has no scored candidate
+  int station, band_offset, n_valid; // the run's winner: m (of the sector's curve) and b
+  int status;           // -1: the run is empty; else LK_GS_* of the sector's template, LK_GS_NO_CANDIDATE or LK_GS_OK
+  int pad[2];
+};
+struct LkEpipolarSearchArgs {
+  LkGuessSearchArgs gs;           // images, lists, guesses, history, level, radius (the band), min_samples, min_score, win_bytes
+  const float2 *center;           // [S] the committed level-0 centres
+  const lk_epipolar_curve *curve; // [S] lk_epipolar_curves' table
+  const int32_t *other;           // [stations] of all sectors, a curve's at its first_index
+  const int32_t *node;            // [stations]
+  const double *inv_depth;        // [stations]
+  const float4 *shape;            // [S][n_nodes] {a11, a12, a21, a22} (shape = 1)
+  const int2 *run;                // [S][n_runs] {first m, stations} of a run on its sector's curve (no stations: none)
+  LkEpNodeRecord *rec;            // [S][n_runs]
+  double *profile;                // [stations]
+  lk_epipolar_match *match;       // [S]
+  int n_nodes, n_runs, with_shape; // with_shape: n_runs == n_nodes
+  int max_run, max_cand;          // the longest run of the launch in stations and in candidates: sizes the dynamic LDS
+};
+
 // Backward (inverse-compositional) update (lk_backward.hip, lk_set_update): one lane group per sector for its whole
 // coarse-to-fine solve.  The group is chosen from the sector's level-0 sample count alone (kLkBwGroup*), so that a
 // sector's record does not depend on what else is solved with it.

@@ -91,7 +91,7 @@ struct LkPassSlot {
   virtual ~LkPassSlot() = default;
 };
 enum LkPass { LK_PASS_RESEED, LK_PASS_STRAIN, LK_PASS_UNCERTAINTY, LK_PASS_OUTLIER, LK_PASS_TRACK, LK_PASS_RESIDUAL, LK_PASS_PATTERN,
-              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_ROTATED, LK_PASS_MOTION, LK_PASS_NOISE, LK_PASS_LENS, LK_PASS_STEREO, LK_PASS_COUNT };
+              LK_PASS_FIELD, LK_PASS_ZNSSD, LK_PASS_QUADRATIC, LK_PASS_SPLINE, LK_PASS_WEIGHTED, LK_PASS_COMPOSED, LK_PASS_ROTATED, LK_PASS_MOTION, LK_PASS_NOISE, LK_PASS_LENS, LK_PASS_STEREO, LK_PASS_EPIPOLAR, LK_PASS_COUNT };
 LkPassSlot **lk_internal_pass_slot(lk_engine *e, int which);
 
 // What a post-processing pass reads of the engine (lk_strain_field, lk_parameter_uncertainty, lk_flag_outliers,
@@ -197,6 +197,10 @@ int lk_internal_lens_last(lk_engine *e, float *device_ms, int *chunk, int *chunk
 // lk_stereo_points) and the frames of the points held on the device (-1: none); the time covers the kernels - for
 // lk_stereo_strain with the bounding box's round trip and the grid - not the copies of records, points or results
 int lk_internal_stereo_last(lk_engine *e, float *device_ms, int *group, double *members, int *held_frames);
+// lk_search_epipolar: its two kernels by HIP events (waits for them), the host's time for the curve table, the candidates of
+// all sectors, the LDS window bound of the launch and the longest run of stations one workgroup takes
+int lk_internal_epipolar_last(lk_engine *e, float *search_ms, float *reduce_ms, double *curves_ms, long long *candidates,
+                              int *win_bytes, int *max_run);
 // Test hook (tests/test_cell_grid_gpu.py), no pass's last call: the cell grid over the committed centres that a neighbour pass
 // builds for `radius` (lk_pass_grid, in buffers of its own), its geometry and its tables - cell_of [S], start [nx ny + 1] (the
 // caller's array holds start_capacity words; 4 S + 1025 always suffice), members [S]; any pointer may be null.  Changes no

@@ -41,6 +41,14 @@ hipError_t lk_launch_rotated_search(const LkRotatedSearchArgs &a, hipStream_t st
 // one lane group per sector: the winner across angles, the guess, the history, the match and the profile
 hipError_t lk_launch_rotated_reduce(const LkRotatedSearchArgs &a, hipStream_t st);
 
+// ---- lk_epipolar_search.hip: the same search along the epipolar curve of a calibrated rig
+// one workgroup per (sector, run of stations that share a template map): the per-run records and the profile
+hipError_t lk_launch_epipolar_search(const LkEpipolarSearchArgs &a, hipStream_t st);
+// one lane group per sector: the winner across the runs, the guess, the history and the match
+hipError_t lk_launch_epipolar_reduce(const LkEpipolarSearchArgs &a, hipStream_t st);
+// LDS left for the staged window of a launch whose longest run has max_run stations and max_cand candidates
+int lk_epipolar_search_window_budget(int max_run, int max_cand);
+
 // ---- lk_kernels.hip: pyramids and the level table
 hipError_t lk_launch_pyramid(const uint8_t *src, int srows, int scols, uint8_t *dst, hipStream_t st);
 hipError_t lk_launch_set_views(const LkLevelView *h_views, LkLevelView *d_views, hipStream_t st);

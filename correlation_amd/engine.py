@@ -376,6 +376,49 @@ class HipCorrelationEngine:
         """lk_rotation_table: the {cos, sin} table search_rotated uploads, float32 [2 n_half + 1][2]."""
         return _ffi.rotation_table(angle_step, n_half, angle_center)
 
+    # ---- stereo initial guess: the same search along the epipolar curve of a calibrated rig ------
+    def search_epipolar(self, cams, z_near, z_far, level=-1, band=1, n_nodes=17, shape=0, normal=None, depth_range=None,
+                        guesses=None, min_samples=0, min_score=0.0, def_slot=-1):
+        """search_guesses' template scored at the integer stations of every sector's epipolar curve in camera 1 - camera 0's ray
+        through the sector's centre between the depths z_near and z_far (depth_range [S][2]: per sector) - and +-band pixels
+        across it (include/lk_engine.h: lk_search_epipolar).  cams: two CAMERA_DTYPE records; shape 1: the template is mapped by
+        the Jacobian the plane of `normal` induces and an OK sector also gets g[2..5].  guesses as for search_guesses (their
+        first two words are no search centre here)."""
+        cfg = _ffi.epipolar_config(z_near, z_far, level, band, n_nodes, shape, normal, min_samples, min_score, def_slot)
+        rig = None if cams is None else _ffi._rig(cams)
+        dr = _ffi._depth_range(depth_range, self.n_sectors)
+        g = None if guesses is None else np.array(guesses, np.float32).reshape(self.n_sectors, 6)
+        self._chk(self.lib.lk_search_epipolar(self._h, C.byref(cfg), None if rig is None else rig.ctypes.data_as(C.c_void_p),
+                                              None if dr is None else dr.ctypes.data_as(C.c_void_p),
+                                              None if g is None else _ffi.fptr(g)))
+        return g
+
+    def epipolar_search_info(self):
+        """The matches of the last search_epipolar: an EPIPOLAR_MATCH_DTYPE array [S]."""
+        out = np.zeros(self.n_sectors, _ffi.EPIPOLAR_MATCH_DTYPE)
+        self._chk(self.lib.lk_get_epipolar_search_info(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def epipolar_search_profile(self):
+        """The last search_epipolar's curves (EPIPOLAR_CURVE_DTYPE [S]) and its best score per station, float64, concatenated:
+        sector s at curves[s]["first_index"], curves[s]["n_stations"] values, -2 where a station has none."""
+        curves, count = np.zeros(max(self.n_sectors, 1), _ffi.EPIPOLAR_CURVE_DTYPE), C.c_int(0)
+        self._chk(self.lib.lk_get_epipolar_search_profile(self._h, curves.ctypes.data_as(C.c_void_p), None, C.byref(count)))
+        prof = np.zeros(max(count.value, 1), np.float64)
+        self._chk(self.lib.lk_get_epipolar_search_profile(self._h, curves.ctypes.data_as(C.c_void_p), prof.ctypes.data_as(C.c_void_p),
+                                                          C.byref(count)))
+        return curves[:self.n_sectors], prof[:count.value]
+
+    def epipolar_last(self):
+        """bench hook: (search kernel ms, reduce kernel ms, host curve table ms, candidates, LDS window bytes, longest run)"""
+        a, b, c, n, w, r = C.c_float(0), C.c_float(0), C.c_double(0), C.c_longlong(0), C.c_int(0), C.c_int(0)
+        fn = self.lib.lk_internal_epipolar_last
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_longlong),
+                       C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self._chk(fn(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n), C.byref(w), C.byref(r)))
+        return a.value, b.value, c.value, n.value, w.value, r.value
+
     # ---- recovery pass: failed sectors re-solved from their converged neighbours ---------------
     def reseed_failed(self, radius, chi_max=0.0, min_neighbours=1, max_rounds=8, want_records=True):
         """lk_reseed_failed on the records of the last correlate_all: returns (records [S] or None, sectors recovered)."""

@@ -486,6 +486,124 @@ int lk_get_rotated_search_profile(lk_engine *e, double *best_per_angle);
 /* host: {c_k, s_k}, [2K+1][2], the table the kernels read; LK_ERROR_BAD_DOMAIN for a bad n_half, step or centre */
 int lk_rotation_table(const lk_rotated_search *cfg, float *cos_sin_out);
 
+/* ---- stereo initial guess: ZNCC search along the epipolar curve ------------------------------ */
+/* The cross-camera pair of a calibrated rig (lk_stereo_points below: camera 0's reference frame as LK_IMG_UND, a frame of
+ * camera 1 as the deformed image) has its match on one curve: the image in camera 1 of camera 0's ray through the sector's
+ * centre, cut to a depth range.  lk_search_epipolar scores lk_search_guesses' template at the integer stations of that curve
+ * and in a band of +-B pixels across it, instead of a square of (2R+1)^2 shifts about a given centre (csrc/lk_epipolar_search.hip,
+ * csrc/lk_epipolar_search.cpp).  The incoming g[0], g[1] are not a search centre here: the curve is.
+ *   curve      lk_epipolar_curves, on the host, in double, with the camera functions of lk_stereo_project / lk_stereo_triangulate
+ *              (csrc/lk_stereo.hpp), once per call.  Of sector s, at level L, with N = n_nodes:
+ *                start     c = the committed level-0 centre (lk_get_sector_info) widened to double; m = c undistorted in camera
+ *                          0; the ray o + z d of m with d = R0^T K0^-1 (m, 1), so that z is the depth along camera 0's axis.
+ *                nodes     rho_near = 1 / z_near, rho_far = 1 / z_far (the sector's depth_range entry where one is given);
+ *                          rho_k = rho_near + k ((rho_far - rho_near) / (N - 1)), k = 0 .. N-1; P_k = o + (1 / rho_k) d;
+ *                          q_k = P_k projected into camera 1, lens included; w_k = (q_k - c) / 2^L, a displacement in level-L
+ *                          pixels as g / 2^L is for the other searches.
+ *                axis      a = x if |w_{N-1}.x - w_0.x| >= |w_{N-1}.y - w_0.y|, else y; b is the other coordinate.
+ *                stations  lo, hi = the smaller and the larger of w_0.a, w_{N-1}.a; the integers t = ceil(lo) .. floor(hi), or,
+ *                          where there is none, the single station t = floor((lo + hi) / 2 + 0.5).  Index m = t - t_first.
+ *                segment   of station t: the segments [k, k+1] taken in the order of increasing a (k = 0, 1, .. where
+ *                          w_{N-1}.a >= w_0.a, else k = N-2, N-3, ..), the first whose larger a-end is >= t, or the last of
+ *                          them where there is none (the single station only): where t lies inside the node range this is the
+ *                          first segment that contains t.  lambda = (t - w_k.a) / (w_{k+1}.a - w_k.a), 0 for a zero
+ *                          denominator, clamped to [0, 1] (which changes it for the single station only).
+ *                          other(t) = floor(w_k.b + lambda (w_{k+1}.b - w_k.b) + 0.5);  node(t) = lambda < 0.5 ? k : k+1;
+ *                          inv_depth(t) = rho_k + lambda (rho_{k+1} - rho_k).
+ *                shape     (shape = 1) A_k, the 2 x 2 Jacobian at c of the map camera-0 pixel -> camera-1 pixel induced by the
+ *                          plane through P_k with normal `normal` (a world vector; all zero: camera 0's optical axis, the third
+ *                          row of R0), by central differences with a step of one level-0 pixel: f(p) = p undistorted in camera
+ *                          0, its ray met with the plane at z = ((P_k - o) . n) / (d . n), projected into camera 1;
+ *                          A_k = {(f(c + ex) - f(c - ex)).x / 2, (f(c + ey) - f(c - ey)).x / 2, the same of .y}, rounded to four
+ *                          floats {a11, a12, a21, a22}.  A point fails where the undistortion or the projection refuses it, d . n
+ *                          is 0, z is not > 0 or a value is not finite.
+ *                status    LK_GS_NO_CURVE: c outside camera 0's lens; a node the projection refuses (or a w_k that is not
+ *                          finite or not below 2^30 in size); node a-coordinates that are not monotone (equal neighbours are);
+ *                          a shape point that fails.  LK_GS_TOO_LONG: more than LK_EP_MAX_STATIONS stations, or a run of
+ *                          stations of one node times 2B+1 above LK_EP_MAX_GROUP.  Such a curve has no stations.  Else 0.
+ *   candidates (m, b), |b| <= B: the level-L displacement (t, other(t) + b) for axis x, (other(t) + b, t) for axis y.
+ *   template   lk_search_guesses', bit for bit: the samples, their rounding and clamping, St, Stt, TOO_LARGE, TOO_FEW,
+ *              TEXTURELESS.
+ *   position   template sample (x, y) reads the level-L deformed pixel (X, Y) + displacement, nearest neighbour.  shape = 0:
+ *              (X, Y) = (x, y).  shape = 1: lk_search_rotated's form with the full matrix A of node(t) about C = c 2^-L, every
+ *              float32 product and sum rounded on its own: dx = (float)x - Cx, dy = (float)y - Cy; rx = a11 dx + a12 dy,
+ *              ry = a21 dx + a22 dy; X = (int)floorf((Cx + rx) + 0.5f), Y likewise.
+ *   validity   every sample of the candidate inside the level-L deformed image, and n Sdd != Sd^2.  The score is
+ *              lk_search_guesses' expression from exact integer sums.
+ *   winner     the higher score, then the smaller |b|, then the smaller b, then the smaller m.
+ *   reported   profile[m] = the best score of station m over b, -2 where it has none;  runner_up = the best profile[m'] with
+ *              |m' - m_win| >= 2 (-2: none): the ambiguity along the curve;  n_valid = scored candidates over the whole curve;
+ *              station_refined = (float)(m_win + t) with t lk_search_rotated's parabola offset over profile[m_win - 1 ..
+ *              m_win + 1] (0 unless both neighbours exist and have a score and the denominator is negative; clamped to
+ *              [-0.5, 0.5]);  inv_depth = (float)(inv_depth(m_win) + |t| (inv_depth(m_win + sign t) - inv_depth(m_win))).  Both
+ *              are reported only.
+ *   status     checked in this order: NO_CURVE, TOO_LONG, TOO_LARGE, TOO_FEW, TEXTURELESS, NO_CANDIDATE, WEAK (best <=
+ *              min_score).
+ *   guess      an OK sector gets g[0], g[1] = (float)((double)displacement * 2^L), as the other searches form them; with
+ *              shape = 1 also g[2..5] = (a11 - 1.f, a12, a21, a22 - 1.f) of the winner's node, lk_search_rotated's layout; with
+ *              shape = 0 g[2..5] stay as they were.  A sector that is not OK keeps its six words, bit for bit.  The engine-held
+ *              guesses and the sequence history are written as lk_search_guesses writes them.
+ *   match      lk_epipolar_match; a sector without a winner reports zeros and scores of -2.
+ *   errors     LK_ERROR_BAD_DOMAIN with a message that starts with the function's name: whatever lk_search_guesses refuses of
+ *              `search` but the radius; LK_FM_U; shape = 1 on a model other than LK_FM_UVUXUYVXVY; a band outside 0 ..
+ *              LK_EP_MAX_BAND; n_nodes outside 2 .. LK_EP_MAX_NODES; depths that are not 0 < z_near <= z_far, both finite, in
+ *              the configuration or in an entry of depth_range; a shape other than 0 or 1; a normal that is not finite;
+ *              non-zero reserved words; cams NULL or a camera that lk_stereo_project refuses.
+ *   bytes      integer sums, unfused float steps, one table built on the host: a sector's match, profile and guess are the same
+ *              bits in any batch, mode, ring slot or call, whatever other sectors are in the launch. */
+#define LK_GS_NO_CURVE 6    /* further values of the LK_GS_* statuses */
+#define LK_GS_TOO_LONG 7
+#define LK_EP_MAX_BAND 8
+#define LK_EP_MAX_NODES 33
+#define LK_EP_MAX_STATIONS 2048
+#define LK_EP_MAX_GROUP 4096
+typedef struct lk_epipolar_search {   /* 80 bytes */
+  lk_guess_search search;   /* level, min_samples, min_score, def_slot: lk_search_guesses' meaning; radius: the band B */
+  int     n_nodes;          /* N, 2 .. LK_EP_MAX_NODES */
+  int     shape;            /* 0: the template is shifted; 1: mapped by the plane-induced Jacobian of the station's node */
+  int     reserved[3];      /* must be 0 */
+  double  z_near, z_far;    /* depth along camera 0's optical axis, 0 < z_near <= z_far */
+  double  normal[3];        /* shape = 1: the world normal of the surface; all zero: camera 0's optical axis */
+} lk_epipolar_search;
+typedef struct lk_epipolar_curve {    /* 32 bytes, one per sector */
+  int32_t axis;             /* 0: stations along x; 1: along y */
+  int32_t first_station;    /* t of station 0, level-L pixels */
+  int32_t n_stations;
+  int32_t first_index;      /* of station 0 in the station arrays */
+  int32_t status;           /* 0, LK_GS_NO_CURVE or LK_GS_TOO_LONG */
+  int32_t reserved[3];
+} lk_epipolar_curve;
+typedef struct lk_epipolar_match {    /* 64 bytes, one per sector */
+  int32_t shift_x, shift_y; /* the winner's displacement, level-L pixels */
+  int32_t station;          /* m of the winner */
+  int32_t band_offset;      /* b of the winner */
+  int32_t node;             /* node(t) of the winner's station */
+  int32_t n_samples, n_valid, status; /* status: LK_GS_* */
+  double  score, runner_up; /* -2 where there is none */
+  float   station_refined, inv_depth;
+  int32_t reserved[2];
+} lk_epipolar_match;
+struct lk_camera;             /* (defined with lk_stereo_points below) */
+/* cams: [2]; depth_range: NULL or host [S][2] {z_near, z_far} per sector; guesses_inout as for lk_search_guesses (NULL: the
+ * engine-held guesses, asynchronous on the engine stream) */
+int lk_search_epipolar(lk_engine *e, const lk_epipolar_search *cfg, const struct lk_camera *cams, const double *depth_range,
+                       float *guesses_inout);
+/* the matches of the last lk_search_epipolar, [S] (waits for it) */
+int lk_get_epipolar_search_info(lk_engine *e, lk_epipolar_match *out);
+/* its curves [S] (or NULL) and its best score per station, concatenated: sector s at curves_out[s].first_index, n_stations
+ * values, -2 where a station has no score (waits for it); *n_stations_out (or NULL): the length of the profile.  profile_out
+ * NULL: the curves and the length alone */
+int lk_get_epipolar_search_profile(lk_engine *e, lk_epipolar_curve *curves_out, double *profile_out, int *n_stations_out);
+/* Host, needs no engine: the table the kernels read, of n centres [n][2] (level-0 pixels of camera 0) at pyramid level
+ * `level` >= 0 (cfg->search.level is not read; of `search` only the radius is).  curves_out [n]; *n_stations_out: the stations
+ * of all curves together.  The station arrays other_out, node_out, inv_depth_out [capacity] and shape_out [n][N][4] (read only
+ * with cfg->shape = 1) may all be NULL to ask for the curves and the count alone; otherwise capacity must be at least that
+ * count.  LK_ERROR_BAD_DOMAIN for what `errors` lists of the configuration, the cameras and depth_range, for n < 1, a level
+ * outside 0 .. 30, a null centres, curves_out or n_stations_out, or a capacity that is too small. */
+int lk_epipolar_curves(const lk_epipolar_search *cfg, const struct lk_camera *cams, int n, const float *centres,
+                       const double *depth_range, int level, lk_epipolar_curve *curves_out, int *n_stations_out, int capacity, int32_t *other_out,
+                       int32_t *node_out, double *inv_depth_out, float *shape_out);
+
 /* ---- recovery pass: re-solve failed sectors from their converged neighbours ------------- */
 /* lk_reseed_failed repairs the engine-held records of the last lk_correlate_all* / lk_wait_results after the fact: a sector
  * that failed is given a guess extrapolated from neighbours that converged and is solved again; what was recovered seeds
@@ -1184,7 +1302,7 @@ int lk_lens_fit(lk_engine *e, const lk_lens_fit_config *cfg, const lk_lens *init
  *             min_neighbours < 3; non-zero reserved words; a camera that lk_stereo_project refuses; one point array null and
  *             the other not; device-held points with no lk_stereo_points before, with another n_frames or another sector
  *             count.
- *   scope     not covered: calibration of the rig; epipolar-constrained search; dense 3-D maps; lk_group, lk_tracker, the
+ *   scope     not covered: calibration of the rig; dense 3-D maps (the epipolar-constrained search is lk_search_epipolar); lk_group, lk_tracker, the
  *             report CSV and the CudaClass adapter. */
 typedef struct lk_camera {            /* 256 bytes */
   double  fx, fy, cx, cy, skew;       /* pixels; fx, fy > 0 */
